@@ -58,6 +58,31 @@ def hbm_traffic(label, width, height):
         return None
 
 
+DUMP_BYTES = 64 << 20     # --dump-outputs writes at most this much
+DUMP_SURFELS = 1 << 19    # surfel records written at most; a larger map is sampled (fixed seed)
+
+
+def dump_outputs(d, pipe):
+    """--dump-outputs DIR: what a caller of processScan reads after the last timed scan, as DIR/<name>.npy (float32 /
+    float64): the pose and the last increment, the map's pose table, the surfel map as (n, 16) float32 rows in
+    SURFEL_DTYPE field order (a fixed seeded sample when the map is larger than the budget; `surfels_index` holds the
+    row numbers taken) and the data / model frames of that scan.  Untimed: called after the timed region."""
+    out = {"pose": pipe.getCurrentPose(), "last_increment": pipe.lastIncrement(), "map_poses": pipe.map.poses()}
+    for which, name in ((0, "data"), (2, "model")):
+        f = pipe.frame(which)
+        out[name + "_vertex"], out[name + "_normal"], out[name + "_semantic"] = f.vertex, f.normal, f.semantic
+    surfels = pipe.map.getAllSurfels()
+    cap = min(DUMP_SURFELS, (DUMP_BYTES - sum(a.nbytes for a in out.values())) // (16 * 4 + 8))
+    index = np.arange(surfels.shape[0])
+    if index.size > cap:
+        index = np.sort(np.random.default_rng(0).choice(index.size, cap, replace=False))
+    out["surfels"] = np.stack([surfels[f][index].astype(np.float32) for f in surfels.dtype.names], axis=1)
+    out["surfels_index"] = index.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def cached_scan(k, W, H):
     """synthetic scan k; with SUMA_SCAN_CACHE=<dir> the generated arrays are kept there (A/B loops inside one GPU session
     run bench.py many times on the same scans: generation is ~25 ms per scan, a load ~2 ms)"""
@@ -319,7 +344,12 @@ def main():
                     help="single: BASELINE configs[1] (the bench contract); hypotheses: configs[2], 8 ICP hypotheses per scan "
                          "sharded over the ranks; sequences11: configs[3], the 11 KITTI sequence lengths (scaled) LPT-assigned")
     ap.add_argument("--kernels-json", default=os.path.join(ROOT, "gpurun_out", "bench_kernels.json"))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="single mode: write what the timed path computed in its last step as DIR/<name>.npy (rank 0, "
+                         "at most 64 MB; see dump_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "single":
+        ap.error("--dump-outputs is implemented for --mode single only")
     rc = self_launch_if_needed(args)
     if rc is not None:
         raise SystemExit(rc)
@@ -497,6 +527,8 @@ def main():
     dominant = [k for k in ctx.profile_get() if k["launches"]]
     map_size = pipe.map.size()
     pose = pipe.getCurrentPose()
+    if args.dump_outputs and rank == 0:  # before any untimed leg below moves the pipeline on
+        dump_outputs(args.dump_outputs, pipe)
     # ---- the same pipeline fed the way the reference's caller feeds processScan(const rv::Laserscan&)
     #      (SurfelMapping.cpp:175, 323-331): pageable host vectors, one blocking call per scan, no look-ahead.  The next K
     #      scans of the sequence; NOT the headline (the bench contract times resident inputs), reported beside it.

@@ -8,10 +8,16 @@ software-rasteriser interface.  These tests (CPU only; skipped where Mesa is not
   * own pass-through shaders fed with the ORACLE'S vertices -- nothing but GL's clipping / rasterisation / depth test
     decides the outcome, so the comparison with oracle/o_map.c is exact up to what the GL specification leaves open
     (a pixel centre lying ON an edge, sub-pixel snapping of the last 1/256 pixel);
-  * the reference's OWN render_surfels.{vert,geom,frag} (read from /root/reference/src/shader) on a map the oracle built:
-    here the driver's atan / asin / FMA contraction and its attribute interpolation differ from include/suma_detmath.h in
-    the last ulps, so agreement is measured, not demanded: >= 97 % of the texels carry the same surfel.
+  * the reference's OWN render_surfels.{vert,geom,frag} on a map the oracle built: here the driver's atan / asin / FMA
+    contraction and its attribute interpolation differ from include/suma_detmath.h in the last ulps, so agreement is
+    measured, not demanded: >= 97 % of the texels carry the same surfel.
+
+What the reference's shaders produced in llvmpipe for the tests that need nothing else on the reference side is recorded in
+tests/golden/gl_reference_900x64.npz (tests/golden/make_gl_reference_golden.py, where the reference's sources and Mesa
+exist), together with a digest of the inputs the oracle gave them; those tests need neither here.  Each GL image is
+stored as the XOR of its bits with the oracle's image of the same pass (see `recorded`).
 """
+import hashlib
 import os
 
 import numpy as np
@@ -21,6 +27,32 @@ from conftest import get_scan
 from semantic_suma_amd.types import params_with_size
 
 W, H = 900, 64
+GL_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gl_reference_900x64.npz")
+
+
+def digest(*arrays):
+    """SHA-256 of the bytes of the arrays, in order (the same function as tests/golden/make_gl_reference_golden.py)"""
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def gl_golden(key, *inputs):
+    """the recorded GL outputs, after checking that `inputs` are the ones the recording of `key` was made from"""
+    z = np.load(GL_GOLDEN)
+    assert str(z[key + "_digest"]) == digest(*inputs), \
+        f"{key}: the oracle made other inputs than were recorded; re-record: python tests/golden/make_gl_reference_golden.py"
+    return z
+
+
+def recorded(z, name, oracle_image):
+    """GL image `name`, rebuilt bit for bit from its stored XOR with the oracle's image of the same pass -- after checking
+    that `oracle_image` is the very image the XOR was taken against, so what comes back is the recorded GL output"""
+    oracle_image = np.ascontiguousarray(oracle_image)
+    assert digest(oracle_image) == str(z[name + "_oracle_digest"]), \
+        f"{name}: the oracle's image is not the recorded one; re-record: python tests/golden/make_gl_reference_golden.py"
+    return (oracle_image.view(np.uint32) ^ z[name + "_xor"]).view(oracle_image.dtype)
 
 
 @pytest.fixture(scope="module")
@@ -127,15 +159,16 @@ def test_quads_with_disc_and_depth_test(gl, scene):
     assert np.mean(want != got) < 0.01 and np.mean((want >= 0) != (got >= 0)) < 0.004
 
 
-def test_reference_render_shaders_in_gl(gl, scene):
-    """SurfelMap::render_active through the reference's own GLSL in llvmpipe against the oracle's rendering of the same
-    map: the same surfel wins >= 97 % of the texels (measured 98.1 %; the rest are silhouette texels where the driver's
-    atan / asin / FMA choices move a corner across a pixel centre or a disc boundary)."""
+def test_reference_render_shaders_in_gl(scene):
+    """SurfelMap::render_active through the reference's own GLSL in llvmpipe (recorded) against the oracle's rendering of
+    the same map: the same surfel wins >= 97 % of the texels (measured 98.1 %; the rest are silhouette texels where the
+    driver's atan / asin / FMA choices move a corner across a pixel centre or a disc boundary)."""
     p, ctx, pose, ts = scene["p"], scene["ctx"], scene["pose"], scene["ts"]
+    z = gl_golden("scene", ctx.map_surfels(), ctx.map_poses(ts + 1), pose, np.int64(ts))
     out = ctx.frame(model=True)
     ctx.map_render(pose, pose, 0.0, out)
     o = [ctx.map_frame(1).map(m) for m in range(3)]
-    g = gl.SurfelRenderer(p).render(ctx.map_surfels(), ctx.map_poses(ts + 1).reshape(-1, 16), pose, 0.0, ts - 100, False)
+    g = [recorded(z, name, o[m]) for m, name in enumerate(("render_vertex", "render_normal", "render_semantic"))]
     va, vb = o[0][..., 3] > 0.5, g[0][..., 3] > 0.5
     assert va.sum() > 30000
     same = va & vb & np.all(np.abs(o[0] - g[0]) <= 1e-4 * (1.0 + np.abs(o[0])), axis=-1)
@@ -162,8 +195,8 @@ def test_committed_gl_golden_is_reproduced_by_the_oracle():
     assert vb.sum() > 5000 and same.sum() >= 0.97 * max(va.sum(), vb.sum())
 
 
-def test_reference_jacobian_shaders_in_gl(gl, oracle_lib):
-    """Frame2Model::jacobianProducts through the reference's own Frame2Model_jacobians.{vert,geom,frag} in llvmpipe:
+def test_reference_jacobian_shaders_in_gl(oracle_lib):
+    """Frame2Model::jacobianProducts through the reference's own Frame2Model_jacobians.{vert,geom,frag} in llvmpipe (recorded):
     LINEAR rectangle samplers with CLAMP_TO_BORDER on all six maps, 16 points per geometry-shader invocation blended
     (GL_ONE, GL_ONE) into the 2 x 8 RGB32F target, unpacked as Frame2Model.cpp:214-227.  This pins the conventions the
     oracle's K6 rests on -- texel centres at integer + 0.5, the four-tap weights, border colour 0, the layout of the 48
@@ -178,9 +211,9 @@ def test_reference_jacobian_shaders_in_gl(gl, oracle_lib):
         frames.append(ora.preprocess(pts, lab, prob, k, ora.frame()))
     T = np.eye(4)
     T[0, 3] = 0.9
-    J = gl.Jacobians(p)
+    z = gl_golden("jacobian", *[frames[0].map(m) for m in range(3)], *[frames[1].map(m) for m in range(3)], T)
     for iteration in (0, 1):
-        b = J.run([frames[1].map(m) for m in range(3)], [frames[0].map(m) for m in range(3)], T, iteration)
+        b = z["jacobian_b"][iteration]
         F, acc, JtJ, Jtr, st = ora.jacobian_products(frames[1], frames[0], T, iteration)
         valid, Fg, outlier, invalid = b[42], b[43], b[44], b[46]
         assert st.valid > 5000
@@ -193,8 +226,8 @@ def test_reference_jacobian_shaders_in_gl(gl, oracle_lib):
         assert np.allclose(b[36:42], Jtr, rtol=0, atol=0.01 * np.abs(Jtr).max())
 
 
-def test_reference_vertexmap_shaders_in_gl(gl, oracle_lib):
-    """Preprocessing::process, first pass, through the reference's gen_vertexmap.{vert,frag} in llvmpipe: size-1 points,
+def test_reference_vertexmap_shaders_in_gl(oracle_lib):
+    """Preprocessing::process, first pass, through the reference's gen_vertexmap.{vert,frag} in llvmpipe (recorded): size-1 points,
     two colour attachments, DEPTH24_STENCIL8 + GL_LESS, the label / prob attribute pointers 4 / 5 floats into their
     buffers (quirk B-1).  The synthetic scanner fires at exact azimuth steps, so many points sit ON a texel border and the
     driver's atan decides the column: >= 98 % of the 57 600 texels are bit-equal to the oracle's vertex map (measured
@@ -202,17 +235,18 @@ def test_reference_vertexmap_shaders_in_gl(gl, oracle_lib):
     p = params_with_size(W)
     ora = oracle_lib.Oracle(p)
     pts, lab, prob, _ = get_scan(3, W, True)
-    V = gl.VertexMap(p)
-    for ts in (3, 20):
-        gv, gs = V.run(pts, lab, prob, ts)
-        ov = ora.preprocess(pts, lab, prob, ts, ora.frame()).map(0)
+    z = gl_golden("vertexmap", pts, lab, prob)
+    for i, ts in enumerate((3, 20)):
+        frame = ora.preprocess(pts, lab, prob, ts, ora.frame())  # owns the memory map(0) views: keep it alive
+        ov = frame.map(0)
+        gv = recorded(z, f"vertexmap_{i}", ov)
         same = np.all(ov.view(np.uint32) == gv.view(np.uint32), axis=-1)
         assert same.mean() >= 0.98
         assert abs(int((ov[..., 3] > 0.5).sum()) - int((gv[..., 3] > 0.5).sum())) <= 0.005 * (ov[..., 3] > 0.5).sum()
 
 
-def test_reference_indexmap_shaders_in_gl(gl, oracle_lib):
-    """SurfelMap::renderIndexmap (K7) through the reference's gen_indexmap.{vert,frag} in llvmpipe against the index map
+def test_reference_indexmap_shaders_in_gl(oracle_lib):
+    """SurfelMap::renderIndexmap (K7) through the reference's gen_indexmap.{vert,frag} in llvmpipe (recorded) against the index map
     the oracle's update made of the same map from the same pose: size-1 points at texel centres, GL_LESS on 24-bit depth,
     the earlier surfel on equal depth.  The shader snaps to texel centres itself, so only the driver's atan / asin can
     move a surfel to the neighbouring texel: >= 97 % of the texels name the same surfel (measured 99.3 % of 57 600)."""
@@ -231,7 +265,7 @@ def test_reference_indexmap_shaders_in_gl(gl, oracle_lib):
     inv = np.eye(4, dtype=np.float32)  # the rigid inverse in float, as the HIP path and the oracle form it
     inv[:3, :3] = R.T
     inv[:3, 3] = -(R.T @ t)
-    got, gv = gl.IndexMap(p).run(before, ctx.map_poses(ts + 1).reshape(-1, 16), pose, inv)
+    got = recorded(gl_golden("indexmap", before, ctx.map_poses(ts + 1), pose, inv), "indexmap", want)
     assert want.shape == got.shape and (want > 0).sum() > 20000
     same = want == got
     assert same.mean() >= 0.97, same.mean()
@@ -442,14 +476,15 @@ def test_reference_radius_and_compose_shaders_in_gl(gl, oracle_lib):
 
 
 
-def test_reference_render_composed_in_gl(gl, scene, oracle_lib):
+def test_reference_render_composed_in_gl(scene, oracle_lib):
     """SurfelMap::render_composed (SurfelMap.cpp:1116-1165: GL_LEQUAL, the old surfels from pose_old, then -- without
-    clearing -- the new ones from pose_new into the same depth buffer) through the reference's shaders in llvmpipe against
+    clearing -- the new ones from pose_new into the same depth buffer) through the reference's shaders in llvmpipe (recorded) against
     the oracle's composed frame.  The 12-scan map is given timestamp 106, so that timestamp_ - composeSurfelAge_ = 6 makes
     the surfels of scans 0-5 "old" and those of scans 6-11 "new" and both passes draw: >= 97 % of the texels carry the
     same surfel."""
     p, ctx, pose, ts = scene["p"], scene["ctx"], scene["pose"], 106
     surfels, poses = ctx.map_surfels(), ctx.map_poses(int(scene["ts"]) + 1)
+    z = gl_golden("scene", surfels, poses, pose, np.int64(scene["ts"]))
     ora = oracle_lib.Oracle(p)
     ora.map_upload(surfels, ts)
     ora.map_update_poses(poses.reshape(-1, 4, 4).transpose(0, 2, 1))
@@ -457,14 +492,10 @@ def test_reference_render_composed_in_gl(gl, scene, oracle_lib):
     pose_old[0, 3] -= 0.4  # a loop-closure candidate seen from a slightly different place
     ora.map_render_composed(pose_old, pose, 0.0)
     want = [ora.map_frame(2).map(m) for m in range(2)]
-    R = gl.SurfelRenderer(p)
-    pt = poses.reshape(-1, 16)
-    tg = R.render_pass(surfels, pt, pose_old, 0.0, ts - 100, True, depth_func="LEQUAL")
-    old_only = tg[0].read()[..., 3] > 0.5
-    tg = R.render_pass(surfels, pt, pose, 0.0, ts - 100, False, depth_func="LEQUAL", targets=tg, clear_first=False)
-    got = [t.read() for t in tg]
+    old_only = int(z["composed_old_only_texels"])  # texels the old pass alone drew
+    got = [recorded(z, "composed_vertex", want[0]), recorded(z, "composed_normal", want[1])]
     va, vb = want[0][..., 3] > 0.5, got[0][..., 3] > 0.5
-    assert va.sum() > 30000 and old_only.sum() > 5000 and vb.sum() > old_only.sum() + 5000, "both passes must draw"
+    assert va.sum() > 30000 and old_only > 5000 and vb.sum() > old_only + 5000, "both passes must draw"
     same = va & vb & np.all(np.abs(want[0] - got[0]) <= 1e-4 * (1.0 + np.abs(want[0])), axis=-1)
     print(f"render_composed in GL: {same.sum()} of {max(va.sum(), vb.sum())} texels carry the same surfel")
     assert same.sum() >= 0.97 * max(va.sum(), vb.sum())

@@ -1,7 +1,8 @@
 """CPU tests of the phase API of the scan pipeline on the oracle side (TEST INFRASTRUCTURE), and of the host math the
 loop-closure hooks add.  The GPU legs (HIP pipeline == oracle, bit for bit) are in tests/test_gpu_phases.py."""
+import os
+
 import numpy as np
-import pytest
 
 from conftest import get_scan
 from semantic_suma_amd.types import params_with_size
@@ -30,16 +31,16 @@ def test_phases_equal_the_single_call(oracle_lib):
 
 
 def test_se3_log_is_the_reference_function(oracle_lib):
-    """ora_se3_log against SE3::log of the reference's lie_algebra.cpp compiled where it lies (oracle/_ref)"""
-    pyref = pytest.importorskip("oracle.pyref")
-    if not pyref.available():
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
+    """ora_se3_log against SE3::log of the reference's lie_algebra.cpp compiled where it lies (oracle/_ref), recorded on
+    200 poses in tests/golden/se3_log_200.npz (tests/golden/make_se3_log_golden.py)"""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "se3_log_200.npz"))
     rng = np.random.default_rng(5)
     for k in range(200):
         x = rng.uniform(-1, 1, 6) * (1e-6 if k % 10 == 0 else 1.0)
         x[3:] *= 0.5 if k % 3 else 3.0
         T = oracle_lib.se3_exp(x)
-        a, b = oracle_lib.se3_log(T), pyref.se3_log(T)
+        assert np.array_equal(T, z["T"][k]), f"pose {k} is not the recorded one"
+        a, b = oracle_lib.se3_log(T), z["log"][k]
         assert np.allclose(a, b, rtol=0, atol=1e-13), (k, a - b)
     assert np.array_equal(oracle_lib.se3_log(np.eye(4)), np.zeros(6))
 
