@@ -946,9 +946,9 @@ __global__ void __launch_bounds__(ICP_THREADS) k_icp_finish(const long long* pin
   icp_iter_body<false>(g, GN_KARG_OFFSET(2)); /* two leading pointers, then IterArgs */
 }
 
-static IcpArgs make_args(suma_ctx* c) {
+static IcpArgs make_args(suma_ctx* c, const GnChain& ch) {
   IcpArgs a;
-  const suma_frame *cur = c->icp_current, *mod = c->icp_model;
+  const suma_frame *cur = ch.current, *mod = ch.model;
   a.Vd = cur->map[SUMA_MAP_VERTEX];
   a.Nd = cur->map[SUMA_MAP_NORMAL];
   a.Sd = cur->map[SUMA_MAP_SEMANTIC];
@@ -961,16 +961,14 @@ static IcpArgs make_args(suma_ctx* c) {
   a.Hm = (int32_t)mod->height;
   a.fov_up = c->pd.fov_up;
   a.fov = c->pd.fov;
-  /* Frame2Model.cpp:66-67; an adapter-side Frame2Model object may carry its own values (suma_icp_set_objective) */
-  const float max_angle = c->obj_set ? c->obj.icp_max_angle : c->p.icp_max_angle;
-  a.angle_thresh = (float)cos((double)max_angle * M_PI / 180.0);
-  a.distance_thresh = c->obj_set ? c->obj.icp_max_distance : c->p.icp_max_distance;
-  a.factor = c->obj_set ? c->obj.factor : c->p.factor;
+  a.angle_thresh = (float)cos((double)ch.obj.icp_max_angle * M_PI / 180.0); /* Frame2Model.cpp:66-67 */
+  a.distance_thresh = ch.obj.icp_max_distance;
+  a.factor = ch.obj.factor;
   a.k8_enabled = 0;
   a.k8 = launch_k8_out(c);
   a.k8_ds = c->ds;
-  a.weight_function = c->obj_set ? c->obj.weight_function : c->p.weight_function;
-  a.bilinear = c->obj_set ? c->obj.bilinear_sampling : c->p.bilinear_sampling;
+  a.weight_function = ch.obj.weight_function;
+  a.bilinear = ch.obj.bilinear_sampling;
   a.P = (uint32_t)a.W * (uint32_t)a.H;
   return a;
 }
@@ -981,32 +979,25 @@ static long long* part_buf(suma_ctx* c, uint32_t launch) {
   return (long long*)c->gn_partial + (size_t)(launch % 3u) * SUMA_MAX_HYP * ICP_RECORDS * SUMA_ACC_WORDS;
 }
 
-/* iteration0 / iteration0_rest: Frame2Model::iteration_ the first / every other chain of the batch starts with (0 right
- * behind a setData; > 0 for a minimisation that follows another one on the same setData, SurfelMapping.cpp:693-700) */
-hipError_t launch_gn_init(suma_ctx* c, const double* h_T0s, uint32_t n_hyp, int with_history, uint32_t iteration0,
-                          uint32_t iteration0_rest) {
-  double* hist = with_history ? c->gn_history : nullptr;
+hipError_t launch_gn_init(suma_ctx* c, const GnChain& ch) {
   c->gn_launch = 0;
-  c->gn_init_pending = 0;
-  if (n_hyp == 1) {
-    /* single chain: no launch here, the first k_icp_iter takes the start state by value */
-    for (int i = 0; i < 16; ++i) c->gn_T0_host[i] = h_T0s[i];
-    c->gn_iteration0 = iteration0;
-    c->gn_init_pending = 1;
-  } else {
-    hipError_t e = hipMemcpyAsync(c->gn_T0s, h_T0s, (size_t)n_hyp * 16 * sizeof(double), hipMemcpyHostToDevice, c->ls);
+  /* a single chain needs no launch here: its first k_icp_step takes the start state by value */
+  if (ch.n_hyp > 1) {
+    hipError_t e = hipMemcpyAsync(c->gn_T0s, ch.T0s, (size_t)ch.n_hyp * 16 * sizeof(double), hipMemcpyHostToDevice, c->ls);
     if (e != hipSuccess) return e;
-    k_gn_init<<<n_hyp, 64, 0, c->ls>>>(gn_buf(c, 0), c->gn_T0s, hist, iteration0, iteration0_rest);
+    k_gn_init<<<ch.n_hyp, 64, 0, c->ls>>>(gn_buf(c, 0), c->gn_T0s, ch.with_history ? c->gn_history : nullptr,
+                                           ch.iteration0, ch.iteration0_rest);
   }
   return hipGetLastError();
 }
 
 /* one launch of the chain; pixel = 0 is the closing consume-only launch (one block per hypothesis) */
-hipError_t launch_icp_iteration(suma_ctx* c, uint32_t n_hyp, uint32_t max_iter, double epsilon, double delta,
-                                int eval_only, int with_history, int pixel) {
+hipError_t launch_icp_iteration(suma_ctx* c, const GnChain& ch, int eval_only, int pixel) {
+  const uint32_t n_hyp = ch.n_hyp;
+  const bool self_closing = pixel && eval_only && n_hyp == 1;
   IterArgs g;
-  g.a = make_args(c);
-  g.a.k8_enabled = (pixel && eval_only && n_hyp == 1 && c->gn_fuse_k8) ? 1 : 0;
+  g.a = make_args(c, ch);
+  g.a.k8_enabled = (self_closing && ch.fuse_k8) ? 1 : 0;
   g.gin = gn_buf(c, c->gn_launch);
   g.gout = gn_buf(c, c->gn_launch + 1);
   /* the accumulator rotation runs across chains (gn_launch restarts with every chain, this does not) */
@@ -1018,26 +1009,25 @@ hipError_t launch_icp_iteration(suma_ctx* c, uint32_t n_hyp, uint32_t max_iter, 
   c->gn_part_dirty[(rot + 2) % 3u] = 0;
   if (pixel && c->gn_part_dirty[(rot + 1) % 3u] < n_hyp) c->gn_part_dirty[(rot + 1) % 3u] = n_hyp;
   g.nblocks = c->icp_blocks;
-  g.max_iter = max_iter;
-  g.epsilon = epsilon;
-  g.delta_thr = delta;
+  g.max_iter = ch.max_iterations > 0 ? ch.max_iterations : 0xffffffffu;
+  g.epsilon = ch.epsilon;
+  g.delta_thr = ch.delta;
   g.eval_only = eval_only;
   g.pixel = pixel;
-  g.history = with_history ? c->gn_history : nullptr;
+  g.history = ch.with_history ? c->gn_history : nullptr;
   g.history_cap = c->gn_history_cap;
-  g.emit_pose = (!pixel && c->gn_emit_pose) ? 1 : 0;
-  for (int i = 0; i < 16; ++i) g.pose_base.m[i] = c->gn_pose_base[i];
+  g.emit_pose = (!pixel && ch.pose_base) ? 1 : 0;
+  for (int i = 0; i < 16; ++i) g.pose_base.m[i] = ch.pose_base ? ch.pose_base[i] : 0.0;
   g.pose_block = c->pose_block;
-  g.host_out = pixel ? nullptr : c->gn_host_out;
-  g.host_seq = c->gn_host_seq;
-  g.host_full = c->gn_host_full;
+  g.host_out = pixel ? nullptr : ch.report;
+  g.host_seq = ch.report_seq;
+  g.host_full = ch.report_full;
   g.ds = c->ds;
-  g.fused_report = (pixel && eval_only && n_hyp == 1) ? c->gn_fused_report : nullptr;
+  g.fused_report = self_closing ? ch.report : nullptr;
   g.fused_counter = &c->ds->reserved0;
-  g.init = c->gn_init_pending;
-  g.iteration0 = c->gn_iteration0;
-  for (int i = 0; i < 16; ++i) g.T0.m[i] = c->gn_T0_host[i];
-  c->gn_init_pending = 0;
+  g.init = (n_hyp == 1 && c->gn_launch == 0) ? 1 : 0; /* a single chain starts in its first launch */
+  g.iteration0 = ch.iteration0;
+  for (int i = 0; i < 16; ++i) g.T0.m[i] = g.init ? ch.T0s[i] : 0.0;
   c->gn_launch += 1;
   dim3 grid(pixel ? c->icp_blocks : 1, n_hyp);
   if (pixel)

@@ -373,13 +373,7 @@ extern "C" int suma_ctx_create(const suma_params* params, int hip_device, suma_c
     CK(hipHostMalloc((void**)&c->h_rec, 2 * sizeof(HostResult), hipHostMallocDefault));
     memset(c->h_rec, 0, 2 * sizeof(HostResult));
     c->rec_seq = 0;
-    c->gn_host_full = 0;
-    c->gn_emit_pose = 0;
-    c->gn_host_out = nullptr;
-    c->gn_fused_report = nullptr;
-    c->gn_fuse_k8 = 0;
     c->k8_fused_frame = nullptr;
-    c->gn_host_seq = 0;
     c->cache_slots = nullptr;
     /* submap cache arena */
     /* default 16 x max_surfels (4.3 GB at the reference's 4.19 M): every tile of a KITTI-length
@@ -755,6 +749,24 @@ static void unpack_acc(suma_ctx* c, const HostResult& h, double* JtJ, double* Jt
   if (acc) memcpy(acc, g.acc, sizeof(g.acc));
 }
 
+/* the chain of a C-ABI call: the adapter's frames (suma_icp_set_data) and objective (suma_icp_set_objective; the ctx
+ * parameters while none is set), the ctx's iteration budget and stopping tests, no history, nothing reported */
+static GnChain gn_chain_ctx(const suma_ctx* c, const double* T0s, uint32_t n_hyp) {
+  const suma_params& p = c->p;
+  GnChain ch = {};
+  ch.current = c->icp_current;
+  ch.model = c->icp_model;
+  ch.obj = c->obj_set ? c->obj
+                      : suma_icp_objective{p.icp_max_distance, p.icp_max_angle, p.weight_function, p.factor,
+                                           p.bilinear_sampling};
+  ch.max_iterations = p.max_iterations;
+  ch.epsilon = (double)p.stopping_threshold;
+  ch.delta = (double)p.delta;
+  ch.T0s = T0s;
+  ch.n_hyp = n_hyp;
+  return ch;
+}
+
 extern "C" int suma_icp_jacobian_products(suma_ctx* c, const double pose[16], uint32_t iteration, double JtJ[36],
                                           double Jtr[6], int64_t* acc, suma_icp_stats* stats) {
   if (!c || !pose) return SUMA_ERR_INVALID;
@@ -762,7 +774,9 @@ extern "C" int suma_icp_jacobian_products(suma_ctx* c, const double pose[16], ui
   if (c->gate_pending) CK(flush_gate(c));
   accessed(c, c->icp_current);
   accessed(c, c->icp_model);
-  CK(launch_gn_init(c, pose, 1, 0, iteration));
+  GnChain ch = gn_chain_ctx(c, pose, 1);
+  ch.iteration0 = iteration;
+  CK(launch_gn_init(c, ch));
   /* ONE launch: the pixel pass closes itself (its last block totals the accumulator records) and reports the sums
    * straight into a pinned host record the host polls -- no consume-only launch, no copy command, no stream
    * synchronisation (round 3: two launches + hipMemcpyAsync + hipStreamSynchronize).  If the frame is data-sized and
@@ -775,17 +789,13 @@ extern "C" int suma_icp_jacobian_products(suma_ctx* c, const double pose[16], ui
                            c->k8_fused_stamp == c->timestamp && c->k8_fused_params == c->params_version);
   HostResult* rec = &c->h_rec[1];
   c->rec_seq += 1;
+  ch.report = rec;
+  ch.report_seq = c->rec_seq;
+  ch.report_full = 1;
+  ch.fuse_k8 = k8_wanted ? 1 : 0;
   {
     ProfScope ps(c, k8_wanted ? "k6k8_stats_radius" : "k6_icp_step", (96.0 + (k8_wanted ? 81.0 : 0.0)) * (double)cur->width * cur->height);
-    c->gn_fused_report = rec;
-    c->gn_host_seq = c->rec_seq;
-    c->gn_host_full = 1;
-    c->gn_fuse_k8 = k8_wanted ? 1 : 0;
-    hipError_t e = launch_icp_iteration(c, 1, 1, 0.0, 0.0, 1, 0, 1);
-    c->gn_fuse_k8 = 0;
-    c->gn_host_full = 0;
-    c->gn_fused_report = nullptr;
-    CK(e);
+    CK(launch_icp_iteration(c, ch, 1, 1));
   }
   if (k8_wanted) {
     c->k8_fused_frame = cur;
@@ -809,30 +819,28 @@ extern "C" int suma_icp_jacobian_products(suma_ctx* c, const double pose[16], ui
  * converged after SUMA_GN_HARD_CAP iterations is reported as an error instead of returned silently. */
 #define SUMA_GN_CHUNK 32u
 #define SUMA_GN_HARD_CAP (1u << 16)
-static int enqueue_minimize(suma_ctx* c, const double* T0s, uint32_t n_hyp, int with_history, uint32_t iteration0 = 0,
-                            uint32_t iteration0_rest = 0) {
-  const uint32_t max_iter = c->p.max_iterations;
-  const uint32_t iter_arg = max_iter > 0 ? max_iter : 0xffffffffu;
+static int enqueue_minimize(suma_ctx* c, const GnChain& ch) {
+  const uint32_t max_iter = ch.max_iterations, n_hyp = ch.n_hyp;
   if (c->gate_pending) CK(flush_gate(c)); /* the chain reads the frame the side stream preprocessed (k_sync.hip) */
-  accessed(c, c->icp_current);
-  accessed(c, c->icp_model);
-  if (with_history) c->hist_seq += 1; /* this chain overwrites the device-side pose history */
-  CK(launch_gn_init(c, T0s, n_hyp, with_history, iteration0, iteration0_rest));
+  accessed(c, ch.current);
+  accessed(c, ch.model);
+  if (ch.with_history) c->hist_seq += 1; /* this chain overwrites the device-side pose history */
+  CK(launch_gn_init(c, ch));
   /* launch j runs the pixel phase of iteration j after consuming the sums of iteration j-1; the
    * closing launch only consumes */
-  const double launch_bytes = 96.0 * (double)c->icp_current->width * c->icp_current->height * n_hyp;
+  const double launch_bytes = 96.0 * (double)ch.current->width * ch.current->height * n_hyp;
   if (max_iter > 0) {
     /* one event pair around the whole chain of identical pixel launches: per-launch time = chain / N */
     ProfScope ps(c, "k6_icp_step", launch_bytes * max_iter, max_iter);
     for (uint32_t i = 0; i < max_iter; ++i)
-      CK(launch_icp_iteration(c, n_hyp, iter_arg, (double)c->p.stopping_threshold, (double)c->p.delta, 0, with_history, 1));
+      CK(launch_icp_iteration(c, ch, 0, 1));
   } else {
     uint32_t total = 0;
     for (;;) {
       {
         ProfScope ps(c, "k6_icp_step", launch_bytes * SUMA_GN_CHUNK, SUMA_GN_CHUNK);
         for (uint32_t i = 0; i < SUMA_GN_CHUNK; ++i)
-          CK(launch_icp_iteration(c, n_hyp, iter_arg, (double)c->p.stopping_threshold, (double)c->p.delta, 0, with_history, 1));
+          CK(launch_icp_iteration(c, ch, 0, 1));
       }
       total += SUMA_GN_CHUNK;
       CK(hipMemcpyAsync(c->h_gn, gn_result(c), (size_t)n_hyp * sizeof(GnState), hipMemcpyDeviceToHost, c->stream));
@@ -847,7 +855,7 @@ static int enqueue_minimize(suma_ctx* c, const double* T0s, uint32_t n_hyp, int 
   }
   {
     ProfScope ps(c, "k6_icp_finish", 0.0);
-    CK(launch_icp_iteration(c, n_hyp, iter_arg, (double)c->p.stopping_threshold, (double)c->p.delta, 0, with_history, 0));
+    CK(launch_icp_iteration(c, ch, 0, 0));
   }
   return SUMA_OK;
 }
@@ -862,14 +870,14 @@ extern "C" int suma_icp_minimize(suma_ctx* c, const double T0[16], double T_out[
   if (!c->icp_current || !c->icp_model) return fail(c, SUMA_ERR_INVALID, "suma_icp_set_data has not been called");
   HostResult* rec = &c->h_rec[0];
   c->rec_seq += 1;
-  c->gn_host_out = rec;
-  c->gn_host_seq = c->rec_seq;
-  c->gn_host_full = 1;
-  const uint32_t iteration0 = c->icp_iteration0; /* suma_icp_set_iteration, one shot */
+  GnChain ch = gn_chain_ctx(c, T0, 1);
+  ch.with_history = 1;
+  ch.iteration0 = c->icp_iteration0; /* suma_icp_set_iteration, one shot */
   c->icp_iteration0 = 0;
-  int r = enqueue_minimize(c, T0, 1, 1, iteration0);
-  c->gn_host_out = nullptr;
-  c->gn_host_full = 0;
+  ch.report = rec;
+  ch.report_seq = c->rec_seq;
+  ch.report_full = 1;
+  int r = enqueue_minimize(c, ch);
   if (r) return r;
   const uint64_t mark = c->enq_seq;
   r = wait_host_result(c, rec, c->rec_seq);
@@ -906,11 +914,10 @@ extern "C" int suma_icp_history(suma_ctx* c, double* history, uint32_t history_c
   return SUMA_OK;
 }
 
-extern "C" int suma_icp_minimize_batch(suma_ctx* c, const double* T0s, uint32_t n_hyp, double* T_out,
-                                       suma_icp_stats* stats) {
-  if (!c || !T0s || !T_out || n_hyp == 0 || n_hyp > SUMA_MAX_HYP) return SUMA_ERR_INVALID;
-  if (!c->icp_current || !c->icp_model) return fail(c, SUMA_ERR_INVALID, "suma_icp_set_data has not been called");
-  int r = enqueue_minimize(c, T0s, n_hyp, 0);
+/* n_hyp chains side by side; poses and statistics read back */
+static int minimize_batch(suma_ctx* c, const GnChain& ch, double* T_out, suma_icp_stats* stats) {
+  const uint32_t n_hyp = ch.n_hyp;
+  int r = enqueue_minimize(c, ch);
   if (r) return r;
   CK(hipMemcpyAsync(c->h_gn, gn_result(c), (size_t)n_hyp * sizeof(GnState), hipMemcpyDeviceToHost, c->stream));
   CK(hipStreamSynchronize(c->stream));
@@ -920,6 +927,13 @@ extern "C" int suma_icp_minimize_batch(suma_ctx* c, const double* T0s, uint32_t 
     if (stats) fill_stats(c->h_gn[h], &stats[h]);
   }
   return SUMA_OK;
+}
+
+extern "C" int suma_icp_minimize_batch(suma_ctx* c, const double* T0s, uint32_t n_hyp, double* T_out,
+                                       suma_icp_stats* stats) {
+  if (!c || !T0s || !T_out || n_hyp == 0 || n_hyp > SUMA_MAX_HYP) return SUMA_ERR_INVALID;
+  if (!c->icp_current || !c->icp_model) return fail(c, SUMA_ERR_INVALID, "suma_icp_set_data has not been called");
+  return minimize_batch(c, gn_chain_ctx(c, T0s, n_hyp), T_out, stats);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -1442,13 +1456,6 @@ extern "C" int suma_map_cache_stats(suma_ctx* c, uint32_t* used, uint32_t* capac
 /* ---------------------------------------------------------------------------------------------
  * loop-closure verification (SurfelMapping.cpp:662-757)
  * ------------------------------------------------------------------------------------------- */
-static void mul4_dd(const double* A, const double* B, double* C) {
-  for (int c = 0; c < 4; ++c)
-    for (int r = 0; r < 4; ++r)
-      C[4 * c + r] =
-          ((A[r] * B[4 * c] + A[4 + r] * B[4 * c + 1]) + A[8 + r] * B[4 * c + 2]) + A[12 + r] * B[4 * c + 3];
-}
-
 /* One speculative round of the verification: the chains of `n` initial guesses as ONE batched minimisation (grid.y =
  * guess) against whatever model frame the objective points at, then -- still without a host round trip -- the
  * jacobianProducts evaluation at the pose each chain ended on (SurfelMapping.cpp:705), as one more batched pixel pass
@@ -1459,21 +1466,43 @@ static int verify_round(suma_ctx* c, const double* inits, uint32_t n, uint32_t i
    * (SurfelMapping.cpp:693-700): the first guess of a round starts where the caller says, every later one behind at
    * least one increment of its predecessor.  The shader reads the counter as `iteration > 0` and nothing else
    * (Frame2Model_jacobians.geom:129, the Tukey weight), so "1" stands for the count a speculative chain cannot know. */
-  int r = enqueue_minimize(c, inits, n, 0, iteration0, iteration0 > 0 ? iteration0 : 1u); /* :700, n chains side by side */
+  GnChain ch = gn_chain_ctx(c, inits, n);
+  ch.iteration0 = iteration0;
+  ch.iteration0_rest = iteration0 > 0 ? iteration0 : 1u;
+  int r = enqueue_minimize(c, ch); /* :700, n chains side by side */
   if (r) return r;
-  const uint32_t iter_arg = c->p.max_iterations > 0 ? c->p.max_iterations : 0xffffffffu;
   {
-    ProfScope ps(c, "k6_icp_step", 96.0 * (double)c->icp_current->width * c->icp_current->height * n);
-    CK(launch_icp_iteration(c, n, iter_arg, (double)c->p.stopping_threshold, (double)c->p.delta, 1, 0, 1)); /* :705 */
+    ProfScope ps(c, "k6_icp_step", 96.0 * (double)ch.current->width * ch.current->height * n);
+    CK(launch_icp_iteration(c, ch, 1, 1)); /* :705 */
   }
   {
     ProfScope ps(c, "k6_icp_finish", 0.0);
-    CK(launch_icp_iteration(c, n, iter_arg, (double)c->p.stopping_threshold, (double)c->p.delta, 1, 0, 0));
+    CK(launch_icp_iteration(c, ch, 1, 0));
   }
   CK(hipMemcpyAsync(c->h_gn, gn_result(c), (size_t)n * sizeof(GnState), hipMemcpyDeviceToHost, c->stream));
   CK(hipStreamSynchronize(c->stream));
   host_synced(c);
   return SUMA_OK;
+}
+
+/* The end of every verification: the gate on the objective's counters (SurfelMapping.cpp:713 / :563, float ratios
+ * against the thresholds, and the caller's own condition) and, on a pass, the composed view rendered from pose_old and
+ * the objective evaluated at identity against it (:717-723 / :567-572).  The objective is left pointing at
+ * composedFrame(), as the reference leaves it for whatever it minimises next (:719). */
+static int closure_gate(suma_ctx* c, const suma_frame* current, const suma_icp_stats& s0, double min_valid_ratio,
+                        double max_outlier_ratio, bool and_also, const float pose_old[16], const float pose_new[16],
+                        float conf_threshold, int32_t* passed, suma_icp_stats* composed, double JtJ[36]) {
+  const float valid_ratio = (float)s0.valid / (float)(s0.valid + s0.invalid);
+  const float outlier_ratio = (float)s0.outlier / (float)(s0.outlier + s0.inlier);
+  *passed = ((double)valid_ratio > min_valid_ratio && (double)outlier_ratio < max_outlier_ratio && and_also) ? 1 : 0;
+  if (!*passed) return SUMA_OK;
+  int r = suma_map_render_composed(c, pose_old, pose_new, conf_threshold);
+  if (r) return r;
+  r = suma_icp_set_data(c, current, c->composed_frame);
+  if (r) return r;
+  double I[16];
+  mat4_eye(I);
+  return suma_icp_jacobian_products(c, I, 0, JtJ, nullptr, nullptr, composed);
 }
 
 /* SurfelMapping.cpp:679-757 with the initial guesses BATCHED.  The reference minimises the guesses
@@ -1491,7 +1520,7 @@ extern "C" int suma_loop_closure_verify(suma_ctx* c, const suma_frame* current, 
                                         suma_loop_result* out) {
   if (!c || !current || !pose_prior || !initializations || !pose_new || !out) return SUMA_ERR_INVALID;
   float prior_f[16];
-  for (int i = 0; i < 16; ++i) prior_f[i] = (float)pose_prior[i];
+  mat4_cast_f(pose_prior, prior_f);
   int r = suma_map_render_inactive(c, prior_f, conf_threshold); /* :679 */
   if (r) return r;
   r = suma_icp_set_data(c, current, c->old_frame); /* :693 */
@@ -1510,22 +1539,14 @@ extern "C" int suma_loop_closure_verify(suma_ctx* c, const suma_frame* current, 
       memset(o, 0, sizeof(*o));
       memcpy(o->gn_pose, g.Tk, sizeof(g.Tk));
       fill_stats(g, &o->after_minimize);
-      const suma_icp_stats& s0 = o->after_minimize;
-      const float valid_ratio = (float)s0.valid / (float)(s0.valid + s0.invalid);
-      const float outlier_ratio = (float)s0.outlier / (float)(s0.outlier + s0.inlier);
       double pd[16];
-      mul4_dd(pose_prior, o->gn_pose, pd);
-      for (int i = 0; i < 16; ++i) o->pose_old[i] = (float)pd[i];
-      o->passed = (valid_ratio > min_valid_ratio && outlier_ratio < max_outlier_ratio) ? 1 : 0; /* :713 */
+      mat4_mul(pose_prior, o->gn_pose, pd);
+      mat4_cast_f(pd, o->pose_old);
+      /* on a pass, composedFrame() is the model of every later guess (:719); the evaluation overwrites h_gn[0] */
+      r = closure_gate(c, current, o->after_minimize, min_valid_ratio, max_outlier_ratio, true, o->pose_old, pose_new,
+                       conf_threshold, &o->passed, &o->composed, o->JtJ);
+      if (r) return r;
       if (o->passed) {
-        r = suma_map_render_composed(c, o->pose_old, pose_new, conf_threshold); /* :717 */
-        if (r) return r;
-        r = suma_icp_set_data(c, current, c->composed_frame); /* :719 -- the model of every later guess */
-        if (r) return r;
-        double I[16];
-        for (int i = 0; i < 16; ++i) I[i] = (i % 5 == 0) ? 1.0 : 0.0;
-        r = suma_icp_jacobian_products(c, I, 0, o->JtJ, nullptr, nullptr, &o->composed); /* :720-723; overwrites h_gn[0] */
-        if (r) return r;
         next = k + 1; /* what was speculated behind this guess saw the wrong model: redo it */
         iteration0 = 0; /* setData at :719; the evaluation at identity increments nothing */
         break;
@@ -1543,7 +1564,7 @@ extern "C" int suma_loop_closure_verify_serial(suma_ctx* c, const suma_frame* cu
                                         suma_loop_result* out) {
   if (!c || !current || !pose_prior || !initializations || !pose_new || !out) return SUMA_ERR_INVALID;
   float prior_f[16];
-  for (int i = 0; i < 16; ++i) prior_f[i] = (float)pose_prior[i];
+  mat4_cast_f(pose_prior, prior_f);
   int r = suma_map_render_inactive(c, prior_f, conf_threshold); /* :679 */
   if (r) return r;
   r = suma_icp_set_data(c, current, c->old_frame); /* :693 */
@@ -1563,24 +1584,13 @@ extern "C" int suma_loop_closure_verify_serial(suma_ctx* c, const suma_frame* cu
     if (r) return r;
     o->after_minimize.iterations = mst.iterations;
     o->after_minimize.converged = mst.converged;
-    const suma_icp_stats& s0 = o->after_minimize;
-    const float valid_ratio = (float)s0.valid / (float)(s0.valid + s0.invalid);
-    const float outlier_ratio = (float)s0.outlier / (float)(s0.outlier + s0.inlier);
     double pd[16];
-    mul4_dd(pose_prior, o->gn_pose, pd);
-    for (int i = 0; i < 16; ++i) o->pose_old[i] = (float)pd[i];
-    o->passed = (valid_ratio > min_valid_ratio && outlier_ratio < max_outlier_ratio) ? 1 : 0; /* :713 */
-    if (o->passed) {
-      r = suma_map_render_composed(c, o->pose_old, pose_new, conf_threshold); /* :717 */
-      if (r) return r;
-      r = suma_icp_set_data(c, current, c->composed_frame); /* :719 -- stays set for the next guess */
-      if (r) return r;
-      double I[16];
-      for (int i = 0; i < 16; ++i) I[i] = (i % 5 == 0) ? 1.0 : 0.0;
-      r = suma_icp_jacobian_products(c, I, 0, o->JtJ, nullptr, nullptr, &o->composed); /* :720-723 */
-      if (r) return r;
-      iteration = 0; /* setData at :719 */
-    }
+    mat4_mul(pose_prior, o->gn_pose, pd);
+    mat4_cast_f(pd, o->pose_old);
+    r = closure_gate(c, current, o->after_minimize, min_valid_ratio, max_outlier_ratio, true, o->pose_old, pose_new,
+                     conf_threshold, &o->passed, &o->composed, o->JtJ);
+    if (r) return r;
+    if (o->passed) iteration = 0; /* setData at :719 */
   }
   return SUMA_OK;
 }
@@ -1627,63 +1637,31 @@ extern "C" int suma_loop_closure_track(suma_ctx* c, const suma_frame* current, c
   if (!c || !current || !last_pose_old || !last_increment || !pose_new || !o) return SUMA_ERR_INVALID;
   memset(o, 0, sizeof(*o));
   float pf[16];
-  for (int i = 0; i < 16; ++i) pf[i] = (float)last_pose_old[i]; /* :548 */
+  mat4_cast_f(last_pose_old, pf); /* :548 */
   int r = suma_map_render_inactive(c, pf, conf_threshold); /* :550 */
   if (r) return r;
   r = suma_icp_set_data(c, current, c->old_frame); /* :553 */
   if (r) return r;
   r = suma_icp_minimize(c, last_increment, o->increment_old, nullptr, 0, nullptr, &o->after_minimize); /* :554 */
   if (r) return r;
-  const suma_icp_stats& s0 = o->after_minimize; /* the objective's counters as the last step left them (:557-558) */
-  const float valid_ratio = (float)s0.valid / (float)(s0.valid + s0.invalid);
-  const float outlier_ratio = (float)s0.outlier / (float)(s0.outlier + s0.inlier);
   double la[6], lb[6], sq = 0.0;
   suma_se3_log(last_increment, la);
   suma_se3_log(o->increment_old, lb);
   for (int i = 0; i < 6; ++i) sq += (la[i] - lb[i]) * (la[i] - lb[i]);
   o->increment_difference = (float)sqrt(sq); /* :561 */
-  mul4_dd(last_pose_old, o->increment_old, o->pose_old);
-  o->passed = ((double)valid_ratio > min_valid_ratio && (double)outlier_ratio < max_outlier_ratio &&
-               (double)o->increment_difference < max_increment_difference) ? 1 : 0; /* :563: floats against double literals */
-  if (o->passed) {
-    float po[16];
-    for (int i = 0; i < 16; ++i) po[i] = (float)o->pose_old[i]; /* :564 */
-    r = suma_map_render_composed(c, po, pose_new, conf_threshold); /* :567 */
-    if (r) return r;
-    r = suma_icp_set_data(c, current, c->composed_frame); /* :569 */
-    if (r) return r;
-    double I[16];
-    for (int i = 0; i < 16; ++i) I[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    r = suma_icp_jacobian_products(c, I, 0, o->JtJ, nullptr, nullptr, &o->composed); /* :570-572 */
-    if (r) return r;
-  }
-  return SUMA_OK;
+  mat4_mul(last_pose_old, o->increment_old, o->pose_old);
+  float po[16];
+  mat4_cast_f(o->pose_old, po); /* :564 */
+  /* the objective's counters as the last step left them (:557-558) */
+  return closure_gate(c, current, o->after_minimize, min_valid_ratio, max_outlier_ratio,
+                      (double)o->increment_difference < max_increment_difference, po, pose_new, conf_threshold,
+                      &o->passed, &o->composed, o->JtJ);
 }
 
 /* ---------------------------------------------------------------------------------------------
  * SurfelMapping::processScan
  * ------------------------------------------------------------------------------------------- */
 static int resolve_stats(suma_pipeline* s, bool need_sync);
-
-static void eye_d(double* T) {
-  for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0 : 0.0;
-}
-static void mul4_d(const double* A, const double* B, double* C) {
-  for (int c = 0; c < 4; ++c)
-    for (int r = 0; r < 4; ++r)
-      C[4 * c + r] =
-          ((A[r] * B[4 * c] + A[4 + r] * B[4 * c + 1]) + A[8 + r] * B[4 * c + 2]) + A[12 + r] * B[4 * c + 3];
-}
-static void rigid_inv_d(const double* m, double* out) {
-  for (int c = 0; c < 3; ++c)
-    for (int r = 0; r < 3; ++r) out[4 * c + r] = m[4 * r + c];
-  for (int r = 0; r < 3; ++r) out[12 + r] = -((m[4 * r] * m[12] + m[4 * r + 1] * m[13]) + m[4 * r + 2] * m[14]);
-  out[3] = out[7] = out[11] = 0.0;
-  out[15] = 1.0;
-}
-static void cast_f(const double* T, float* out) {
-  for (int i = 0; i < 16; ++i) out[i] = (float)T[i];
-}
 
 extern "C" int suma_pipeline_create(const suma_params* params, int hip_device, suma_pipeline** out) {
   if (!params || !out) return SUMA_ERR_INVALID;
@@ -1725,12 +1703,12 @@ extern "C" int suma_pipeline_create(const suma_params* params, int hip_device, s
   s->res_seq = 0;
   s->stats_pending = false;
   s->stats_slot = 0;
-  eye_d(s->current_pose);
-  eye_d(s->last_pose);
-  eye_d(s->pose_old);
-  eye_d(s->pose_new);
-  eye_d(s->last_increment);
-  eye_d(s->last_pose_old);
+  mat4_eye(s->current_pose);
+  mat4_eye(s->last_pose);
+  mat4_eye(s->pose_old);
+  mat4_eye(s->pose_new);
+  mat4_eye(s->last_increment);
+  mat4_eye(s->last_pose_old);
   s->phase = 0;
   float p_unstable = 0.1f; /* SurfelMapping.cpp:108-109 */
   s->log_unstable = (float)log((double)(p_unstable / (1.0f - p_unstable)));
@@ -1808,20 +1786,32 @@ static float conf_threshold(const suma_pipeline* s) {
   return ct;
 }
 
-/* one minimisation with the optional fixed-iteration override; reads back pose + stats + counters */
-static int minimize_cfg(suma_pipeline* s, const suma_frame* cur, const suma_frame* model, const double* T0, double* T,
-                        int32_t fixed_iterations, suma_icp_stats* st) {
+/* a chain of the scan pipeline: the current frame against `model` (left on the ctx as the adapter's frames, where the
+ * reference's objective_ keeps them), with processScan's fixed-iteration override and, for the fallback minimisation,
+ * the fallback gates (SurfelMapping.cpp:438-449).  Those re-parameterise the pipeline's own objective, which runs on
+ * suma_params; an adapter objective set on the ctx keeps its values. */
+static GnChain pipeline_chain(suma_pipeline* s, const suma_frame* model, const double* T0s, uint32_t n_hyp,
+                              int32_t fixed_iterations, bool fallback) {
   suma_ctx* c = s->c;
-  suma_params saved = c->p;
-  if (fixed_iterations > 0) {
-    c->p.max_iterations = (uint32_t)fixed_iterations;
-    c->p.stopping_threshold = 0.0f;
-    c->p.delta = 0.0f;
-  }
-  c->icp_current = cur;
+  c->icp_current = s->current_frame;
   c->icp_model = model;
-  int r = enqueue_minimize(c, T0, 1, 0);
-  c->p = saved;
+  GnChain ch = gn_chain_ctx(c, T0s, n_hyp);
+  if (fixed_iterations > 0) {
+    ch.max_iterations = (uint32_t)fixed_iterations;
+    ch.epsilon = 0.0;
+    ch.delta = 0.0;
+  }
+  if (fallback && !c->obj_set) {
+    ch.obj.icp_max_distance = c->p.fallback_max_distance;
+    ch.obj.icp_max_angle = c->p.fallback_max_angle;
+  }
+  return ch;
+}
+
+/* one single-chain minimisation; reads back pose + stats + counters */
+static int minimize_cfg(suma_pipeline* s, const GnChain& ch, double* T, suma_icp_stats* st) {
+  suma_ctx* c = s->c;
+  int r = enqueue_minimize(c, ch);
   if (r) return r;
   CK(hipMemcpyAsync(c->h_gn, gn_result(c), sizeof(GnState), hipMemcpyDeviceToHost, c->stream));
   CK(hipMemcpyAsync(c->h_ds, c->ds, sizeof(DevState), hipMemcpyDeviceToHost, c->stream));
@@ -1850,27 +1840,16 @@ static int update_pose(suma_pipeline* s, int32_t fixed_iterations) {
   if (!c->p.initialize_identity)
     memcpy(T0, s->last_increment, sizeof(T0));
   else
-    eye_d(T0);
+    mat4_eye(T0);
   suma_icp_stats mst;
   /* --- frame-to-model minimisation (:384-396), result copied to the host, event recorded --- */
   {
-    suma_params saved = c->p;
-    if (fixed_iterations > 0) {
-      c->p.max_iterations = (uint32_t)fixed_iterations;
-      c->p.stopping_threshold = 0.0f;
-      c->p.delta = 0.0f;
-    }
-    c->icp_current = s->current_frame;
-    c->icp_model = c->new_frame;
-    c->gn_emit_pose = 1;
-    memcpy(c->gn_pose_base, s->pose_new, sizeof(c->gn_pose_base));
+    GnChain ch = pipeline_chain(s, c->new_frame, T0, 1, fixed_iterations, false);
+    ch.pose_base = s->pose_new;
     s->res_seq += 1;
-    c->gn_host_out = &s->h_res[0]; /* the closing launch reports straight into pinned host memory */
-    c->gn_host_seq = s->res_seq;
-    int r0 = enqueue_minimize(c, T0, 1, 0);
-    c->gn_emit_pose = 0;
-    c->gn_host_out = nullptr;
-    c->p = saved;
+    ch.report = &s->h_res[0]; /* the closing launch reports straight into pinned host memory */
+    ch.report_seq = s->res_seq;
+    int r0 = enqueue_minimize(c, ch);
     if (r0) return r0;
   }
   /* --- re-render from pose_new * increment (pose taken from HBM), K7 splat and the
@@ -1881,23 +1860,19 @@ static int update_pose(suma_pipeline* s, int32_t fixed_iterations) {
   s->last_model->version++;
   /* --- statistics pass (:411-423) --- */
   double I[16];
-  eye_d(I);
-  c->icp_current = s->current_frame;
-  c->icp_model = c->new_frame;
-  CK(launch_gn_init(c, I, 1, 0, 0));
+  mat4_eye(I);
+  GnChain st = gn_chain_ctx(c, I, 1); /* the frames of the minimisation above */
+  CK(launch_gn_init(c, st));
   const uint32_t slot = s->stats_slot ^ 1u; /* the previous scan's record may not have been looked at yet */
   {
     /* one launch: the pass closes itself (last block totals and reports to the host record) */
     ProfScope ps(c, "k6k8_stats_radius", (96.0 + 81.0) * (double)c->P); /* K6 reads + K8's 81 B of products per pixel */
-    c->gn_fused_report = &s->h_res[1 + slot];
-    c->gn_host_seq = s->res_seq;
+    st.report = &s->h_res[1 + slot];
+    st.report_seq = s->res_seq;
     /* this launch streams the three maps of the current frame: K8's per-pixel work for the update that
      * follows (pose independent) and the per-update counter resets ride along -- no k8_radius launch */
-    c->gn_fuse_k8 = 1;
-    hipError_t e = launch_icp_iteration(c, 1, 1, 0.0, 0.0, 1, 0, 1);
-    c->gn_fuse_k8 = 0;
-    c->gn_fused_report = nullptr;
-    CK(e);
+    st.fuse_k8 = 1;
+    CK(launch_icp_iteration(c, st, 1, 1));
     c->k8_fused_frame = s->current_frame;
     c->k8_fused_version = s->current_frame->version;
     c->k8_fused_stamp = c->timestamp;
@@ -1925,10 +1900,10 @@ static int update_pose(suma_pipeline* s, int32_t fixed_iterations) {
 
   double inv_last[16], delta[16], posed[16];
   float posef[16];
-  rigid_inv_d(s->last_increment, inv_last);
-  mul4_d(inv_last, increment, delta);
-  mul4_d(s->pose_new, increment, posed);
-  cast_f(posed, posef); /* the same value the closing launch wrote to HBM */
+  mat4_rigid_inv(s->last_increment, inv_last);
+  mat4_mul(inv_last, increment, delta);
+  mat4_mul(s->pose_new, increment, posed);
+  mat4_cast_f(posed, posef); /* the same value the closing launch wrote to HBM */
   c->k7.valid = true;
   c->k7.map_version = c->map_version;
   c->k7.params_version = c->params_version;
@@ -1940,16 +1915,12 @@ static int update_pose(suma_pipeline* s, int32_t fixed_iterations) {
   const bool fallback = (s->timestamp > 1 && ((double)t_err > 0.4 || (double)r_err > 0.1) && c->p.fallback_mode); /* :438-449: float against the double literals */
   if (fallback) {
     s->track_loss += 1;
-    suma_params saved = c->p;
-    c->p.icp_max_distance = c->p.fallback_max_distance;
-    c->p.icp_max_angle = c->p.fallback_max_angle;
-    r = minimize_cfg(s, s->current_frame, s->last_frame, T0, increment, fixed_iterations, &mst);
-    c->p = saved;
+    r = minimize_cfg(s, pipeline_chain(s, s->last_frame, T0, 1, fixed_iterations, true), increment, &mst);
     if (r) return r;
   }
   memcpy(s->last_pose, s->current_pose, sizeof(s->last_pose));
   double np[16];
-  mul4_d(s->current_pose, increment, np);
+  mat4_mul(s->current_pose, increment, np);
   memcpy(s->current_pose, np, sizeof(np));
   memcpy(s->last_pose_old, s->pose_old, sizeof(s->last_pose_old)); /* :456 */
   memcpy(s->pose_old, np, sizeof(np));
@@ -1989,8 +1960,8 @@ int pipeline_begin_scan_impl(suma_pipeline* s, const suma_float4* d_points, cons
     if (r) return r;
   }
   float po[16], pn[16];
-  cast_f(s->pose_old, po);
-  cast_f(s->pose_new, pn);
+  mat4_cast_f(s->pose_old, po);
+  mat4_cast_f(s->pose_new, pn);
   r = map_render_dedup(c, po, pn, conf_threshold(s), s->last_model);
   if (r) return r;
   s->phase = 1;
@@ -2014,7 +1985,7 @@ int pipeline_update_map_impl(suma_pipeline* s) {
   suma_ctx* c = s->c;
   if (s->phase != 2) return fail(c, SUMA_ERR_INVALID, "suma_pipeline_update_map: call suma_pipeline_update_pose first");
   float pc[16];
-  cast_f(s->current_pose, pc);
+  mat4_cast_f(s->current_pose, pc);
   int r = suma_map_update(c, pc, s->current_frame);
   if (r) return r;
   r = map_render_dedup(c, pc, pc, conf_threshold(s), s->current_model);
@@ -2060,12 +2031,12 @@ extern "C" int suma_pipeline_reset(suma_pipeline* s) {
   s->timestamp = 0;
   s->track_loss = 0;
   s->phase = 0;
-  eye_d(s->current_pose);
-  eye_d(s->last_pose);
-  eye_d(s->pose_old);
-  eye_d(s->pose_new);
-  eye_d(s->last_increment);
-  eye_d(s->last_pose_old);
+  mat4_eye(s->current_pose);
+  mat4_eye(s->last_pose);
+  mat4_eye(s->pose_old);
+  mat4_eye(s->pose_new);
+  mat4_eye(s->last_increment);
+  mat4_eye(s->last_pose_old);
   c->obj_set = false;
   c->k8_fused_frame = nullptr;
   return suma_synchronize(c);
@@ -2080,21 +2051,16 @@ extern "C" int suma_pipeline_minimize_hypotheses(suma_pipeline* s, const double*
   if (!s || !T0s || !T_out || n_hyp == 0 || n_hyp > SUMA_MAX_HYP) return SUMA_ERR_INVALID;
   suma_ctx* c = s->c;
   if (s->phase != 1) return fail(c, SUMA_ERR_INVALID, "suma_pipeline_minimize_hypotheses: between suma_pipeline_begin_scan and suma_pipeline_apply_increment");
-  suma_params saved = c->p;
-  if (fixed_iterations > 0) {
-    c->p.max_iterations = (uint32_t)fixed_iterations;
-    c->p.stopping_threshold = 0.0f;
-    c->p.delta = 0.0f;
-  }
-  c->icp_current = s->current_frame;
-  c->icp_model = c->new_frame;
+  const GnChain ch = pipeline_chain(s, c->new_frame, T0s, n_hyp, fixed_iterations, false);
   /* this path never runs update_pose, whose result record carries DevState: fetch it with the batch (the copy rides in
    * front of the batch's own read-back and synchronisation), so that the map size the grids are sized from and the
    * capacity / arena / time-out bits reach the host on every scan (round-3 advisor) */
   hipError_t e = hipMemcpyAsync(c->h_ds, c->ds, sizeof(DevState), hipMemcpyDeviceToHost, c->stream);
-  int r = (e == hipSuccess) ? suma_icp_minimize_batch(c, T0s, n_hyp, T_out, stats) : SUMA_ERR_HIP;
-  c->p = saved;
-  if (e != hipSuccess) c->err = std::string("hipMemcpyAsync(DevState): ") + hipGetErrorString(e);
+  if (e != hipSuccess) {
+    c->err = std::string("hipMemcpyAsync(DevState): ") + hipGetErrorString(e);
+    return SUMA_ERR_HIP;
+  }
+  int r = minimize_batch(c, ch, T_out, stats);
   if (r) return r;
   c->known_surfels = c->h_ds->n_surfels;
   return check_overflow(c);
@@ -2105,7 +2071,7 @@ extern "C" int suma_pipeline_apply_increment(suma_pipeline* s, const double incr
   if (s->phase != 1) return fail(s->c, SUMA_ERR_INVALID, "suma_pipeline_apply_increment: call suma_pipeline_begin_scan first");
   memcpy(s->last_pose, s->current_pose, sizeof(s->last_pose));
   double np[16];
-  mul4_d(s->current_pose, increment, np);
+  mat4_mul(s->current_pose, increment, np);
   memcpy(s->current_pose, np, sizeof(np));
   memcpy(s->last_pose_old, s->pose_old, sizeof(s->last_pose_old));
   memcpy(s->pose_old, np, sizeof(np));
@@ -2124,7 +2090,7 @@ extern "C" int suma_pipeline_integrate_loop_closures(suma_pipeline* s, const flo
   int r = suma_map_update_poses(c, poses16, n); /* :236 */
   if (r) return r;
   double np[16];
-  mul4_d(difference, s->current_pose, np); /* :239 */
+  mat4_mul(difference, s->current_pose, np); /* :239 */
   memcpy(s->current_pose, np, sizeof(np));
   memcpy(s->pose_old, np, sizeof(np)); /* :243 */
   memcpy(s->pose_new, np, sizeof(np));
@@ -2149,7 +2115,7 @@ extern "C" int suma_pipeline_verify_loop_closure(suma_pipeline* s, const double 
   if (!s) return SUMA_ERR_INVALID;
   if (s->phase != 2) return fail(s->c, SUMA_ERR_INVALID, "suma_pipeline_verify_loop_closure: between suma_pipeline_update_pose and suma_pipeline_update_map (SurfelMapping.cpp:196)");
   float pn[16];
-  cast_f(s->pose_new, pn); /* currentPose_new_.cast<float>(), :717 */
+  mat4_cast_f(s->pose_new, pn); /* currentPose_new_.cast<float>(), :717 */
   return suma_loop_closure_verify(s->c, s->current_frame, pose_prior, initializations, n_init, pn, conf_threshold(s),
                                   min_valid_ratio, max_outlier_ratio, out);
 }
@@ -2158,7 +2124,7 @@ extern "C" int suma_pipeline_track_loop_closure(suma_pipeline* s, double min_val
   if (!s) return SUMA_ERR_INVALID;
   if (s->phase != 2) return fail(s->c, SUMA_ERR_INVALID, "suma_pipeline_track_loop_closure: between suma_pipeline_update_pose and suma_pipeline_update_map (SurfelMapping.cpp:196)");
   float pn[16];
-  cast_f(s->pose_new, pn);
+  mat4_cast_f(s->pose_new, pn);
   return suma_loop_closure_track(s->c, s->current_frame, s->last_pose_old, s->last_increment, pn, conf_threshold(s),
                                  min_valid_ratio, max_outlier_ratio, max_increment_difference, out);
 }

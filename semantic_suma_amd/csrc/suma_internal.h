@@ -87,6 +87,30 @@ struct HostResult {
   double JtJ[36], Jtr[6]; /* of the last step (LieGaussNewton::information); closing launch of suma_icp_minimize only */
 };
 
+/* One Gauss-Newton chain as its caller describes it: filled once, passed to enqueue_minimize (suma_api.hip),
+ * launch_gn_init and launch_icp_iteration, and nothing of it is kept on the context. */
+struct GnChain {
+  const suma_frame *current, *model;
+  suma_icp_objective obj; /* resolved: the adapter's object or the ctx parameters (Frame2Model.cpp:66-67) */
+  /* LieGaussNewton's budget (0: until convergence) and stopping tests; an eval-only launch reads none of them */
+  uint32_t max_iterations;
+  double epsilon, delta;
+  /* start state: n_hyp poses, read by launch_gn_init (batch) or by the chain's first launch (single chain), and
+   * Frame2Model::iteration_ of the first / every other chain (0 right behind a setData; > 0 for a minimisation that
+   * follows another one on the same setData, SurfelMapping.cpp:693-700) */
+  const double* T0s;
+  uint32_t n_hyp;
+  uint32_t iteration0, iteration0_rest;
+  int with_history; /* LieGaussNewton::history() into gn_history (single chain) */
+  /* if set: the chain reports to this pinned host record, stamped with report_seq -- from its closing launch, or from
+   * the eval-only pixel pass of a single chain, which then closes itself.  report_full: also acc / JtJ / Jtr / n_hist */
+  HostResult* report;
+  uint32_t report_seq;
+  int report_full;
+  const double* pose_base; /* if set: the closing launch writes pose_base * increment to pose_block */
+  int fuse_k8; /* the self-closing eval-only pass also runs K8's per-pixel work and the counter resets */
+};
+
 struct MapConsts {
   float pixel_size, log_prior, log_unstable, p_unstable;
   float radconf_angle_thresh, update_angle_thresh;
@@ -145,7 +169,6 @@ struct suma_ctx {
   struct Ingest* ingest;   /* pinned double-buffered scan staging + copy stream + helper threads (suma_ingest.hip) */
   HostResult* h_rec;       /* pinned: results of suma_icp_minimize / suma_icp_jacobian_products ([0] / [1]) */
   uint32_t rec_seq;
-  int gn_host_full;        /* the reporting launch being enqueued also writes HostResult.acc / n_hist */
   std::string err;
 
   proj_t pd, pm; /* data / model projection */
@@ -180,18 +203,9 @@ struct suma_ctx {
   uint64_t k8_fused_version; /* suma_frame.version the products were made from */
   uint32_t k8_fused_stamp;
   uint64_t k8_fused_params;
-  int gn_fuse_k8; /* the next eval-only pixel launch also runs K8's per-pixel work and the counter resets */
-  HostResult* gn_fused_report; /* if set: the next eval-only pixel launch closes itself and reports here (gn_host_seq) */
-  HostResult* gn_host_out; /* if set: the closing launch being enqueued reports to this pinned host record ... */
-  uint32_t gn_host_seq;    /* ... and stamps it with this sequence number */
-  int gn_emit_pose;        /* the closing launch of the chain being enqueued writes pose_block */
-  double gn_pose_base[16];
   float* pose_block;       /* device: 16 floats pose + 16 floats inverse for the post-ICP render */
-  int gn_init_pending; /* the next k_icp_iter launch starts a fresh single chain from gn_T0_host */
-  uint32_t gn_iteration0;
   HostEntryTimes het;
   uint32_t icp_iteration0; /* suma_icp_set_iteration: Frame2Model::iteration_ for the NEXT suma_icp_minimize (one shot) */
-  double gn_T0_host[16];
   double* gn_history;  /* (max_iterations + 1) x 16 doubles (single minimise only) */
   double* gn_T0s;      /* SUMA_MAX_HYP x 16 staging for batched starts */
   uint32_t gn_history_cap;
@@ -360,10 +374,8 @@ hipError_t launch_preprocess(suma_ctx* c, const float4* d_pts, const float* d_la
 hipError_t launch_k1_average(suma_ctx* c, const float4* d_pts, const float* d_labels, const float* d_probs, uint32_t n,
                              uint32_t timestamp, float4* vertex, float4* raw_semantic);
 hipError_t launch_k1c_bilateral(suma_ctx* c, float4* vertex);
-hipError_t launch_gn_init(suma_ctx* c, const double* h_T0s, uint32_t n_hyp, int with_history, uint32_t iteration0,
-                          uint32_t iteration0_rest = 0);
-hipError_t launch_icp_iteration(suma_ctx* c, uint32_t n_hyp, uint32_t max_iter, double epsilon, double delta,
-                                int eval_only, int with_history, int pixel);
+hipError_t launch_gn_init(suma_ctx* c, const GnChain& ch);
+hipError_t launch_icp_iteration(suma_ctx* c, const GnChain& ch, int eval_only, int pixel);
 const GnState* gn_result(suma_ctx* c);
 /* k_render.hip */
 hipError_t launch_map_render(suma_ctx* c, const float* pose_old, const float* pose_new, float conf_threshold,
@@ -394,5 +406,27 @@ hipError_t flush_gate(suma_ctx* c);
 
 /* host helper shared by api + pipeline */
 void rigid_inverse_f(const float* m, float* out);
+
+/* host-side 4 x 4 double matrices, column-major (suma_api.hip, suma_runner.hip).  Every product has the one fixed
+ * operation order all ranks use, ((a0 b0 + a1 b1) + a2 b2) + a3 b3 (distributed.py mul4). */
+static inline void mat4_eye(double* T) {
+  for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0 : 0.0;
+}
+/* C = A * B */
+static inline void mat4_mul(const double* A, const double* B, double* C) {
+  for (int c = 0; c < 4; ++c)
+    for (int r = 0; r < 4; ++r)
+      C[4 * c + r] = ((A[r] * B[4 * c] + A[4 + r] * B[4 * c + 1]) + A[8 + r] * B[4 * c + 2]) + A[12 + r] * B[4 * c + 3];
+}
+static inline void mat4_rigid_inv(const double* m, double* out) {
+  for (int c = 0; c < 3; ++c)
+    for (int r = 0; r < 3; ++r) out[4 * c + r] = m[4 * r + c];
+  for (int r = 0; r < 3; ++r) out[12 + r] = -((m[4 * r] * m[12] + m[4 * r + 1] * m[13]) + m[4 * r + 2] * m[14]);
+  out[3] = out[7] = out[11] = 0.0;
+  out[15] = 1.0;
+}
+static inline void mat4_cast_f(const double* T, float* out) {
+  for (int i = 0; i < 16; ++i) out[i] = (float)T[i];
+}
 
 #endif

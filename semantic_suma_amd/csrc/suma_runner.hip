@@ -1,7 +1,7 @@
 /*
  * suma_runner.hip -- native host loops for the replica configurations (include/suma_runner.h): BASELINE configs[3]
  * (several sequences at once, one pipeline + one host thread each) and configs[2] (several pose hypotheses per scan).
- * Host code only; everything goes through the public C-ABI of suma_hip.h.
+ * Host code only; everything goes through the public C-ABI of suma_hip.h (and the host matrix helpers of suma_internal.h).
  */
 #include <string.h>
 
@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/suma_runner.h"
+#include "suma_internal.h"
 
 static double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -115,13 +116,6 @@ extern "C" int suma_run_sequences(const suma_params* params, int hip_device, con
   return rc;
 }
 
-/* C = A * B, column-major, in the fixed operation order every rank uses (distributed.py mul4) */
-static void mul4(const double* A, const double* B, double* C) {
-  for (int c = 0; c < 4; ++c)
-    for (int r = 0; r < 4; ++r)
-      C[4 * c + r] = ((A[r] * B[4 * c] + A[4 + r] * B[4 * c + 1]) + A[8 + r] * B[4 * c + 2]) + A[12 + r] * B[4 * c + 3];
-}
-
 extern "C" int suma_run_hypotheses(const suma_params* params, int hip_device, const suma_hypothesis_job* job,
                                    int32_t fixed_iterations, suma_exchange_fn exchange, void* user, double* poses,
                                    int32_t* winners, char error[160]) {
@@ -140,7 +134,7 @@ extern "C" int suma_run_hypotheses(const suma_params* params, int hip_device, co
   std::vector<double> starts(16 * mine.size()), Ts(16 * mine.size()), local(18 * (size_t)n_hyp), all(18 * (size_t)n_hyp);
   std::vector<suma_icp_stats> stats(mine.size());
   double increment[16];
-  for (int i = 0; i < 16; ++i) increment[i] = (i % 5 == 0) ? 1.0 : 0.0;
+  mat4_eye(increment);
   /* A rank that fails must still take part in the NEXT exchange, or its peers wait in the collective for ever (round-3
    * advisor): it stops working on its pipeline, sends a table whose every row carries NaN in the residual column, every
    * rank sees the NaN in the summed table and all of them leave at the same scan. */
@@ -163,7 +157,7 @@ extern "C" int suma_run_hypotheses(const suma_params* params, int hip_device, co
     if (t > 0) {
       std::fill(local.begin(), local.end(), 0.0);
       if (failed == SUMA_OK && !mine.empty()) {
-        for (size_t j = 0; j < mine.size(); ++j) mul4(increment, job->perturbations + 16 * (size_t)mine[j], &starts[16 * j]);
+        for (size_t j = 0; j < mine.size(); ++j) mat4_mul(increment, job->perturbations + 16 * (size_t)mine[j], &starts[16 * j]);
         r = suma_pipeline_minimize_hypotheses(s, starts.data(), (uint32_t)mine.size(), fixed_iterations, Ts.data(), stats.data());
         if (r != SUMA_OK) fail_local(r);
         if (failed == SUMA_OK)
