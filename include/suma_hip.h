@@ -334,6 +334,61 @@ int suma_pipeline_track_loop_closure(suma_pipeline* s, double min_valid_ratio, d
 /* SE3::log (lie_algebra.cpp:36-71), host side: x = (v, omega) */
 void suma_se3_log(const double T[16], double x[6]);
 
+/* Semantic front end (suma_semantic_project / suma_semantic_unproject, include/suma_hip.h): the range image a
+ * RangeNet++-style segmentation network consumes, and the map from its class scores back to per-point labels.  It
+ * stands in for RangenetAPI::infer + the argmax of the reference's KITTIReader::read (src/io/KITTIReader.cpp:172-200);
+ * the network itself is the caller's.  The image has its own geometry (RangeNet++ is trained on 64 x 2048, fov 3 / -25):
+ * it is NOT the data image of suma_params.  (Kept here, not in suma_types.h: that header is part of the arithmetic
+ * specification the CPU checker's recorded traces are tied to.) */
+#define SUMA_SEM_MAX_CLASSES 32 /* compile-time maximum of n_classes (the reference's network has 20) */
+#define SUMA_SEM_CHANNELS 5     /* input planes: range, x, y, z, remission */
+typedef struct suma_semantic_params {
+  uint32_t width, height;            /* W x H of the network's range image */
+  float fov_up, fov_down;            /* degrees; only |fov_up| and |fov_down| are used */
+  float means[SUMA_SEM_CHANNELS];    /* per-channel normalisation (v - mean) / std, from the model's config */
+  float stds[SUMA_SEM_CHANNELS];
+  uint32_t n_classes;                /* C: score planes, 1 .. SUMA_SEM_MAX_CLASSES */
+  int32_t label_map[SUMA_SEM_MAX_CLASSES]; /* class index -> reported label id (learning_map_inv) */
+} suma_semantic_params;
+
+/* ---- semantic front end (suma_semantic_params above): the device side of the reference's
+ *      RangenetAPI::infer + argmax (KITTIReader.cpp:172-200) around a segmentation network the caller runs.
+ *      Both entries run on the ctx stream and take caller-owned device buffers (k_semantic.hip states the arithmetic).
+ *
+ * suma_semantic_project: d_points n x (x, y, z, remission) as in a KITTI .bin -> d_input, a planar [5, H, W] fp32
+ *   tensor of the channels (range, x, y, z, remission), each (v - mean_c) / std_c, 0 in every channel of an empty pixel.
+ *   RangeNet++'s convention: depth = |p|, yaw = -atan2(y, x), pitch = asin(z / depth),
+ *   u = 0.5 (yaw / pi + 1) W, v = (1 - (pitch + |fov_down|) / fov) H, fov = |fov_up| + |fov_down|; floor, then CLAMP
+ *   to [0, W-1] x [0, H-1].  Row 0 is the TOP of the image (highest pitch) -- the opposite of the frames' vertex maps.
+ *   A point with a non-finite coordinate, zero range or a range that overflows is not projected.  The nearest point
+ *   wins its pixel, equal ranges go to the lower point index.
+ *   d_pixel (optional): n int32, the pixel y * W + x of every point, -1 = not projected.
+ *   d_proj_idx (optional): H * W int32, the winning point of every pixel, -1 = empty. */
+int suma_semantic_project(suma_ctx* ctx, const suma_semantic_params* sp, const suma_float4* d_points, uint32_t n,
+                          float* d_input, int32_t* d_pixel, int32_t* d_proj_idx);
+/* suma_semantic_unproject: d_scores a planar [C, H, W] fp32 tensor (C = n_classes), d_pixel as written by
+ *   suma_semantic_project -> d_labels / d_probs (n floats each).  Every projected point reads its own pixel's scores,
+ *   also a point hidden behind a nearer one.  scores_are_logits != 0: a softmax over C first.  Then the reference's
+ *   rule literally (KITTIReader.cpp:189-200): label = 0, prob = 0; for j = 0 .. C-1: if (prob <= s_j) label =
+ *   label_map[j], prob = s_j -- the last maximum wins, all-negative scores give (0, 0), a NaN never wins.  Points that
+ *   were not projected (pixel < 0 or >= H * W) get (0, 0). */
+int suma_semantic_unproject(suma_ctx* ctx, const suma_semantic_params* sp, const float* d_scores, int scores_are_logits,
+                            const int32_t* d_pixel, uint32_t n, float* d_labels, float* d_probs);
+/* ---- a scan whose labels come from network scores still on the device: begin_scan_device / process_scan_device with
+ *      the back-projection in front.  The pipeline's preprocessing stream waits for producer_event (a hipEvent_t recorded
+ *      behind the work that writes d_points / d_scores / d_pixel; NULL = those buffers are complete at call time), runs
+ *      suma_semantic_unproject into labels / probs the ctx owns, then K1-K3 exactly as begin_scan_device does -- no host
+ *      synchronisation.  Unlike the *_device entries, the scan buffers need not be complete when the call is made.
+ *      They are read until the ctx stream (suma_ctx_stream) has passed the suma_pipeline_update_map of this scan
+ *      (process_scan_scores includes it): the ctx stream waits for the preprocessing before its first reader of the
+ *      frame, so work enqueued on the ctx stream after the call, or behind an event recorded there, may reuse them. */
+int suma_pipeline_begin_scan_scores(suma_pipeline* s, const suma_semantic_params* sp, const suma_float4* d_points,
+                                    const float* d_scores, int scores_are_logits, const int32_t* d_pixel, uint32_t n,
+                                    void* producer_event);
+int suma_pipeline_process_scan_scores(suma_pipeline* s, const suma_semantic_params* sp, const suma_float4* d_points,
+                                      const float* d_scores, int scores_are_logits, const int32_t* d_pixel, uint32_t n,
+                                      void* producer_event, int32_t fixed_iterations);
+
 /* ---- device scratch for callers that keep scans resident in HBM (bench, replay) */
 int suma_device_alloc(suma_ctx* ctx, uint64_t bytes, void** d_ptr);
 int suma_device_free(suma_ctx* ctx, void* d_ptr);

@@ -188,6 +188,11 @@ struct suma_ctx {
   float4* scan_points;           /* staging for host scans */
   float *scan_labels, *scan_probs;
   uint32_t scan_cap;
+  /* semantic front end (k_semantic.hip), allocated on first use */
+  unsigned long long* sem_zbuf; /* sem_zbuf_cap keys, left cleared by every resolve */
+  size_t sem_zbuf_cap;
+  float *sem_labels, *sem_probs; /* the back-projection of the scan pipeline's scores entry */
+  uint32_t sem_cap;
 
   /* ICP */
   const suma_frame *icp_current, *icp_model;

@@ -29,6 +29,16 @@ def read_velodyne(path: str) -> np.ndarray:
     return pts
 
 
+def read_velodyne_raw(path: str) -> np.ndarray:
+    """-> points[N, 4] float32 (x, y, z, remission) as stored: the input of the semantic front end
+    (segmentation.SemanticFrontEnd), whose remission channel needs the fourth column.  The pipeline takes this layout
+    as it is -- K1 and the vertex-map filters read only x, y, z of a point."""
+    raw = np.fromfile(path, dtype="<f4")
+    if raw.size % 4:
+        raise ValueError(f"{path}: size is not a multiple of 4 floats")
+    return raw.reshape(-1, 4).copy()
+
+
 # SemanticKITTI learning_map (raw id -> one of RangeNet++'s 20 training classes) and learning_map_inv (training
 # class -> the raw id it is reported as).  The reference only ever sees learning_map_inv values: KITTIReader.cpp:189-200
 # assigns labels[i] = label_map_[argmax_j], j < 20.

@@ -50,6 +50,20 @@ class SumaParams(C.Structure):
     ]
 
 
+SEM_MAX_CLASSES = 32  # SUMA_SEM_MAX_CLASSES
+SEM_CHANNELS = 5      # SUMA_SEM_CHANNELS: range, x, y, z, remission
+
+
+class SemanticParams(C.Structure):
+    """``struct suma_semantic_params``: geometry and normalisation of a segmentation network's range image, its class
+    count and label map (the semantic front end, semantic_suma_amd/segmentation.py)."""
+    _fields_ = [
+        ("width", u32), ("height", u32), ("fov_up", f32), ("fov_down", f32),
+        ("means", f32 * SEM_CHANNELS), ("stds", f32 * SEM_CHANNELS),
+        ("n_classes", u32), ("label_map", i32 * SEM_MAX_CLASSES),
+    ]
+
+
 class IcpStats(C.Structure):
     _fields_ = [("error", f64), ("inlier_residual", f64), ("valid", u32), ("outlier", u32), ("inlier", u32),
                 ("invalid", u32), ("iterations", u32), ("converged", u32)]
