@@ -368,7 +368,7 @@ int suma_semantic_project(suma_ctx* ctx, const suma_semantic_params* sp, const s
                           float* d_input, int32_t* d_pixel, int32_t* d_proj_idx);
 /* suma_semantic_unproject: d_scores a planar [C, H, W] fp32 tensor (C = n_classes), d_pixel as written by
  *   suma_semantic_project -> d_labels / d_probs (n floats each).  Every projected point reads its own pixel's scores,
- *   also a point hidden behind a nearer one.  scores_are_logits != 0: a softmax over C first.  Then the reference's
+ *   also a point hidden behind a nearer one (suma_semantic_unproject_knn below votes instead).  scores_are_logits != 0: a softmax over C first.  Then the reference's
  *   rule literally (KITTIReader.cpp:189-200): label = 0, prob = 0; for j = 0 .. C-1: if (prob <= s_j) label =
  *   label_map[j], prob = s_j -- the last maximum wins, all-negative scores give (0, 0), a NaN never wins.  Points that
  *   were not projected (pixel < 0 or >= H * W) get (0, 0). */
@@ -388,6 +388,41 @@ int suma_pipeline_begin_scan_scores(suma_pipeline* s, const suma_semantic_params
 int suma_pipeline_process_scan_scores(suma_pipeline* s, const suma_semantic_params* sp, const suma_float4* d_points,
                                       const float* d_scores, int scores_are_logits, const int32_t* d_pixel, uint32_t n,
                                       void* producer_event, int32_t fixed_iterations);
+
+/* ---- RangeNet++'s KNN post-processing (Milioto et al., IROS 2019, section III-D), opt-in: the back-projection above
+ *      with a vote among the points nearest in range around each point's pixel, so that a point hidden behind a nearer
+ *      one does not take that one's class (k_semantic_knn.hip states the arithmetic).  The published defaults are
+ *      search 5, k 5, sigma 1, cutoff 1. */
+typedef struct suma_semantic_knn {
+  uint32_t search; /* S: an S x S window around the pixel, odd, 1 .. 9 */
+  uint32_t k;      /* K candidates vote, 1 .. S * S; the point itself is always the first */
+  float sigma;     /* Gaussian of the window's distance weights, finite, > 0 */
+  float cutoff;    /* a candidate farther than cutoff (weighted range difference, m) does not vote; <= 0: no cutoff */
+} suma_semantic_knn;
+/* suma_semantic_unproject_knn: as suma_semantic_unproject, with d_points and d_proj_idx as suma_semantic_project took /
+ *   wrote them.  Each point's candidates are its pixel (its own range, the pixel's class) and the S x S - 1 pixels
+ *   around it (the range of their winner, +inf when empty; outside the image 0 and no class: the columns do not wrap),
+ *   ranked by |range - the point's range| * (1 - the normalised Gaussian weight of the offset), ties to the lower
+ *   window index.  The first K vote for their pixel's class (the reference's argmax rule, on the index) unless it is
+ *   none, index 0 or (cutoff > 0) farther than cutoff; the most votes win, equal counts go to the lowest index.
+ *   label = label_map[winner], prob = the largest pixel prob among its voters; no vote gives (0, 0).  search = 1 or
+ *   k = 1 gives the plain back-projection for every point whose pixel class is >= 1.  Runs on the ctx stream; its
+ *   scratch (12 bytes a pixel, kept by the ctx) is used only there.  Invalid parameters return SUMA_ERR_INVALID. */
+int suma_semantic_unproject_knn(suma_ctx* ctx, const suma_semantic_params* sp, const suma_semantic_knn* knn,
+                                const suma_float4* d_points, const float* d_scores, int scores_are_logits,
+                                const int32_t* d_pixel, const int32_t* d_proj_idx, uint32_t n, float* d_labels,
+                                float* d_probs);
+/* the *_scores pipeline entries with suma_semantic_unproject_knn in front: on the preprocessing stream, behind
+ *   producer_event, with the same buffer lifetime rule (d_proj_idx is a scan buffer too).  The pipeline keeps scratch of
+ *   its own for this, used only on that stream. */
+int suma_pipeline_begin_scan_scores_knn(suma_pipeline* s, const suma_semantic_params* sp, const suma_semantic_knn* knn,
+                                        const suma_float4* d_points, const float* d_scores, int scores_are_logits,
+                                        const int32_t* d_pixel, const int32_t* d_proj_idx, uint32_t n,
+                                        void* producer_event);
+int suma_pipeline_process_scan_scores_knn(suma_pipeline* s, const suma_semantic_params* sp, const suma_semantic_knn* knn,
+                                          const suma_float4* d_points, const float* d_scores, int scores_are_logits,
+                                          const int32_t* d_pixel, const int32_t* d_proj_idx, uint32_t n,
+                                          void* producer_event, int32_t fixed_iterations);
 
 /* ---- device scratch for callers that keep scans resident in HBM (bench, replay) */
 int suma_device_alloc(suma_ctx* ctx, uint64_t bytes, void** d_ptr);

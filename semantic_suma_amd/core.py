@@ -23,7 +23,7 @@ import os
 
 import numpy as np
 
-from .types import ACC_WORDS, SURFEL_DTYPE, IcpStats, SemanticParams, SumaParams
+from .types import ACC_WORDS, SURFEL_DTYPE, IcpStats, SemanticKnnParams, SemanticParams, SumaParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -203,6 +203,10 @@ def lib():
     L.suma_semantic_unproject.argtypes = [vp, sp, vp, C.c_int, vp, u32, vp, vp]
     L.suma_pipeline_begin_scan_scores.argtypes = [vp, sp, vp, vp, C.c_int, vp, u32, vp]
     L.suma_pipeline_process_scan_scores.argtypes = [vp, sp, vp, vp, C.c_int, vp, u32, vp, i32]
+    kp = C.POINTER(SemanticKnnParams)
+    L.suma_semantic_unproject_knn.argtypes = [vp, sp, kp, vp, vp, C.c_int, vp, vp, u32, vp, vp]
+    L.suma_pipeline_begin_scan_scores_knn.argtypes = [vp, sp, kp, vp, vp, C.c_int, vp, vp, u32, vp]
+    L.suma_pipeline_process_scan_scores_knn.argtypes = [vp, sp, kp, vp, vp, C.c_int, vp, vp, u32, vp, i32]
     L.suma_device_alloc.argtypes = [vp, C.c_uint64, pp]
     L.suma_device_free.argtypes = [vp, vp]
     L.suma_device_upload.argtypes = [vp, vp, vp, C.c_uint64]
@@ -871,22 +875,44 @@ class SurfelMapping:
                        "suma_pipeline_process_scan_device")
 
     def processScanScores(self, sp: SemanticParams, d_points: int, d_scores: int, d_pixel: int, n: int,
-                          logits: bool = False, producer_event: int = 0, fixed_iterations: int = 0):
+                          logits: bool = False, producer_event: int = 0, fixed_iterations: int = 0,
+                          knn: SemanticKnnParams = None, d_proj_idx: int = 0):
         """processScanDevice with the labels / probs back-projected on the device from a network's planar [C, H, W] fp32
         scores (suma_pipeline_process_scan_scores); the preprocessing waits for ``producer_event`` (a hipEvent_t, 0 =
-        the buffers are complete), not for the host"""
-        self.ctx.check(self.L.suma_pipeline_process_scan_scores(self.h, C.byref(sp), C.c_void_p(d_points),
-                                                                C.c_void_p(d_scores), int(bool(logits)),
-                                                                C.c_void_p(d_pixel), n, C.c_void_p(producer_event or None),
-                                                                fixed_iterations),
-                       "suma_pipeline_process_scan_scores")
+        the buffers are complete), not for the host.  ``knn`` (segmentation.semantic_knn): RangeNet++'s KNN
+        post-processing in front instead (suma_pipeline_process_scan_scores_knn), which also reads ``d_proj_idx``"""
+        if knn is None:
+            self.ctx.check(self.L.suma_pipeline_process_scan_scores(self.h, C.byref(sp), C.c_void_p(d_points),
+                                                                    C.c_void_p(d_scores), int(bool(logits)),
+                                                                    C.c_void_p(d_pixel), n,
+                                                                    C.c_void_p(producer_event or None),
+                                                                    fixed_iterations),
+                           "suma_pipeline_process_scan_scores")
+            return
+        self.ctx.check(self.L.suma_pipeline_process_scan_scores_knn(self.h, C.byref(sp), C.byref(knn),
+                                                                    C.c_void_p(d_points), C.c_void_p(d_scores),
+                                                                    int(bool(logits)), C.c_void_p(d_pixel),
+                                                                    C.c_void_p(d_proj_idx or None), n,
+                                                                    C.c_void_p(producer_event or None),
+                                                                    fixed_iterations),
+                       "suma_pipeline_process_scan_scores_knn")
 
     def beginScanScores(self, sp: SemanticParams, d_points: int, d_scores: int, d_pixel: int, n: int,
-                        logits: bool = False, producer_event: int = 0):
-        self.ctx.check(self.L.suma_pipeline_begin_scan_scores(self.h, C.byref(sp), C.c_void_p(d_points),
-                                                              C.c_void_p(d_scores), int(bool(logits)), C.c_void_p(d_pixel),
-                                                              n, C.c_void_p(producer_event or None)),
-                       "suma_pipeline_begin_scan_scores")
+                        logits: bool = False, producer_event: int = 0, knn: SemanticKnnParams = None,
+                        d_proj_idx: int = 0):
+        if knn is None:
+            self.ctx.check(self.L.suma_pipeline_begin_scan_scores(self.h, C.byref(sp), C.c_void_p(d_points),
+                                                                  C.c_void_p(d_scores), int(bool(logits)),
+                                                                  C.c_void_p(d_pixel), n,
+                                                                  C.c_void_p(producer_event or None)),
+                           "suma_pipeline_begin_scan_scores")
+            return
+        self.ctx.check(self.L.suma_pipeline_begin_scan_scores_knn(self.h, C.byref(sp), C.byref(knn),
+                                                                  C.c_void_p(d_points), C.c_void_p(d_scores),
+                                                                  int(bool(logits)), C.c_void_p(d_pixel),
+                                                                  C.c_void_p(d_proj_idx or None), n,
+                                                                  C.c_void_p(producer_event or None)),
+                       "suma_pipeline_begin_scan_scores_knn")
 
     def prefetchScan(self, points, labels=None, probs=None):
         """stage a scan (pinned copy + async upload on the ingest thread / copy stream); the arrays are kept alive

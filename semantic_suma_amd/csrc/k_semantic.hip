@@ -138,12 +138,12 @@ __global__ void __launch_bounds__(256)
 }
 
 /* ---- host side ---- */
-static int sem_fail(suma_ctx* c, int code, const std::string& msg) {
+int sem_fail(suma_ctx* c, int code, const std::string& msg) {
   c->err = msg;
   return code;
 }
 
-static int semantic_check(suma_ctx* c, const suma_semantic_params* sp) {
+int semantic_check(suma_ctx* c, const suma_semantic_params* sp) {
   if (!sp) return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_params: NULL");
   if (sp->n_classes == 0 || sp->n_classes > SUMA_SEM_MAX_CLASSES)
     return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_params: n_classes = " + std::to_string(sp->n_classes) +

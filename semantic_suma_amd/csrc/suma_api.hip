@@ -317,6 +317,7 @@ extern "C" int suma_ctx_create(const suma_params* params, int hip_device, suma_c
   c->sem_zbuf_cap = 0;
   c->sem_labels = c->sem_probs = nullptr;
   c->sem_cap = 0;
+  c->sem_knn[0] = c->sem_knn[1] = SemKnnScratch{nullptr, 0};
   c->filt_cap = 0;
   derive(c);
   c->P = (size_t)params->data_width * params->data_height;
@@ -441,7 +442,8 @@ extern "C" void suma_ctx_destroy(suma_ctx* c) {
                  c->zbuf_b,    c->surfels[0],  c->surfels[1],  c->poses,       c->poses_inv, c->tile_status, c->tile_group,
                  c->ds,        c->gn,          c->gn_partial,  c->gn_history,  c->gn_T0s,    c->cache_arena,
                  c->cache_slots, c->scan_points, c->scan_labels, c->scan_probs, c->sync_flags, c->zbuf_k1,
-                 c->filt_temp, c->filt_sort, c->filt_sort_tmp, c->sem_zbuf, c->sem_labels, c->sem_probs};
+                 c->filt_temp, c->filt_sort, c->filt_sort_tmp, c->sem_zbuf, c->sem_labels, c->sem_probs,
+                 c->sem_knn[0].buf, c->sem_knn[1].buf};
   for (void* p : dev)
     if (p) hipFree(p);
   if (c->h_ds) hipHostFree(c->h_ds);

@@ -149,6 +149,12 @@ struct HostEntryTimes {
   uint32_t copy_threads; /* caller + helpers that took a share of the copies */
 };
 
+/* a record image of the KNN back-projection (k_semantic_knn.hip): P x {class, prob bits} then P ranges, cap pixels */
+struct SemKnnScratch {
+  void* buf;
+  uint32_t cap;
+};
+
 struct suma_ctx {
   suma_params p;
   int device;
@@ -193,6 +199,9 @@ struct suma_ctx {
   size_t sem_zbuf_cap;
   float *sem_labels, *sem_probs; /* the back-projection of the scan pipeline's scores entry */
   uint32_t sem_cap;
+  /* KNN post-processing (k_semantic_knn.hip): [0] suma_semantic_unproject_knn (ctx stream), [1] the pipeline's
+   * scores_knn entry (its input stream); each only grows */
+  SemKnnScratch sem_knn[2];
 
   /* ICP */
   const suma_frame *icp_current, *icp_model;
@@ -325,6 +334,9 @@ int pipeline_update_pose_impl(suma_pipeline* s, int32_t fixed_iterations);
 int pipeline_update_map_impl(suma_pipeline* s);
 /* the stream behind which a scan's input buffers are free again (the preprocessing that read them runs there) */
 hipStream_t pipeline_input_stream(suma_pipeline* s);
+/* k_semantic.hip: parameter check of the semantic entries (sets c->err) */
+int sem_fail(suma_ctx* c, int code, const std::string& msg);
+int semantic_check(suma_ctx* c, const suma_semantic_params* sp);
 /* suma_ingest.hip */
 void ingest_destroy(suma_ctx* c);
 void ingest_drain(suma_ctx* c);

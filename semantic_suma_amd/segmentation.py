@@ -8,7 +8,9 @@ is the caller's PyTorch model, and the two data-parallel stages around it are HI
     project(points)            N x (x, y, z, remission) -> input [1, 5, H, W] fp32 (range, x, y, z, remission),
                                normalised (v - mean) / std; also keeps pixel[N] and proj_idx[H, W]
     unproject(scores, logits)  planar [1, C, H, W] fp32 scores -> per-point (labels[N], probs[N]) by the reference's
-                               argmax rule (the last maximum wins, all-negative scores give (0, 0), NaN never wins)
+                               argmax rule (the last maximum wins, all-negative scores give (0, 0), NaN never wins);
+                               knn=semantic_knn(): RangeNet++'s KNN post-processing instead (csrc/k_semantic_knn.hip),
+                               a vote among the points nearest in range around each point's pixel
     process_scan(mapping, ...) project -> model(input) -> SurfelMapping.processScanScores: the back-projection and K1-K3
                                run on the pipeline's preprocessing stream behind an event, without a host synchronisation
 
@@ -27,6 +29,12 @@ process_scan that includes the pipeline's preprocessing, which its ctx stream jo
 ``record_stream`` on the context's stream: the caching allocator would record events on it after the context, and
 with it the stream, may be gone.)  Tensors made on other streams follow torch's usual multi-stream rules.
 
+KNN post-processing (RangeNet++, Milioto et al., IROS 2019, section III-D; opt-in, ``knn=semantic_knn()``): a point
+hidden behind a nearer one in its pixel otherwise takes that one's class, so at every depth edge the foreground's
+class bleeds onto the background.  With ``knn`` each point's label is voted by the k candidates nearest in range among
+its pixel and the search x search pixels around it (weighted by an inverted Gaussian of the offset, class 0 and
+candidates farther than ``cutoff`` do not vote).  The arithmetic is stated in csrc/k_semantic_knn.hip.
+
 The means and stds have no defaults: they belong to the trained model (RangeNet++ ships them in its arch_cfg.yaml
 ``sensor: img_means / img_stds``).  The label map defaults to SemanticKITTI's learning_map_inv.  No weights ship here.
 """
@@ -38,7 +46,7 @@ import torch
 
 from . import kitti
 from .core import Context, SumaError, SurfelMapping
-from .types import SEM_CHANNELS, SEM_MAX_CLASSES, SemanticParams
+from .types import SEM_CHANNELS, SEM_MAX_CLASSES, SemanticKnnParams, SemanticParams
 
 
 def semantic_params(width: int, height: int, fov_up: float, fov_down: float, means, stds, n_classes: int = 20,
@@ -62,6 +70,12 @@ def semantic_params(width: int, height: int, fov_up: float, fov_down: float, mea
     for j, v in enumerate(label_map):
         sp.label_map[j] = int(v)
     return sp
+
+
+def semantic_knn(search: int = 5, k: int = 5, sigma: float = 1.0, cutoff: float = 1.0) -> SemanticKnnParams:
+    """suma_semantic_knn, RangeNet++'s published defaults: a search x search window (odd, 1 .. 9), k voters
+    (1 .. search^2), the Gaussian's sigma (> 0) and the range cutoff in metres (<= 0: none).  The library checks them."""
+    return SemanticKnnParams(search=search, k=k, sigma=sigma, cutoff=cutoff)
 
 
 def _check_one_hip_runtime():
@@ -95,6 +109,7 @@ class SemanticFrontEnd:
         self.n_classes = int(semantic_params.n_classes)
         self.pixel = None     # int32 [N]: pixel of every point of the last projection, -1 = not projected
         self.proj_idx = None  # int32 [H, W]: winning point of every pixel, -1 = empty
+        self.points = None    # float32 [N, 4]: the points of the last projection (the KNN back-projection reads them)
         self.input = None     # fp32 [1, 5, H, W]
         self._event = None
 
@@ -126,7 +141,7 @@ class SemanticFrontEnd:
                                                     C.c_void_p(inp.data_ptr()), C.c_void_p(pixel.data_ptr()),
                                                     C.c_void_p(proj_idx.data_ptr())),
                        "suma_semantic_project")
-        self.input, self.pixel, self.proj_idx = inp, pixel, proj_idx
+        self.input, self.pixel, self.proj_idx, self.points = inp, pixel, proj_idx, points
         return inp
 
     def project(self, points):
@@ -139,13 +154,21 @@ class SemanticFrontEnd:
         cur.wait_stream(ext)
         return inp
 
-    def unproject(self, scores, logits: bool = False, pixel=None):
+    def unproject(self, scores, logits: bool = False, pixel=None, knn: SemanticKnnParams = None, points=None,
+                  proj_idx=None):
         """planar fp32 scores [1, C, H, W] -> (labels[N], probs[N]) float32 for the points of the last projection
-        (or of ``pixel``); logits=True applies a softmax over C first"""
+        (or of ``pixel``); logits=True applies a softmax over C first.  ``knn`` (semantic_knn()): RangeNet++'s KNN
+        post-processing, which also reads the projection's points and proj_idx (pass ``points`` / ``proj_idx`` with
+        ``pixel``)"""
         scores = self._scores(scores)
-        pixel = self.pixel if pixel is None else pixel
+        if pixel is None:
+            pixel, points_, proj_idx_ = self.pixel, self.points, self.proj_idx
+            points = points_ if points is None else points
+            proj_idx = proj_idx_ if proj_idx is None else proj_idx
         if pixel is None:
             raise ValueError("unproject: no projection yet (call project first or pass pixel)")
+        if knn is not None and (points is None or proj_idx is None):
+            raise ValueError("unproject: knn needs the projection's points and proj_idx with an explicit pixel")
         n = pixel.shape[0]
         dev = scores.device
         labels = torch.empty(n, dtype=torch.float32, device=dev)
@@ -153,16 +176,31 @@ class SemanticFrontEnd:
         cur = torch.cuda.current_stream(dev)
         ext = self._stream(dev)
         ext.wait_stream(cur)
-        self.ctx.check(self.L.suma_semantic_unproject(self.ctx.h, C.byref(self.sp), C.c_void_p(scores.data_ptr()),
-                                                      int(bool(logits)), C.c_void_p(pixel.data_ptr()), n,
-                                                      C.c_void_p(labels.data_ptr()), C.c_void_p(probs.data_ptr())),
-                       "suma_semantic_unproject")
+        if knn is None:
+            self.ctx.check(self.L.suma_semantic_unproject(self.ctx.h, C.byref(self.sp), C.c_void_p(scores.data_ptr()),
+                                                          int(bool(logits)), C.c_void_p(pixel.data_ptr()), n,
+                                                          C.c_void_p(labels.data_ptr()), C.c_void_p(probs.data_ptr())),
+                           "suma_semantic_unproject")
+        else:
+            points = self._points(points)
+            if points.shape[0] != n or proj_idx.numel() != self.width * self.height:
+                raise ValueError("unproject: points / pixel / proj_idx are not of one projection")
+            self.ctx.check(self.L.suma_semantic_unproject_knn(self.ctx.h, C.byref(self.sp), C.byref(knn),
+                                                              C.c_void_p(points.data_ptr()),
+                                                              C.c_void_p(scores.data_ptr()), int(bool(logits)),
+                                                              C.c_void_p(pixel.data_ptr()),
+                                                              C.c_void_p(proj_idx.data_ptr()), n,
+                                                              C.c_void_p(labels.data_ptr()),
+                                                              C.c_void_p(probs.data_ptr())),
+                           "suma_semantic_unproject_knn")
         cur.wait_stream(ext)
         return labels, probs
 
-    def process_scan(self, mapping, points, model, fixed_iterations: int = 0, logits: bool = False):
+    def process_scan(self, mapping, points, model, fixed_iterations: int = 0, logits: bool = False,
+                     knn: SemanticKnnParams = None):
         """SurfelMapping.processScan with the labels of ``model``: project -> model(input) -> the pipeline's scores
-        entry.  The model runs on the context's stream; the pipeline's preprocessing waits for it on the device."""
+        entry (its KNN form with ``knn``).  The model runs on the context's stream; the pipeline's preprocessing waits
+        for it on the device."""
         mapping = self.mapping if mapping is None else mapping
         if not isinstance(mapping, SurfelMapping):
             raise TypeError("process_scan needs a core.SurfelMapping")
@@ -177,7 +215,8 @@ class SemanticFrontEnd:
             event = torch.cuda.Event()
             event.record(ext)
         mapping.processScanScores(self.sp, points.data_ptr(), scores.data_ptr(), self.pixel.data_ptr(), points.shape[0],
-                                  logits=logits, producer_event=event.cuda_event, fixed_iterations=fixed_iterations)
+                                  logits=logits, producer_event=event.cuda_event, fixed_iterations=fixed_iterations,
+                                  knn=knn, d_proj_idx=self.proj_idx.data_ptr())
         self._event = event  # the preprocessing stream's wait may still be pending: keep the event until the next scan
         # the pipeline's ctx stream has passed its preprocessing once it has passed this scan's map update
         if mapping.ctx.h.value != self.ctx.h.value:

@@ -64,6 +64,12 @@ class SemanticParams(C.Structure):
     ]
 
 
+class SemanticKnnParams(C.Structure):
+    """``struct suma_semantic_knn``: RangeNet++'s KNN post-processing of the back-projection (window ``search`` x
+    ``search``, ``k`` voters, Gaussian ``sigma``, range ``cutoff``; segmentation.semantic_knn)."""
+    _fields_ = [("search", u32), ("k", u32), ("sigma", f32), ("cutoff", f32)]
+
+
 class IcpStats(C.Structure):
     _fields_ = [("error", f64), ("inlier_residual", f64), ("valid", u32), ("outlier", u32), ("inlier", u32),
                 ("invalid", u32), ("iterations", u32), ("converged", u32)]
