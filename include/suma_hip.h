@@ -424,6 +424,48 @@ int suma_pipeline_process_scan_scores_knn(suma_pipeline* s, const suma_semantic_
                                           const int32_t* d_pixel, const int32_t* d_proj_idx, uint32_t n,
                                           void* producer_event, int32_t fixed_iterations);
 
+/* ---- SurfelMap::draw (SurfelMap.cpp:1167-1230): the viewer's picture of the active map, without a graphics pipeline.
+ *      The reference's draw_surfels.{vert,geom,frag} program run by a compute rasteriser (k_draw.hip states the
+ *      arithmetic).  (Kept here, not in suma_types.h, for the reason given at suma_semantic_params.) */
+#define SUMA_DRAW_MAX_LIGHTS 10  /* draw_surfels.geom: uniform Light lights[10] */
+#define SUMA_DRAW_MAX_SIZE 8192u /* width and height: 1 .. SUMA_DRAW_MAX_SIZE */
+#define SUMA_DRAW_COLORS 260     /* texels of the semantic colour map (SurfelMap::setColorMap, SurfelMap.cpp:1238-1256) */
+typedef struct suma_draw_light {
+  float position[4]; /* w < 0.0001: a directional light from -position.xyz */
+  float ambient[3], diffuse[3], specular[3];
+} suma_draw_light;
+typedef struct suma_draw_params {
+  float mvp[16];          /* column-major: projection * view * conversion (ViewportWidget.cpp:913) */
+  float view_pos[3];      /* camera position in the map frame (ViewportWidget.cpp:567, 909-911) */
+  uint32_t width, height; /* 1 .. SUMA_DRAW_MAX_SIZE each */
+  int32_t color_mode;     /* 0 .. 5, SurfelMapVisualOptions::colorMode (SurfelMap.h:23-33), default 5:
+                             0 Phong, 1 normal shading, 2 abs(normal), 3 viridis(confidence), 4 surfel colour, 5 semantic */
+  float conf_threshold;   /* default 10 */
+  int32_t backface_culling; /* default 0 */
+  int32_t use_stability;    /* default 0: SurfelMap never sets it on its draw program (SurfelMap.cpp:187-229) */
+  float clear_color[4];     /* RGBA in [0, 1], default white (ViewportWidget.cpp:472) */
+  uint32_t num_lights;      /* 0 .. SUMA_DRAW_MAX_LIGHTS, default 1 */
+  suma_draw_light lights[SUMA_DRAW_MAX_LIGHTS];
+  float mat_ambient[3], mat_diffuse[3], mat_specular[3], mat_emission[3], mat_shininess, mat_alpha;
+  uint8_t color_map[SUMA_DRAW_COLORS][3]; /* label id -> RGB (setColorMap has already swapped the BGR of the config) */
+} suma_draw_params;
+
+/* The state SurfelMap's constructor leaves on draw_surfels_ (SurfelMap.cpp:195-229: the last value of every uniform it
+ * sets twice, num_lights = 1; lights 1-4 hold its "evenly distributed sun light") and SurfelMapVisualOptions' defaults
+ * (color_mode 5, conf_threshold 10, no back-face culling), white clear colour; mvp, view_pos, width, height and color_map
+ * are the caller's (zeroed here). */
+void suma_draw_params_default(suma_draw_params* dp);
+
+/* suma_map_draw: the active map (the buffer SurfelMap::draw reads, suma_map_export_surfels) drawn on the ctx stream,
+ *   behind the last update / upload / update_poses, with a 24-bit GL_LESS depth test and no blending.
+ *   d_rgba8: width * height RGBA8 pixels (4 bytes each, R first) in glReadPixels order -- row 0 is the BOTTOM row.
+ *   d_ids (optional): width * height int32, the index of the surfel that won each pixel, -1 where nothing was drawn.
+ *   Returns without synchronising; both buffers are complete once the ctx stream has passed the call.  The z-buffer
+ *   (8 bytes a pixel, grown to the largest image drawn) and a queue of max_surfels entries are the ctx's; nothing else of
+ *   the ctx changes (map, poses, counters, render de-duplication).  Invalid parameters return SUMA_ERR_INVALID with a
+ *   message and launch nothing. */
+int suma_map_draw(suma_ctx* ctx, const suma_draw_params* dp, void* d_rgba8, int32_t* d_ids);
+
 /* ---- device scratch for callers that keep scans resident in HBM (bench, replay) */
 int suma_device_alloc(suma_ctx* ctx, uint64_t bytes, void** d_ptr);
 int suma_device_free(suma_ctx* ctx, void* d_ptr);

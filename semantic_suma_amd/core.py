@@ -7,7 +7,7 @@ stand for (PRBonn/semantic_suma, src/core):
     Preprocessing    src/core/Preprocessing.h:47-58          process(points, frame, labels, probs, timestamp)
     Frame2Model      src/core/Frame2Model.h:28-73 / Objective.h:14-82
     LieGaussNewton   src/core/LieGaussNewton.h:25-76         minimize(objective, T0), pose(), history()
-    SurfelMap        src/core/SurfelMap.h:36-78              update / render* / *MapFrame / updatePoses / size
+    SurfelMap        src/core/SurfelMap.h:36-78              update / render* / *MapFrame / updatePoses / size / draw
     SurfelMapping    src/core/SurfelMapping.h:47             processScan(scan)
 
 Everything here is plumbing: numpy arrays in, ctypes calls into ``libsuma_hip.so`` (hand-written
@@ -23,7 +23,8 @@ import os
 
 import numpy as np
 
-from .types import ACC_WORDS, SURFEL_DTYPE, IcpStats, SemanticKnnParams, SemanticParams, SumaParams
+from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX_LIGHTS, SURFEL_DTYPE, DrawParams,
+                    IcpStats, SemanticKnnParams, SemanticParams, SumaParams)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -207,6 +208,7 @@ def lib():
     L.suma_semantic_unproject_knn.argtypes = [vp, sp, kp, vp, vp, C.c_int, vp, vp, u32, vp, vp]
     L.suma_pipeline_begin_scan_scores_knn.argtypes = [vp, sp, kp, vp, vp, C.c_int, vp, vp, u32, vp]
     L.suma_pipeline_process_scan_scores_knn.argtypes = [vp, sp, kp, vp, vp, C.c_int, vp, vp, u32, vp, i32]
+    L.suma_map_draw.argtypes = [vp, C.POINTER(DrawParams), vp, vp]
     L.suma_device_alloc.argtypes = [vp, C.c_uint64, pp]
     L.suma_device_free.argtypes = [vp, vp]
     L.suma_device_upload.argtypes = [vp, vp, vp, C.c_uint64]
@@ -552,6 +554,84 @@ def se3_exp(x):
     return T
 
 
+# ---- camera helpers for SurfelMap.draw (row-major numpy 4x4, float64; mvp = projection @ view @ ROSE2GL)
+# the viewport's conversion_ from the robot frame (x forward, y left, z up) to GL (x right, y up, z backwards):
+# GL x = -y, GL y = z, GL z = -x
+ROSE2GL = np.array([[0.0, -1.0, 0.0, 0.0], [0.0, 0.0, 1.0, 0.0], [-1.0, 0.0, 0.0, 0.0], [0.0, 0.0, 0.0, 1.0]])
+
+
+def perspective(fovy_deg: float, aspect: float, near: float, far: float) -> np.ndarray:
+    """gluPerspective (the viewport's camera: 45 degrees, near 0.1, far 10000, ViewportWidget.cpp:484-487)"""
+    f = 1.0 / np.tan(np.radians(fovy_deg) / 2.0)
+    return np.array([[f / aspect, 0.0, 0.0, 0.0], [0.0, f, 0.0, 0.0],
+                     [0.0, 0.0, (far + near) / (near - far), 2.0 * far * near / (near - far)], [0.0, 0.0, -1.0, 0.0]])
+
+
+def orthographic(left: float, right: float, bottom: float, top: float, near: float, far: float) -> np.ndarray:
+    """glOrtho"""
+    return np.array([[2.0 / (right - left), 0.0, 0.0, -(right + left) / (right - left)],
+                     [0.0, 2.0 / (top - bottom), 0.0, -(top + bottom) / (top - bottom)],
+                     [0.0, 0.0, -2.0 / (far - near), -(far + near) / (far - near)], [0.0, 0.0, 0.0, 1.0]])
+
+
+def look_at(eye, target, up) -> np.ndarray:
+    """gluLookAt: the view matrix of a camera at `eye` looking at `target` (all in the frame the matrix maps from)"""
+    eye, target, up = (np.asarray(v, dtype=np.float64).reshape(3) for v in (eye, target, up))
+    f = target - eye
+    f = f / np.linalg.norm(f)
+    s = np.cross(f, up)
+    s = s / np.linalg.norm(s)
+    u = np.cross(s, f)
+    V = np.eye(4)
+    V[0, :3], V[1, :3], V[2, :3] = s, u, -f
+    V[:3, 3] = -V[:3, :3] @ eye
+    return V
+
+
+def draw_params(mvp, width: int, height: int, view_pos, color_mode: int = 5, color_map=None,
+                conf_threshold: float = 10.0, backface_culling: bool = False, use_stability: bool = False,
+                clear_color=(1.0, 1.0, 1.0, 1.0), lights=None, material=None) -> DrawParams:
+    """a suma_draw_params: ``mvp`` row-major 4x4 (projection @ view @ ROSE2GL for the viewer's camera), ``view_pos`` the
+    camera position in the map frame, ``color_map`` [260, 3] uint8 RGB (default kitti.semantic_color_map()); lights and
+    material default to what SurfelMap's constructor leaves (types.DRAW_LIGHTS[:1], types.DRAW_MATERIAL)"""
+    from .kitti import semantic_color_map
+    dp = DrawParams()
+    m = _cm(mvp, np.float32).reshape(-1)
+    for k in range(16):
+        dp.mvp[k] = float(m[k])
+    for k, v in enumerate(np.asarray(view_pos, dtype=np.float32).reshape(3)):
+        dp.view_pos[k] = float(v)
+    dp.width, dp.height = int(width), int(height)
+    dp.color_mode, dp.conf_threshold = int(color_mode), float(conf_threshold)
+    dp.backface_culling, dp.use_stability = int(bool(backface_culling)), int(bool(use_stability))
+    for k, v in enumerate(clear_color):
+        dp.clear_color[k] = float(v)
+    lights = DRAW_LIGHTS[:1] if lights is None else list(lights)
+    dp.num_lights = len(lights)
+    for i, L in enumerate(lights[:DRAW_MAX_LIGHTS]):
+        for name in ("position", "ambient", "diffuse", "specular"):
+            arr = getattr(dp.lights[i], name)
+            for k, v in enumerate(L[name]):
+                arr[k] = float(v)
+    mat = dict(DRAW_MATERIAL, **(material or {}))
+    for name in ("ambient", "diffuse", "specular", "emission"):
+        arr = getattr(dp, "mat_" + name)
+        for k, v in enumerate(mat[name]):
+            arr[k] = float(v)
+    dp.mat_shininess, dp.mat_alpha = float(mat["shininess"]), float(mat["alpha"])
+    cmap = semantic_color_map() if color_map is None else np.asarray(color_map, dtype=np.uint8)
+    assert cmap.shape == (DRAW_COLORS, 3), cmap.shape
+    C.memmove(C.addressof(dp.color_map), np.ascontiguousarray(cmap).ctypes.data, DRAW_COLORS * 3)
+    return dp
+
+
+def _dev(p):
+    """a device address: an int, or anything with data_ptr() (a torch tensor on the ctx's device)"""
+    if hasattr(p, "data_ptr"):
+        return C.c_void_p(p.data_ptr())
+    return None if p is None or int(p) == 0 else C.c_void_p(int(p))
+
+
 class SurfelMap:
     """SurfelMap.h:36-78"""
 
@@ -623,6 +703,43 @@ class SurfelMap:
         p, n = C.c_void_p(), C.c_uint32(0)
         self.ctx.check(self.ctx.L.suma_map_export_surfels(self.ctx.h, C.byref(p), C.byref(n)), "suma_map_export_surfels")
         return p.value, n.value
+
+    def draw_device(self, d_rgba8, d_ids=None, mvp=None, width: int = 0, height: int = 0, view_pos=(0.0, 0.0, 0.0),
+                    params: DrawParams = None, **options):
+        """SurfelMap::draw (SurfelMap.cpp:1167-1230) into caller-owned device buffers (suma_map_draw): ``d_rgba8`` width x
+        height x 4 bytes, ``d_ids`` (optional) width x height int32; rows in glReadPixels order (row 0 = bottom).  Takes
+        a prepared ``params`` (draw_params) or builds one from the arguments.  Enqueued on the ctx stream, not waited for."""
+        dp = params if params is not None else draw_params(mvp, width, height, view_pos, **options)
+        self.ctx.check(self.ctx.L.suma_map_draw(self.ctx.h, C.byref(dp), _dev(d_rgba8), _dev(d_ids)), "suma_map_draw")
+        return dp
+
+    def draw(self, mvp, width: int, height: int, view_pos, color_mode: int = 5, color_map=None, ids: bool = False,
+             **options):
+        """SurfelMap::draw as a picture: uint8 [height, width, 4] RGBA with row 0 at the TOP (ready to save), and with
+        ``ids=True`` also the int32 [height, width] index of the surfel drawn at each pixel (-1: none).  ``options``:
+        conf_threshold, backface_culling, use_stability, clear_color, lights, material (draw_params)."""
+        dp = draw_params(mvp, width, height, view_pos, color_mode=color_mode, color_map=color_map, **options)
+        P = int(width) * int(height)
+        d_rgba = C.c_void_p()
+        d_ids = C.c_void_p()
+        L, h = self.ctx.L, self.ctx.h
+        self.ctx.check(L.suma_device_alloc(h, 4 * P, C.byref(d_rgba)), "suma_device_alloc")
+        try:
+            if ids:
+                self.ctx.check(L.suma_device_alloc(h, 4 * P, C.byref(d_ids)), "suma_device_alloc")
+            self.ctx.check(L.suma_map_draw(h, C.byref(dp), d_rgba, d_ids if ids else None), "suma_map_draw")
+            img = np.empty((int(height), int(width), 4), dtype=np.uint8)
+            self.ctx.check(L.suma_device_download(h, _ptr(img), d_rgba, 4 * P), "suma_device_download")
+            idm = None
+            if ids:
+                idm = np.empty((int(height), int(width)), dtype=np.int32)
+                self.ctx.check(L.suma_device_download(h, _ptr(idm), d_ids, 4 * P), "suma_device_download")
+        finally:
+            L.suma_device_free(h, d_rgba)
+            if d_ids.value:
+                L.suma_device_free(h, d_ids)
+        img = img[::-1].copy()
+        return (img, idm[::-1].copy()) if ids else img
 
     def getDataSurfels(self):
         """SurfelMap::getDataSurfels (SurfelMap.h:64): (device address, first, count) -- the new surfels of the last

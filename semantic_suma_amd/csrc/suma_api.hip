@@ -318,6 +318,9 @@ extern "C" int suma_ctx_create(const suma_params* params, int hip_device, suma_c
   c->sem_labels = c->sem_probs = nullptr;
   c->sem_cap = 0;
   c->sem_knn[0] = c->sem_knn[1] = SemKnnScratch{nullptr, 0};
+  c->draw_zbuf = nullptr;
+  c->draw_zbuf_cap = 0;
+  c->draw_queue = nullptr;
   c->filt_cap = 0;
   derive(c);
   c->P = (size_t)params->data_width * params->data_height;
@@ -443,7 +446,7 @@ extern "C" void suma_ctx_destroy(suma_ctx* c) {
                  c->ds,        c->gn,          c->gn_partial,  c->gn_history,  c->gn_T0s,    c->cache_arena,
                  c->cache_slots, c->scan_points, c->scan_labels, c->scan_probs, c->sync_flags, c->zbuf_k1,
                  c->filt_temp, c->filt_sort, c->filt_sort_tmp, c->sem_zbuf, c->sem_labels, c->sem_probs,
-                 c->sem_knn[0].buf, c->sem_knn[1].buf};
+                 c->sem_knn[0].buf, c->sem_knn[1].buf, c->draw_zbuf, c->draw_queue};
   for (void* p : dev)
     if (p) hipFree(p);
   if (c->h_ds) hipHostFree(c->h_ds);

@@ -202,6 +202,11 @@ struct suma_ctx {
   /* KNN post-processing (k_semantic_knn.hip): [0] suma_semantic_unproject_knn (ctx stream), [1] the pipeline's
    * scores_knn entry (its input stream); each only grows */
   SemKnnScratch sem_knn[2];
+  /* SurfelMap::draw (k_draw.hip), allocated on first use: z-buffer of the largest image drawn (left cleared by every
+   * resolve) and the large-quad queue, max_surfels ids + its counter (left at 0) */
+  unsigned long long* draw_zbuf;
+  size_t draw_zbuf_cap;
+  uint32_t* draw_queue;
 
   /* ICP */
   const suma_frame *icp_current, *icp_model;

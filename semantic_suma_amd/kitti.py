@@ -49,6 +49,32 @@ LEARNING_MAP_INV = {0: 0, 1: 10, 2: 11, 3: 15, 4: 18, 5: 20, 6: 30, 7: 31, 8: 32
                     14: 51, 15: 70, 16: 71, 17: 72, 18: 80, 19: 81}
 
 
+# SemanticKITTI's colour of every label id, as the dataset's definition (semantic-kitti.yaml, `color_map`) gives it:
+# BGR, the order RangeNet++'s data_cfg.yaml and the reference's colour-map reader keep.
+SEMANTIC_KITTI_COLORS_BGR = {
+    0: (0, 0, 0), 1: (0, 0, 255), 10: (245, 150, 100), 11: (245, 230, 100), 13: (250, 80, 100), 15: (150, 60, 30),
+    16: (255, 0, 0), 18: (180, 30, 80), 20: (255, 0, 0), 30: (30, 30, 255), 31: (200, 40, 255), 32: (90, 30, 150),
+    40: (255, 0, 255), 44: (255, 150, 255), 48: (75, 0, 75), 49: (75, 0, 175), 50: (0, 200, 255), 51: (50, 120, 255),
+    52: (0, 150, 255), 60: (170, 255, 150), 70: (0, 175, 0), 71: (0, 60, 135), 72: (80, 240, 150), 80: (150, 240, 255),
+    81: (0, 0, 255), 99: (255, 255, 50), 252: (245, 150, 100), 253: (200, 40, 255), 254: (30, 30, 255),
+    255: (90, 30, 150), 256: (255, 0, 0), 257: (250, 80, 100), 258: (180, 30, 80), 259: (255, 0, 0),
+}
+
+
+def semantic_color_map(table=None) -> np.ndarray:
+    """-> uint8 [260, 3] RGB: the texture SurfelMap::setColorMap builds (SurfelMap.cpp:1238-1256) from a {label id: (B, G,
+    R)} table (RangeNet++'s data_cfg.yaml order; default: SEMANTIC_KITTI_COLORS_BGR).  Its rule: entry i is the table's
+    colour of id i with blue and red swapped, black where the table has no id i; ids outside 0 .. 259 are ignored."""
+    table = SEMANTIC_KITTI_COLORS_BGR if table is None else table
+    out = np.zeros((260, 3), dtype=np.uint8)
+    for k, bgr in table.items():
+        k = int(k)
+        if 0 <= k < 260:
+            b, g, r = (int(v) for v in bgr)
+            out[k] = (r, g, b)
+    return out
+
+
 def remap_labels(raw_ids: np.ndarray) -> np.ndarray:
     """raw SemanticKITTI ids -> the ids RangeNet++ would report: learning_map followed by learning_map_inv
     (e.g. moving-car 252 -> 10, bus 13 / on-rails 16 / moving-bus 257 -> other-vehicle 20, lane-marking 60 -> road 40,

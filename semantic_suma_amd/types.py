@@ -70,6 +70,37 @@ class SemanticKnnParams(C.Structure):
     _fields_ = [("search", u32), ("k", u32), ("sigma", f32), ("cutoff", f32)]
 
 
+DRAW_MAX_LIGHTS = 10   # SUMA_DRAW_MAX_LIGHTS
+DRAW_MAX_SIZE = 8192   # SUMA_DRAW_MAX_SIZE: width and height
+DRAW_COLORS = 260      # SUMA_DRAW_COLORS: texels of the semantic colour map
+
+
+class DrawLight(C.Structure):
+    """``struct suma_draw_light``: one light of draw_surfels.geom (position.w < 0.0001: directional)"""
+    _fields_ = [("position", f32 * 4), ("ambient", f32 * 3), ("diffuse", f32 * 3), ("specular", f32 * 3)]
+
+
+class DrawParams(C.Structure):
+    """``struct suma_draw_params``: camera, viewport and the uniforms of SurfelMap::draw (core.SurfelMap.draw)"""
+    _fields_ = [
+        ("mvp", f32 * 16), ("view_pos", f32 * 3), ("width", u32), ("height", u32), ("color_mode", i32),
+        ("conf_threshold", f32), ("backface_culling", i32), ("use_stability", i32), ("clear_color", f32 * 4),
+        ("num_lights", u32), ("lights", DrawLight * DRAW_MAX_LIGHTS),
+        ("mat_ambient", f32 * 3), ("mat_diffuse", f32 * 3), ("mat_specular", f32 * 3), ("mat_emission", f32 * 3),
+        ("mat_shininess", f32), ("mat_alpha", f32), ("color_map", (C.c_uint8 * 3) * DRAW_COLORS),
+    ]
+
+
+# SurfelMap's constructor (SurfelMap.cpp:195-229): the value each uniform of draw_surfels_ is left with.  Only light 0
+# is used (num_lights = 1); lights 1-4 are the "evenly distributed sun light" it also sets.
+DRAW_LIGHTS = [
+    dict(position=(0.0, -1.0, -1.0, 0.0), ambient=(0.4, 0.4, 0.4), diffuse=(0.6, 0.52944, 0.4566), specular=(0.3, 0.3, 0.3)),
+] + [dict(position=d, ambient=(0.1,) * 3, diffuse=(0.1,) * 3, specular=(0.1,) * 3)
+     for d in ((1, -1, 1, 0), (-1, -1, 1, 0), (1, -1, -1, 0), (-1, -1, -1, 0))]
+DRAW_MATERIAL = dict(ambient=(0.75, 0.65, 0.5), diffuse=(1.0, 0.9, 0.7), specular=(1.0, 1.0, 1.0),
+                     emission=(0.0, 0.0, 0.0), shininess=16.0, alpha=1.0)
+
+
 class IcpStats(C.Structure):
     _fields_ = [("error", f64), ("inlier_residual", f64), ("valid", u32), ("outlier", u32), ("inlier", u32),
                 ("invalid", u32), ("iterations", u32), ("converged", u32)]
