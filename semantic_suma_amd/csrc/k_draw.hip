@@ -517,39 +517,27 @@ extern "C" void suma_draw_params_default(suma_draw_params* d) {
   d->mat_alpha = 1.0f;
 }
 
-static int draw_fail(suma_ctx* c, const std::string& msg) {
-  c->err = msg;
-  return SUMA_ERR_INVALID;
-}
-
 extern "C" int suma_map_draw(suma_ctx* c, const suma_draw_params* dp, void* d_rgba8, int32_t* d_ids) {
   if (!c) return SUMA_ERR_INVALID;
-  if (!dp) return draw_fail(c, "suma_map_draw: NULL parameters");
-  if (!d_rgba8) return draw_fail(c, "suma_map_draw: NULL colour buffer");
+  if (!dp) return fail(c, SUMA_ERR_INVALID, "suma_map_draw: NULL parameters");
+  if (!d_rgba8) return fail(c, SUMA_ERR_INVALID, "suma_map_draw: NULL colour buffer");
   if (dp->width < 1 || dp->width > SUMA_DRAW_MAX_SIZE || dp->height < 1 || dp->height > SUMA_DRAW_MAX_SIZE)
-    return draw_fail(c, "suma_map_draw: width x height = " + std::to_string(dp->width) + " x " +
-                            std::to_string(dp->height) + " (each must be 1 .. " + std::to_string(SUMA_DRAW_MAX_SIZE) + ")");
+    return fail(c, SUMA_ERR_INVALID, "suma_map_draw: width x height = " + std::to_string(dp->width) + " x " +
+                                     std::to_string(dp->height) + " (each must be 1 .. " +
+                                     std::to_string(SUMA_DRAW_MAX_SIZE) + ")");
   if (dp->color_mode < 0 || dp->color_mode > 5)
-    return draw_fail(c, "suma_map_draw: color_mode = " + std::to_string(dp->color_mode) + " (must be 0 .. 5)");
+    return fail(c, SUMA_ERR_INVALID,
+                "suma_map_draw: color_mode = " + std::to_string(dp->color_mode) + " (must be 0 .. 5)");
   if (dp->num_lights > SUMA_DRAW_MAX_LIGHTS)
-    return draw_fail(c, "suma_map_draw: num_lights = " + std::to_string(dp->num_lights) + " (at most " +
-                            std::to_string(SUMA_DRAW_MAX_LIGHTS) + ")");
+    return fail(c, SUMA_ERR_INVALID, "suma_map_draw: num_lights = " + std::to_string(dp->num_lights) + " (at most " +
+                                     std::to_string(SUMA_DRAW_MAX_LIGHTS) + ")");
   const size_t P = (size_t)dp->width * dp->height;
-  if (P > c->draw_zbuf_cap) { /* left cleared by every resolve: only a new one needs a fill */
-    if (c->draw_zbuf) {
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      hipFree(c->draw_zbuf);
-      c->draw_zbuf = nullptr;
-      c->draw_zbuf_cap = 0;
-    }
-    HIP_TRY(c, hipMalloc((void**)&c->draw_zbuf, P * 8));
-    HIP_TRY(c, hipMemsetAsync(c->draw_zbuf, 0xFF, P * 8, c->stream));
-    c->draw_zbuf_cap = P;
-  }
-  if (!c->draw_queue) {
-    HIP_TRY(c, hipMalloc((void**)&c->draw_queue, ((size_t)c->p.max_surfels + 1) * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemsetAsync(c->draw_queue + c->p.max_surfels, 0, sizeof(uint32_t), c->stream));
-  }
+  int r = grow(c, c->draw_zbuf, P, {c->stream});
+  if (r < 0) return r;
+  if (r) HIP_TRY(c, hipMemsetAsync(c->draw_zbuf, 0xFF, P * 8, c->stream)); /* left cleared by every resolve */
+  r = grow(c, c->draw_queue, (size_t)c->p.max_surfels + 1, {});
+  if (r < 0) return r;
+  if (r) HIP_TRY(c, hipMemsetAsync(c->draw_queue + c->p.max_surfels, 0, sizeof(uint32_t), c->stream));
   DrawArgs a;
   a.surfels = c->surfels[c->cur];
   a.ds = c->ds;

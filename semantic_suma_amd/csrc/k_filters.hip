@@ -177,30 +177,21 @@ static uint32_t key_bits(uint32_t P) { /* pixel part 0 .. P above the 32 index b
   return 32 + b;
 }
 
-static hipError_t filters_reserve(suma_ctx* c, uint32_t n) {
-  hipError_t e;
-  if (!c->filt_temp && (e = hipMalloc((void**)&c->filt_temp, c->P * sizeof(float4))) != hipSuccess) return e;
-  if (n <= c->filt_cap) return hipSuccess;
-  const uint32_t cap = n + n / 4 + 1024;
+/* filt_temp, and the sort buffers for n points; a failure (in practice: out of device memory) sets c->err */
+static int filters_reserve(suma_ctx* c, uint32_t n) {
+  if (grow(c, c->filt_temp, c->P, {}) < 0) return SUMA_ERR_HIP;
   /* the buffers may still be read by a sort in flight on either stream: drain before freeing */
-  if (c->filt_sort || c->filt_sort_tmp) {
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
-    if (c->side_stream && (e = hipStreamSynchronize(c->side_stream)) != hipSuccess) return e;
-  }
-  if (c->filt_sort) hipFree(c->filt_sort);
-  if (c->filt_sort_tmp) hipFree(c->filt_sort_tmp);
-  c->filt_sort = nullptr;
-  c->filt_sort_tmp = nullptr;
-  c->filt_cap = 0;
-  if ((e = hipMalloc((void**)&c->filt_sort, (size_t)2 * cap * sizeof(unsigned long long))) != hipSuccess) return e;
+  const int r = grow(c, c->filt_sort, (size_t)2 * n, {c->stream, c->side_stream}, (size_t)2 * (n + n / 4 + 1024));
+  if (r <= 0) return r;
+  const uint32_t cap = (uint32_t)(c->filt_sort.cap / 2); /* the size type of the sort the launches run */
   size_t bytes = 0;
   unsigned long long* k = c->filt_sort;
-  e = rocprim::radix_sort_keys(nullptr, bytes, k, k + cap, cap, 0, key_bits((uint32_t)c->P), c->stream);
-  if (e != hipSuccess) return e;
-  if ((e = hipMalloc(&c->filt_sort_tmp, bytes ? bytes : 16)) != hipSuccess) return e;
-  c->filt_sort_tmp_bytes = bytes;
-  c->filt_cap = cap;
-  return hipSuccess;
+  HIP_TRY(c, rocprim::radix_sort_keys(nullptr, bytes, k, k + cap, cap, 0, key_bits((uint32_t)c->P), c->stream));
+  if (grow(c, c->filt_sort_tmp, bytes ? bytes : 16, {c->stream, c->side_stream}) < 0) {
+    c->filt_sort.reset(); /* the next call retries both */
+    return SUMA_ERR_HIP;
+  }
+  return SUMA_OK;
 }
 
 /* K1 in sum mode + K1b: the averaged vertex map goes to `vertex`, the summed label texels to `raw_semantic` */
@@ -208,15 +199,15 @@ hipError_t launch_k1_average(suma_ctx* c, const float4* d_pts, const float* d_la
                              uint32_t timestamp, float4* vertex, float4* raw_semantic) {
   const uint32_t P = (uint32_t)c->P;
   hipStream_t st = c->ls;
-  hipError_t e = filters_reserve(c, n);
-  if (e != hipSuccess) return e;
+  if (filters_reserve(c, n)) return hipErrorOutOfMemory;
   ProfScope ps(c, "k1_sum_k1b_average", 40.0 * n + 64.0 * P);
+  hipError_t e;
   if ((e = hipMemsetAsync(c->filt_temp, 0, (size_t)P * sizeof(float4), st)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(raw_semantic, 0, (size_t)P * sizeof(float4), st)) != hipSuccess) return e;
   if (n > 0) {
-    unsigned long long *keys = c->filt_sort, *skeys = keys + c->filt_cap;
+    unsigned long long *keys = c->filt_sort, *skeys = keys + c->filt_sort.cap / 2;
     k1s_keys<<<(n + 255) / 256, 256, 0, st>>>(d_pts, n, c->pd, P, keys);
-    size_t bytes = c->filt_sort_tmp_bytes;
+    size_t bytes = c->filt_sort_tmp.cap;
     e = rocprim::radix_sort_keys(c->filt_sort_tmp, bytes, keys, skeys, n, 0, key_bits(P), st);
     if (e != hipSuccess) return e;
     k1s_sum<<<(n + 255) / 256, 256, 0, st>>>(skeys, n, P, d_pts, d_labels, d_probs, c->p.label_offset,
@@ -232,8 +223,8 @@ hipError_t launch_k1_average(suma_ctx* c, const float4* d_pts, const float* d_la
 hipError_t launch_k1c_bilateral(suma_ctx* c, float4* vertex) {
   const int32_t W = c->pd.W, H = c->pd.H;
   hipStream_t st = c->ls;
-  hipError_t e = filters_reserve(c, 0);
-  if (e != hipSuccess) return e;
+  if (filters_reserve(c, 0)) return hipErrorOutOfMemory;
+  hipError_t e;
   ProfScope ps(c, "k1c_bilateral", 48.0 * c->P);
   dim3 grid((W + BF_TX - 1) / BF_TX, (H + BF_TY - 1) / BF_TY);
   k1c_bilateral<<<grid, BF_TX * BF_TY, 0, st>>>(vertex, c->filt_temp, W, H, c->p.bilateral_sigma_space,

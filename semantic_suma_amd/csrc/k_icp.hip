@@ -976,7 +976,7 @@ static IcpArgs make_args(suma_ctx* c, const GnChain& ch) {
 /* state / partial buffers alternate with the launch parity c->gn_launch */
 static GnState* gn_buf(suma_ctx* c, uint32_t parity) { return c->gn + (size_t)(parity & 1u) * SUMA_MAX_HYP; }
 static long long* part_buf(suma_ctx* c, uint32_t launch) {
-  return (long long*)c->gn_partial + (size_t)(launch % 3u) * SUMA_MAX_HYP * ICP_RECORDS * SUMA_ACC_WORDS;
+  return (long long*)c->gn_partial.p + (size_t)(launch % 3u) * SUMA_MAX_HYP * ICP_RECORDS * SUMA_ACC_WORDS;
 }
 
 hipError_t launch_gn_init(suma_ctx* c, const GnChain& ch) {

@@ -138,28 +138,23 @@ __global__ void __launch_bounds__(256)
 }
 
 /* ---- host side ---- */
-int sem_fail(suma_ctx* c, int code, const std::string& msg) {
-  c->err = msg;
-  return code;
-}
-
 int semantic_check(suma_ctx* c, const suma_semantic_params* sp) {
-  if (!sp) return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_params: NULL");
+  if (!sp) return fail(c, SUMA_ERR_INVALID, "suma_semantic_params: NULL");
   if (sp->n_classes == 0 || sp->n_classes > SUMA_SEM_MAX_CLASSES)
-    return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_params: n_classes = " + std::to_string(sp->n_classes) +
-                                             " (must be 1 .. " + std::to_string(SUMA_SEM_MAX_CLASSES) + ")");
+    return fail(c, SUMA_ERR_INVALID, "suma_semantic_params: n_classes = " + std::to_string(sp->n_classes) +
+                                     " (must be 1 .. " + std::to_string(SUMA_SEM_MAX_CLASSES) + ")");
   if (sp->width == 0 || sp->height == 0 || sp->width > (1u << 24) || sp->height > (1u << 24) ||
       (uint64_t)sp->width * sp->height > (uint64_t)INT32_MAX)
-    return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_params: width x height = " + std::to_string(sp->width) + " x " +
-                                             std::to_string(sp->height) + " is empty or overflows the int32 pixel index");
+    return fail(c, SUMA_ERR_INVALID, "suma_semantic_params: width x height = " + std::to_string(sp->width) + " x " +
+                                     std::to_string(sp->height) + " is empty or overflows the int32 pixel index");
   for (int ch = 0; ch < SUMA_SEM_CHANNELS; ++ch) {
     if (!(sp->stds[ch] != 0.0f) || !std::isfinite(sp->stds[ch]) || !std::isfinite(sp->means[ch]))
-      return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_params: channel " + std::to_string(ch) +
-                                               " needs a finite mean and a finite, non-zero std");
+      return fail(c, SUMA_ERR_INVALID, "suma_semantic_params: channel " + std::to_string(ch) +
+                                       " needs a finite mean and a finite, non-zero std");
   }
   const double fov = (std::fabs((double)sp->fov_up) + std::fabs((double)sp->fov_down)) * M_PI / 180.0;
   if (!(fov > 0.0) || !std::isfinite(fov) || !((float)fov > 0.0f))
-    return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_params: |fov_up| + |fov_down| must be finite and > 0");
+    return fail(c, SUMA_ERR_INVALID, "suma_semantic_params: |fov_up| + |fov_down| must be finite and > 0");
   return SUMA_OK;
 }
 
@@ -198,20 +193,13 @@ extern "C" int suma_semantic_project(suma_ctx* c, const suma_semantic_params* sp
   if (!c) return SUMA_ERR_INVALID;
   int r = semantic_check(c, sp);
   if (r) return r;
-  if (!d_input || (n > 0 && !d_points)) return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_project: NULL buffer");
-  if (n == 0xffffffffu) return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_project: too many points");
+  if (!d_input || (n > 0 && !d_points)) return fail(c, SUMA_ERR_INVALID, "suma_semantic_project: NULL buffer");
+  if (n == 0xffffffffu) return fail(c, SUMA_ERR_INVALID, "suma_semantic_project: too many points");
   const SemProj q = sem_proj(sp);
-  if (q.P > c->sem_zbuf_cap) { /* the z-buffer is left cleared by every resolve: only a new one needs a fill */
-    if (c->sem_zbuf) {
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      hipFree(c->sem_zbuf);
-      c->sem_zbuf = nullptr;
-      c->sem_zbuf_cap = 0;
-    }
-    HIP_TRY(c, hipMalloc((void**)&c->sem_zbuf, (size_t)q.P * 8));
-    HIP_TRY(c, hipMemsetAsync(c->sem_zbuf, 0xFF, (size_t)q.P * 8, c->stream));
-    c->sem_zbuf_cap = q.P;
-  }
+  r = grow(c, c->sem_zbuf, q.P, {c->stream});
+  if (r < 0) return r;
+  /* the z-buffer is left cleared by every resolve: only a new one needs a fill */
+  if (r) HIP_TRY(c, hipMemsetAsync(c->sem_zbuf, 0xFF, (size_t)q.P * 8, c->stream));
   ProfScope ps(c, "semantic_project", 20.0 * n + 32.0 * q.P);
   if (n > 0)
     ks_scatter<<<(n + 255) / 256, 256, 0, c->stream>>>((const float4*)d_points, n, q, c->sem_zbuf, d_pixel);
@@ -227,8 +215,21 @@ extern "C" int suma_semantic_unproject(suma_ctx* c, const suma_semantic_params* 
   int r = semantic_check(c, sp);
   if (r) return r;
   if (n > 0 && (!d_scores || !d_pixel || !d_labels || !d_probs))
-    return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_unproject: NULL buffer");
+    return fail(c, SUMA_ERR_INVALID, "suma_semantic_unproject: NULL buffer");
   HIP_TRY(c, launch_semantic_unproject(c, sp, d_scores, scores_are_logits, d_pixel, n, d_labels, d_probs));
+  return SUMA_OK;
+}
+
+int semantic_scan_input(suma_pipeline* s, uint32_t n, void* producer_event, hipStream_t* st) {
+  suma_ctx* c = s->c;
+  if (s->phase != 0)
+    return fail(c, SUMA_ERR_INVALID, "suma_pipeline_begin_scan: the previous scan has not been closed with suma_pipeline_update_map");
+  *st = pipeline_input_stream(s);
+  /* the previous scan's preprocessing may still read the old labels (input stream), its frame readers follow */
+  const size_t cap = (size_t)n + n / 4 + 1024;
+  if (grow(c, c->sem_labels, n, {*st, c->stream}, cap) < 0 || grow(c, c->sem_probs, n, {*st, c->stream}, cap) < 0)
+    return SUMA_ERR_HIP;
+  if (producer_event) HIP_TRY(c, hipStreamWaitEvent(*st, (hipEvent_t)producer_event, 0));
   return SUMA_OK;
 }
 
@@ -242,24 +243,10 @@ extern "C" int suma_pipeline_begin_scan_scores(suma_pipeline* s, const suma_sema
   int r = semantic_check(c, sp);
   if (r) return r;
   if (n > 0 && (!d_points || !d_scores || !d_pixel))
-    return sem_fail(c, SUMA_ERR_INVALID, "suma_pipeline_begin_scan_scores: NULL buffer");
-  if (s->phase != 0)
-    return sem_fail(c, SUMA_ERR_INVALID, "suma_pipeline_begin_scan: the previous scan has not been closed with suma_pipeline_update_map");
-  const hipStream_t st = pipeline_input_stream(s);
-  if (n > c->sem_cap) {
-    /* the previous scan's preprocessing may still read the old labels (side stream), its frame readers follow */
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->sem_labels) hipFree(c->sem_labels);
-    if (c->sem_probs) hipFree(c->sem_probs);
-    c->sem_labels = c->sem_probs = nullptr;
-    c->sem_cap = 0;
-    const uint32_t cap = n + n / 4 + 1024;
-    HIP_TRY(c, hipMalloc((void**)&c->sem_labels, (size_t)cap * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void**)&c->sem_probs, (size_t)cap * sizeof(float)));
-    c->sem_cap = cap;
-  }
-  if (producer_event) HIP_TRY(c, hipStreamWaitEvent(st, (hipEvent_t)producer_event, 0));
+    return fail(c, SUMA_ERR_INVALID, "suma_pipeline_begin_scan_scores: NULL buffer");
+  hipStream_t st;
+  r = semantic_scan_input(s, n, producer_event, &st);
+  if (r) return r;
   c->ls = st;
   hipError_t e = launch_semantic_unproject(c, sp, d_scores, scores_are_logits, d_pixel, n, c->sem_labels, c->sem_probs);
   c->ls = c->stream;
@@ -272,9 +259,7 @@ extern "C" int suma_pipeline_process_scan_scores(suma_pipeline* s, const suma_se
                                                  const suma_float4* d_points, const float* d_scores,
                                                  int scores_are_logits, const int32_t* d_pixel, uint32_t n,
                                                  void* producer_event, int32_t fixed_iterations) {
-  int r = suma_pipeline_begin_scan_scores(s, sp, d_points, d_scores, scores_are_logits, d_pixel, n, producer_event);
-  if (r == SUMA_OK) r = pipeline_update_pose_impl(s, fixed_iterations);
-  if (r == SUMA_OK) r = pipeline_update_map_impl(s);
-  if (r != SUMA_OK && s) s->phase = 0; /* a failed scan does not wedge the phase check */
-  return r;
+  return pipeline_finish_scan(
+      s, suma_pipeline_begin_scan_scores(s, sp, d_points, d_scores, scores_are_logits, d_pixel, n, producer_event),
+      fixed_iterations, false);
 }

@@ -269,34 +269,26 @@ __global__ void __launch_bounds__(256)
 
 /* ---- host side ---- */
 static int knn_check(suma_ctx* c, const suma_semantic_knn* kp) {
-  if (!kp) return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_knn: NULL");
+  if (!kp) return fail(c, SUMA_ERR_INVALID, "suma_semantic_knn: NULL");
   if (kp->search < 1 || kp->search > KNN_MAX_SEARCH || kp->search % 2 == 0)
-    return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_knn: search = " + std::to_string(kp->search) +
-                                             " (must be odd, 1 .. " + std::to_string(KNN_MAX_SEARCH) + ")");
+    return fail(c, SUMA_ERR_INVALID, "suma_semantic_knn: search = " + std::to_string(kp->search) +
+                                     " (must be odd, 1 .. " + std::to_string(KNN_MAX_SEARCH) + ")");
   if (kp->k < 1 || kp->k > kp->search * kp->search)
-    return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_knn: k = " + std::to_string(kp->k) + " (must be 1 .. search^2 = " +
-                                             std::to_string(kp->search * kp->search) + ")");
+    return fail(c, SUMA_ERR_INVALID, "suma_semantic_knn: k = " + std::to_string(kp->k) + " (must be 1 .. search^2 = " +
+                                     std::to_string(kp->search * kp->search) + ")");
   if (!(kp->sigma > 0.0f) || !std::isfinite(kp->sigma))
-    return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_knn: sigma must be finite and > 0");
-  if (!std::isfinite(kp->cutoff)) return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_knn: cutoff must be finite");
+    return fail(c, SUMA_ERR_INVALID, "suma_semantic_knn: sigma must be finite and > 0");
+  if (!std::isfinite(kp->cutoff)) return fail(c, SUMA_ERR_INVALID, "suma_semantic_knn: cutoff must be finite");
   return SUMA_OK;
 }
 
-/* the record image of one stream's passes: cp (P x 8 bytes) then range (P x 4 bytes) in one block */
-static int knn_reserve(suma_ctx* c, SemKnnScratch* sc, uint32_t P, hipStream_t st) {
-  if (P <= sc->cap) return SUMA_OK;
-  if (sc->buf) {
-    HIP_TRY(c, hipStreamSynchronize(st)); /* every earlier pass that used the block ran on st */
-    hipFree(sc->buf);
-    sc->buf = nullptr;
-    sc->cap = 0;
-  }
-  HIP_TRY(c, hipMalloc(&sc->buf, (size_t)P * 12));
-  sc->cap = P;
-  return SUMA_OK;
+/* the record image of one stream's passes: cp (P x 8 bytes) then range (P x 4 bytes) in one block; every earlier pass
+ * that used the block ran on st */
+static int knn_reserve(suma_ctx* c, DevBuf<char>& sc, uint32_t P, hipStream_t st) {
+  return grow(c, sc, (size_t)P * 12, {st}) < 0 ? SUMA_ERR_HIP : SUMA_OK;
 }
 
-static hipError_t launch_semantic_unproject_knn(suma_ctx* c, hipStream_t st, const SemKnnScratch* sc,
+static hipError_t launch_semantic_unproject_knn(suma_ctx* c, hipStream_t st, char* sc,
                                                 const suma_semantic_params* sp, const suma_semantic_knn* kp,
                                                 const suma_float4* d_points, const float* d_scores, int logits,
                                                 const int32_t* d_pixel, const int32_t* d_proj_idx, uint32_t n,
@@ -321,7 +313,7 @@ static hipError_t launch_semantic_unproject_knn(suma_ctx* c, hipStream_t st, con
   for (uint32_t t = 0; t < KNN_MAX_SEARCH * KNN_MAX_SEARCH; ++t) a.w[t] = t < S * S ? (float)(1.0 - e[t] / sum) : 0.0f;
   for (uint32_t j = 0; j < SUMA_SEM_MAX_CLASSES; ++j) a.label[j] = j < C ? (float)sp->label_map[j] : 0.0f;
   if (n == 0) return hipGetLastError();
-  uint2* cp = (uint2*)sc->buf;
+  uint2* cp = (uint2*)sc;
   float* range = (float*)(cp + P);
   {
     ProfScope ps(c, "semantic_knn_pixels", (16.0 + 4.0 * C) * P + 16.0 * n);
@@ -354,7 +346,7 @@ static int knn_args_check(suma_ctx* c, const suma_semantic_params* sp, const sum
   r = knn_check(c, kp);
   if (r) return r;
   if (n > 0 && (!d_points || !d_scores || !d_pixel || !d_proj_idx))
-    return sem_fail(c, SUMA_ERR_INVALID, std::string(who) + ": NULL buffer");
+    return fail(c, SUMA_ERR_INVALID, std::string(who) + ": NULL buffer");
   return SUMA_OK;
 }
 
@@ -367,12 +359,12 @@ extern "C" int suma_semantic_unproject_knn(suma_ctx* c, const suma_semantic_para
   if (!c) return SUMA_ERR_INVALID;
   int r = knn_args_check(c, sp, knn, "suma_semantic_unproject_knn", d_points, d_scores, d_pixel, d_proj_idx, n);
   if (r) return r;
-  if (n > 0 && (!d_labels || !d_probs)) return sem_fail(c, SUMA_ERR_INVALID, "suma_semantic_unproject_knn: NULL buffer");
+  if (n > 0 && (!d_labels || !d_probs)) return fail(c, SUMA_ERR_INVALID, "suma_semantic_unproject_knn: NULL buffer");
   if (n > 0) {
-    r = knn_reserve(c, &c->sem_knn[0], sp->width * sp->height, c->stream);
+    r = knn_reserve(c, c->sem_knn[0], sp->width * sp->height, c->stream);
     if (r) return r;
   }
-  HIP_TRY(c, launch_semantic_unproject_knn(c, c->stream, &c->sem_knn[0], sp, knn, d_points, d_scores, scores_are_logits,
+  HIP_TRY(c, launch_semantic_unproject_knn(c, c->stream, c->sem_knn[0], sp, knn, d_points, d_scores, scores_are_logits,
                                            d_pixel, d_proj_idx, n, d_labels, d_probs));
   return SUMA_OK;
 }
@@ -386,27 +378,14 @@ extern "C" int suma_pipeline_begin_scan_scores_knn(suma_pipeline* s, const suma_
   suma_ctx* c = s->c;
   int r = knn_args_check(c, sp, knn, "suma_pipeline_begin_scan_scores_knn", d_points, d_scores, d_pixel, d_proj_idx, n);
   if (r) return r;
-  if (s->phase != 0)
-    return sem_fail(c, SUMA_ERR_INVALID, "suma_pipeline_begin_scan: the previous scan has not been closed with suma_pipeline_update_map");
-  const hipStream_t st = pipeline_input_stream(s);
-  if (n > c->sem_cap) { /* the growth rule of suma_pipeline_begin_scan_scores: the labels are shared with it */
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->sem_labels) hipFree(c->sem_labels);
-    if (c->sem_probs) hipFree(c->sem_probs);
-    c->sem_labels = c->sem_probs = nullptr;
-    c->sem_cap = 0;
-    const uint32_t cap = n + n / 4 + 1024;
-    HIP_TRY(c, hipMalloc((void**)&c->sem_labels, (size_t)cap * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void**)&c->sem_probs, (size_t)cap * sizeof(float)));
-    c->sem_cap = cap;
-  }
+  hipStream_t st;
+  r = semantic_scan_input(s, n, producer_event, &st);
+  if (r) return r;
   if (n > 0) {
-    r = knn_reserve(c, &c->sem_knn[1], sp->width * sp->height, st);
+    r = knn_reserve(c, c->sem_knn[1], sp->width * sp->height, st);
     if (r) return r;
   }
-  if (producer_event) HIP_TRY(c, hipStreamWaitEvent(st, (hipEvent_t)producer_event, 0));
-  HIP_TRY(c, launch_semantic_unproject_knn(c, st, &c->sem_knn[1], sp, knn, d_points, d_scores, scores_are_logits,
+  HIP_TRY(c, launch_semantic_unproject_knn(c, st, c->sem_knn[1], sp, knn, d_points, d_scores, scores_are_logits,
                                            d_pixel, d_proj_idx, n, c->sem_labels, c->sem_probs));
   /* K1-K3 follow on the same stream, exactly as suma_pipeline_begin_scan_device runs them */
   return pipeline_begin_scan_impl(s, d_points, c->sem_labels, c->sem_probs, n, nullptr);
@@ -419,8 +398,5 @@ extern "C" int suma_pipeline_process_scan_scores_knn(suma_pipeline* s, const sum
                                                      void* producer_event, int32_t fixed_iterations) {
   int r = suma_pipeline_begin_scan_scores_knn(s, sp, knn, d_points, d_scores, scores_are_logits, d_pixel, d_proj_idx, n,
                                               producer_event);
-  if (r == SUMA_OK) r = pipeline_update_pose_impl(s, fixed_iterations);
-  if (r == SUMA_OK) r = pipeline_update_map_impl(s);
-  if (r != SUMA_OK && s) s->phase = 0; /* a failed scan does not wedge the phase check */
-  return r;
+  return pipeline_finish_scan(s, r, fixed_iterations, false);
 }

@@ -65,7 +65,7 @@ int ensure_side_stream(suma_ctx* c) {
   g_side_ctxs.fetch_add(1); /* counted with the stream: side_stream_released() decrements whenever the stream exists */
   HIP_TRY(c, hipEventCreateWithFlags(&c->pre_event, hipEventDisableTiming));
   HIP_TRY(c, hipEventCreateWithFlags(&c->order_event, hipEventDisableTiming));
-  HIP_TRY(c, hipMalloc((void**)&c->zbuf_k1, c->P * 8));
+  HIP_TRY(c, c->zbuf_k1.alloc(c->P));
   HIP_TRY(c, hipMemsetAsync(c->zbuf_k1, 0xFF, c->P * 8, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return SUMA_OK;

@@ -101,7 +101,7 @@ static inline void accessed(suma_ctx* c, const suma_frame* f) {
 /* the host has just observed the completion of everything the ctx stream held */
 static inline void host_synced(suma_ctx* c) { c->done_seq = c->enq_seq; }
 
-static int fail(suma_ctx* c, int code, const char* msg) {
+int fail(suma_ctx* c, int code, const std::string& msg) {
   c->err = msg;
   return code;
 }
@@ -197,15 +197,14 @@ static int frame_create_raw(suma_ctx* c, uint32_t w, uint32_t h, suma_frame** ou
   f->width = w;
   f->height = h;
   size_t P = (size_t)w * h;
-  float4* base = nullptr;
-  hipError_t e = hipMalloc((void**)&base, 3 * P * sizeof(float4));
+  hipError_t e = f->block.alloc(3 * P);
   if (e != hipSuccess) {
     delete f;
     c->err = std::string("hipMalloc(frame): ") + hipGetErrorString(e);
     return SUMA_ERR_HIP;
   }
-  hipMemsetAsync(base, 0, 3 * P * sizeof(float4), c->stream);
-  for (int m = 0; m < 3; ++m) f->map[m] = base + m * P;
+  hipMemsetAsync(f->block, 0, 3 * P * sizeof(float4), c->stream);
+  for (int m = 0; m < 3; ++m) f->map[m] = f->block + m * P;
   /* the memset is ctx-stream work on this frame: a side-stream preprocessing into it must be ordered behind it when
    * the ctx stream has a backlog (round-4 advisor: last_access stayed 0, so the memset could land on fresh maps) */
   accessed(c, f);
@@ -296,32 +295,6 @@ extern "C" int suma_ctx_create(const suma_params* params, int hip_device, suma_c
   }
   c->p = *params;
   c->device = hip_device;
-  memset(&c->het, 0, sizeof(c->het));
-  c->icp_iteration0 = 0;
-  c->profiling = 0;
-  c->prof_tick = 0;
-  c->epoch = 0;
-  c->scan_cap = 0;
-  c->scan_points = nullptr;
-  c->scan_labels = c->scan_probs = nullptr;
-  c->icp_current = c->icp_model = nullptr;
-  c->obj_set = false;
-  c->side_stream = nullptr;
-  c->sync_flags = nullptr;
-  c->zbuf_k1 = nullptr;
-  c->filt_temp = nullptr;
-  c->filt_sort = nullptr;
-  c->filt_sort_tmp = nullptr;
-  c->filt_sort_tmp_bytes = 0;
-  c->sem_zbuf = nullptr;
-  c->sem_zbuf_cap = 0;
-  c->sem_labels = c->sem_probs = nullptr;
-  c->sem_cap = 0;
-  c->sem_knn[0] = c->sem_knn[1] = SemKnnScratch{nullptr, 0};
-  c->draw_zbuf = nullptr;
-  c->draw_zbuf_cap = 0;
-  c->draw_queue = nullptr;
-  c->filt_cap = 0;
   derive(c);
   c->P = (size_t)params->data_width * params->data_height;
   c->Pm = (size_t)params->model_width * params->model_height;
@@ -330,70 +303,59 @@ extern "C" int suma_ctx_create(const suma_params* params, int hip_device, suma_c
     CK(hipSetDevice(hip_device));
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     c->ls = c->stream;
-    CK(hipMalloc((void**)&c->sync_flags, 16 * sizeof(uint32_t)));
+    CK(c->sync_flags.alloc(16));
     CK(hipMemsetAsync(c->sync_flags, 0, 16 * sizeof(uint32_t), c->stream));
-    c->pre_seq = 0;
-    c->gate_pending = 0;
     const size_t P = c->P, Pm = c->Pm;
-    CK(hipMalloc((void**)&c->zbuf_data, P * 8));
+    CK(c->zbuf_data.alloc(P));
     CK(hipMemsetAsync(c->zbuf_data, 0xFF, P * 8, c->stream));
-    CK(hipMalloc((void**)&c->eroded, P * sizeof(float4)));
-    CK(hipMalloc((void**)&c->radius_conf, P * sizeof(float4)));
+    CK(c->eroded.alloc(P));
+    CK(c->radius_conf.alloc(P));
     CK(hipMemsetAsync(c->radius_conf, 0, P * sizeof(float4), c->stream));
-    CK(hipMalloc((void**)&c->pixrec, P * 4 * sizeof(float4)));
-    CK(hipMalloc((void**)&c->integrated, P));
+    CK(c->pixrec.alloc(P * 4));
+    CK(c->integrated.alloc(P));
     CK(hipMemsetAsync(c->integrated, 0, P, c->stream));
-    CK(hipMalloc((void**)&c->extract_flags, (size_t)params->max_surfels));
-    c->flagged.valid = false;
-    CK(hipMalloc((void**)&c->index_map, P * 4));
+    CK(c->extract_flags.alloc(params->max_surfels));
+    CK(c->index_map.alloc(P));
     CK(hipMemsetAsync(c->index_map, 0, P * 4, c->stream));
-    CK(hipMalloc((void**)&c->zbuf_a, Pm * 8));
-    CK(hipMalloc((void**)&c->zbuf_b, Pm * 8));
+    CK(c->zbuf_a.alloc(Pm));
+    CK(c->zbuf_b.alloc(Pm));
     CK(hipMemsetAsync(c->zbuf_a, 0xFF, Pm * 8, c->stream));
     CK(hipMemsetAsync(c->zbuf_b, 0xFF, Pm * 8, c->stream));
-    for (int b = 0; b < 2; ++b) CK(hipMalloc((void**)&c->surfels[b], (size_t)params->max_surfels * sizeof(suma_surfel)));
-    CK(hipMalloc((void**)&c->poses, (size_t)params->max_poses * 16 * sizeof(float)));
-    CK(hipMalloc((void**)&c->poses_inv, (size_t)params->max_poses * 16 * sizeof(float)));
+    for (int b = 0; b < 2; ++b) CK(c->surfels[b].alloc(params->max_surfels));
+    CK(c->poses.alloc((size_t)params->max_poses * 16));
+    CK(c->poses_inv.alloc((size_t)params->max_poses * 16));
     c->n_tiles_cap = (uint32_t)(((size_t)params->max_surfels + 2 * P) / SUMA_TILE + 2);
-    CK(hipMalloc((void**)&c->tile_status, (size_t)c->n_tiles_cap * 8));
+    CK(c->tile_status.alloc(c->n_tiles_cap));
     CK(hipMemsetAsync(c->tile_status, 0, (size_t)c->n_tiles_cap * 8, c->stream));
     c->group_words = c->n_tiles_cap / 64 + 2;
-    CK(hipMalloc((void**)&c->tile_group, (size_t)2 * c->group_words * 8));
+    CK(c->tile_group.alloc((size_t)2 * c->group_words));
     CK(hipMemsetAsync(c->tile_group, 0, (size_t)2 * c->group_words * 8, c->stream));
-    CK(hipMalloc((void**)&c->ds, sizeof(DevState)));
-    CK(hipHostMalloc((void**)&c->h_ds, sizeof(DevState), hipHostMallocDefault));
+    CK(c->ds.alloc(1));
+    CK(c->h_ds.alloc(1));
     memset(c->h_ds, 0, sizeof(DevState));
     /* ICP */
     c->icp_blocks = 256;
-    CK(hipMalloc((void**)&c->gn, 2 * SUMA_MAX_HYP * sizeof(GnState)));
+    CK(c->gn.alloc(2 * SUMA_MAX_HYP));
     CK(hipMemsetAsync(c->gn, 0, 2 * SUMA_MAX_HYP * sizeof(GnState), c->stream));
-    CK(hipMalloc((void**)&c->gn_partial, (size_t)2 * SUMA_MAX_HYP * c->icp_blocks * SUMA_ACC_WORDS * sizeof(int64_t)));
-    c->gn_part_launch = 0;
-    c->gn_part_dirty[0] = c->gn_part_dirty[1] = c->gn_part_dirty[2] = 0;
+    CK(c->gn_partial.alloc((size_t)2 * SUMA_MAX_HYP * c->icp_blocks * SUMA_ACC_WORDS));
     /* the rotating accumulator records of the Gauss-Newton chain start out zero (k_icp.hip, IterArgs) */
     CK(hipMemset(c->gn_partial, 0, (size_t)2 * SUMA_MAX_HYP * c->icp_blocks * SUMA_ACC_WORDS * sizeof(int64_t)));
-    c->gn_launch = 0;
     c->gn_history_cap = 1025;
-    CK(hipMalloc((void**)&c->gn_history, (size_t)c->gn_history_cap * 16 * sizeof(double)));
-    CK(hipMalloc((void**)&c->gn_T0s, (size_t)SUMA_MAX_HYP * 16 * sizeof(double)));
-    CK(hipHostMalloc((void**)&c->h_gn, SUMA_MAX_HYP * sizeof(GnState), hipHostMallocDefault));
-    CK(hipMalloc((void**)&c->pose_block, 32 * sizeof(float)));
-    CK(hipHostMalloc((void**)&c->h_rec, 2 * sizeof(HostResult), hipHostMallocDefault));
+    CK(c->gn_history.alloc((size_t)c->gn_history_cap * 16));
+    CK(c->gn_T0s.alloc((size_t)SUMA_MAX_HYP * 16));
+    CK(c->h_gn.alloc(SUMA_MAX_HYP));
+    CK(c->pose_block.alloc(32));
+    CK(c->h_rec.alloc(2));
     memset(c->h_rec, 0, 2 * sizeof(HostResult));
-    c->rec_seq = 0;
-    c->k8_fused_frame = nullptr;
-    c->cache_slots = nullptr;
     /* submap cache arena */
     /* default 16 x max_surfels (4.3 GB at the reference's 4.19 M): every tile of a KITTI-length
      * trajectory stays parked in HBM; re-extracted tiles take fresh arena space */
     uint64_t cache = params->cache_surfels ? params->cache_surfels : 16ull * params->max_surfels;
     if (cache > 0xffffffffull) cache = 0xffffffffull;
     c->cache_cap = (uint32_t)cache;
-    CK(hipMalloc((void**)&c->cache_arena, (size_t)c->cache_cap * sizeof(suma_surfel)));
-    c->cache_compactions = 0;
-    c->cache_bound = 0;
+    CK(c->cache_arena.alloc(c->cache_cap));
     c->cache_slots_cap = 65536;
-    CK(hipMalloc((void**)&c->cache_slots, (size_t)c->cache_slots_cap * sizeof(CacheSlot)));
+    CK(c->cache_slots.alloc(c->cache_slots_cap));
     int r = frame_create_raw(c, params->model_width, params->model_height, &c->old_frame);
     if (r) return r;
     r = frame_create_raw(c, params->model_width, params->model_height, &c->new_frame);
@@ -435,27 +397,16 @@ extern "C" void suma_ctx_destroy(suma_ctx* c) {
     if (c->pre_event) hipEventDestroy(c->pre_event);
     if (c->order_event) hipEventDestroy(c->order_event);
   }
-  if (c->h_rec) hipHostFree(c->h_rec);
   for (auto& ev : c->prof_events) {
     hipEventDestroy(ev.a);
     hipEventDestroy(ev.b);
   }
   for (auto& e : c->prof_pool) hipEventDestroy(e);
-  void* dev[] = {c->extract_flags, c->pose_block, c->pixrec, c->zbuf_data, c->eroded,      c->radius_conf, c->integrated,  c->index_map, c->zbuf_a,
-                 c->zbuf_b,    c->surfels[0],  c->surfels[1],  c->poses,       c->poses_inv, c->tile_status, c->tile_group,
-                 c->ds,        c->gn,          c->gn_partial,  c->gn_history,  c->gn_T0s,    c->cache_arena,
-                 c->cache_slots, c->scan_points, c->scan_labels, c->scan_probs, c->sync_flags, c->zbuf_k1,
-                 c->filt_temp, c->filt_sort, c->filt_sort_tmp, c->sem_zbuf, c->sem_labels, c->sem_probs,
-                 c->sem_knn[0].buf, c->sem_knn[1].buf, c->draw_zbuf, c->draw_queue};
-  for (void* p : dev)
-    if (p) hipFree(p);
-  if (c->h_ds) hipHostFree(c->h_ds);
-  if (c->h_gn) hipHostFree(c->h_gn);
   suma_frame_destroy(c->old_frame);
   suma_frame_destroy(c->new_frame);
   suma_frame_destroy(c->composed_frame);
   if (c->stream) hipStreamDestroy(c->stream);
-  delete c;
+  delete c; /* the device and pinned blocks go with their members, c->device still current */
 }
 
 extern "C" int suma_set_params(suma_ctx* c, const suma_params* p) {
@@ -501,7 +452,6 @@ extern "C" void suma_frame_destroy(suma_frame* f) {
     if (c->gate_frame == f) c->gate_frame = nullptr;
     if (c->rendered.out == f) c->rendered.valid = false;
   }
-  if (f->map[0]) hipFree(f->map[0]);
   delete f;
 }
 extern "C" int suma_frame_copy(suma_ctx* c, suma_frame* dst, const suma_frame* src) {
@@ -550,6 +500,7 @@ extern "C" int suma_frame_swap(suma_ctx* c, suma_frame* a, suma_frame* b) {
   /* the hazard bookkeeping follows the BUFFERS: a pending side-stream hand-off into either frame is flushed first, and
    * both handles inherit the later of the two ctx-stream accesses (round-4 advisor) */
   if (c->gate_pending && (c->gate_frame == a || c->gate_frame == b)) CK(flush_gate(c));
+  std::swap(a->block, b->block);
   for (int m = 0; m < 3; ++m) std::swap(a->map[m], b->map[m]);
   const uint64_t la = a->last_access > b->last_access ? a->last_access : b->last_access;
   a->last_access = b->last_access = la;
@@ -609,18 +560,10 @@ extern "C" int suma_preprocess_device(suma_ctx* c, const suma_float4* d_points, 
 }
 
 static int stage_scan(suma_ctx* c, const suma_float4* points, const float* labels, const float* probs, uint32_t n) {
-  if (n > c->scan_cap) {
-    if (c->scan_points) hipFree(c->scan_points);
-    if (c->scan_labels) hipFree(c->scan_labels);
-    if (c->scan_probs) hipFree(c->scan_probs);
-    c->scan_points = nullptr;
-    c->scan_labels = c->scan_probs = nullptr;
-    uint32_t cap = n + n / 4 + 1024;
-    CK(hipMalloc((void**)&c->scan_points, (size_t)cap * sizeof(float4)));
-    CK(hipMalloc((void**)&c->scan_labels, (size_t)cap * sizeof(float)));
-    CK(hipMalloc((void**)&c->scan_probs, (size_t)cap * sizeof(float)));
-    c->scan_cap = cap;
-  }
+  const size_t cap = (size_t)n + n / 4 + 1024;
+  if (grow(c, c->scan_points, n, {}, cap) < 0 || grow(c, c->scan_labels, n, {}, cap) < 0 ||
+      grow(c, c->scan_probs, n, {}, cap) < 0)
+    return SUMA_ERR_HIP;
   if (n == 0) return SUMA_OK;
   CK(hipMemcpyAsync(c->scan_points, points, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->ls));
   if (labels) CK(hipMemcpyAsync(c->scan_labels, labels, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->ls));
@@ -641,7 +584,7 @@ extern "C" int suma_preprocess(suma_ctx* c, const suma_float4* points, const flo
   if (plain) {
     int r = stage_scan(c, points, labels, probs, n);
     if (r) return r;
-    return suma_preprocess_device(c, (const suma_float4*)c->scan_points, labels ? c->scan_labels : nullptr,
+    return suma_preprocess_device(c, (const suma_float4*)c->scan_points.p, labels ? c->scan_labels : nullptr,
                                   probs ? c->scan_probs : nullptr, n, timestamp, out);
   }
   if (c->gate_pending) CK(flush_gate(c)); /* one hand-off at a time */
@@ -1005,8 +948,8 @@ static int cache_compact_if_needed(suma_ctx* c, uint32_t pending_slot) {
     c->cache_nothing_stale = true;
     return SUMA_OK;
   }
-  suma_surfel* fresh = nullptr;
-  CK(hipMalloc((void**)&fresh, (size_t)c->cache_cap * sizeof(suma_surfel)));
+  DevBuf<suma_surfel> fresh;
+  CK(fresh.alloc(c->cache_cap));
   uint32_t off = 0;
   hipError_t e = hipSuccess;
   for (auto& q : slots) {
@@ -1019,12 +962,8 @@ static int cache_compact_if_needed(suma_ctx* c, uint32_t pending_slot) {
   if (ns && e == hipSuccess) e = hipMemcpyAsync(c->cache_slots, slots.data(), ns * sizeof(CacheSlot), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(&c->ds->cache_used, &off, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    hipFree(fresh); /* the old arena and its table stay in place */
-    CK(e);
-  }
-  hipFree(c->cache_arena);
-  c->cache_arena = fresh;
+  CK(e); /* on failure the old arena and its table stay in place */
+  c->cache_arena = std::move(fresh);
   c->h_ds->cache_used = off;
   c->cache_bound = off;
   c->cache_compactions += 1;
@@ -1303,12 +1242,14 @@ extern "C" int suma_map_update_poses(suma_ctx* c, const float* poses16, uint32_t
   if (!c || (!poses16 && n)) return SUMA_ERR_INVALID;
   if (n > c->p.max_poses) n = c->p.max_poses;
   if (n == 0) return SUMA_OK;
-  float* d_tmp = nullptr;
-  CK(hipMalloc((void**)&d_tmp, (size_t)n * 16 * sizeof(float)));
-  hipError_t e = hipMemcpyAsync(d_tmp, poses16, (size_t)n * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_set_poses(c, d_tmp, 0, n);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(d_tmp);
+  hipError_t e;
+  {
+    DevBuf<float> d_tmp;
+    CK(d_tmp.alloc((size_t)n * 16));
+    e = hipMemcpyAsync(d_tmp, poses16, (size_t)n * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_set_poses(c, d_tmp, 0, n);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
   c->map_version++;
   CK(e);
   return SUMA_OK;
@@ -1683,7 +1624,6 @@ extern "C" int suma_pipeline_create(const suma_params* params, int hip_device, s
     suma_ctx_destroy(c);
     return SUMA_ERR_NOMEM;
   }
-  memset(s, 0, sizeof(*s));
   s->c = c;
   suma_frame** fr[4] = {&s->last_frame, &s->current_frame, &s->current_model, &s->last_model};
   for (int k = 0; k < 4; ++k) {
@@ -1696,7 +1636,7 @@ extern "C" int suma_pipeline_create(const suma_params* params, int hip_device, s
       return r;
     }
   }
-  if (hipHostMalloc((void**)&s->h_res, 3 * sizeof(HostResult), hipHostMallocDefault) != hipSuccess) {
+  if (s->h_res.alloc(3) != hipSuccess) {
     g_create_error = "hipHostMalloc failed";
     suma_pipeline_destroy(s);
     return SUMA_ERR_HIP;
@@ -1709,16 +1649,12 @@ extern "C" int suma_pipeline_create(const suma_params* params, int hip_device, s
     suma_pipeline_destroy(s);
     return SUMA_ERR_HIP;
   }
-  s->res_seq = 0;
-  s->stats_pending = false;
-  s->stats_slot = 0;
   mat4_eye(s->current_pose);
   mat4_eye(s->last_pose);
   mat4_eye(s->pose_old);
   mat4_eye(s->pose_new);
   mat4_eye(s->last_increment);
   mat4_eye(s->last_pose_old);
-  s->phase = 0;
   float p_unstable = 0.1f; /* SurfelMapping.cpp:108-109 */
   s->log_unstable = (float)log((double)(p_unstable / (1.0f - p_unstable)));
   *out = s;
@@ -1732,7 +1668,6 @@ extern "C" void suma_pipeline_destroy(suma_pipeline* s) {
   suma_frame_destroy(s->current_frame);
   suma_frame_destroy(s->current_model);
   suma_frame_destroy(s->last_model);
-  if (s->h_res) hipHostFree(s->h_res);
   suma_ctx_destroy(s->c);
   delete s;
 }
@@ -2008,9 +1943,12 @@ hipStream_t pipeline_input_stream(suma_pipeline* s) { return s->c->side_stream ?
 
 int pipeline_process_scan_impl(suma_pipeline* s, const suma_float4* d_points, const float* d_labels,
                                const float* d_probs, uint32_t n, int32_t fixed_iterations, hipEvent_t upload_done) {
-  int r = pipeline_begin_scan_impl(s, d_points, d_labels, d_probs, n, upload_done);
-  if (r == SUMA_OK) r = pipeline_update_pose_impl(s, fixed_iterations);
-  if (r == SUMA_OK) r = pipeline_update_map_impl(s);
+  return pipeline_finish_scan(s, pipeline_begin_scan_impl(s, d_points, d_labels, d_probs, n, upload_done),
+                              fixed_iterations, false);
+}
+int pipeline_finish_scan(suma_pipeline* s, int r, int32_t fixed_iterations, bool begin_only) {
+  if (r == SUMA_OK && !begin_only) r = pipeline_update_pose_impl(s, fixed_iterations);
+  if (r == SUMA_OK && !begin_only) r = pipeline_update_map_impl(s);
   if (r != SUMA_OK && s) s->phase = 0; /* a failed scan does not wedge the phase check */
   return r;
 }

@@ -46,9 +46,8 @@ struct IngestSlot {
   const float *labels, *probs;
   uint32_t n;
   /* staging */
-  char* pinned;
-  char* device;
-  size_t cap_bytes;
+  PinnedBuf<char> pinned; /* pinned and device have the same capacity, in bytes */
+  DevBuf<char> device;
   hipEvent_t uploaded;
   hipEvent_t consumed; /* recorded on the compute stream behind the scan that read this slot */
   bool consumed_valid;
@@ -175,20 +174,14 @@ static size_t scan_bytes(uint32_t n) {
 static size_t labels_offset(uint32_t n) { return (((size_t)n * sizeof(float4)) + 255) & ~(size_t)255; }
 static size_t probs_offset(uint32_t n) { return labels_offset(n) + ((((size_t)n * sizeof(float)) + 255) & ~(size_t)255); }
 
-static hipError_t slot_reserve(Ingest* g, IngestSlot* q, uint32_t n) {
-  const size_t need = scan_bytes(n ? n : 1);
-  if (need <= q->cap_bytes) return hipSuccess;
-  const size_t cap = need + need / 4;
-  if (q->pinned) hipHostFree(q->pinned);
-  if (q->device) hipFree(q->device);
-  q->pinned = q->device = nullptr;
-  q->cap_bytes = 0;
-  hipError_t e = hipHostMalloc((void**)&q->pinned, cap, hipHostMallocDefault);
-  if (e != hipSuccess) return e;
-  e = hipMalloc((void**)&q->device, cap);
-  if (e != hipSuccess) return e;
-  q->cap_bytes = cap;
-  return hipSuccess;
+/* the slot's previous reader has finished when this runs, so nothing is drained; it runs on the ingest thread too, which
+ * must not write c->err: the error is returned */
+static hipError_t slot_reserve(IngestSlot* q, uint32_t n) {
+  const size_t need = scan_bytes(n ? n : 1), cap = need + need / 4;
+  hipError_t e = hipSuccess;
+  if (need > q->pinned.cap) e = q->pinned.alloc(cap);
+  if (e == hipSuccess && need > q->device.cap) e = q->device.alloc(cap);
+  return e;
 }
 
 static void ingest_main(Ingest* g) {
@@ -204,7 +197,7 @@ static void ingest_main(Ingest* g) {
     }
     hipError_t e = hipSuccess;
     if (q->consumed_valid) e = hipEventSynchronize(q->consumed); /* previous user of this slot has finished */
-    if (e == hipSuccess) e = slot_reserve(g, q, q->n);
+    if (e == hipSuccess) e = slot_reserve(q, q->n);
     const uint32_t n = q->n;
     if (e == hipSuccess && n > 0) {
       memcpy(q->pinned, q->points, (size_t)n * sizeof(float4));
@@ -269,10 +262,6 @@ static int ingest_get(suma_ctx* c, Ingest** out) {
   g->c = c;
   g->head = g->tail = 0;
   g->stop = false;
-  for (auto& q : g->slot) {
-    memset(&q, 0, sizeof(q));
-  }
-  for (auto& q : g->bslot) memset(&q, 0, sizeof(q));
   g->bnext = 0;
   g->pool.posted = 0;
   g->pool.pending = 0;
@@ -324,14 +313,10 @@ void ingest_destroy(suma_ctx* c) {
     if (t.joinable()) t.join();
   hipStreamSynchronize(g->copy_stream);
   for (IngestSlot* q = g->slot; q != g->slot + INGEST_SLOTS; ++q) {
-    if (q->pinned) hipHostFree(q->pinned);
-    if (q->device) hipFree(q->device);
     if (q->uploaded) hipEventDestroy(q->uploaded);
     if (q->consumed) hipEventDestroy(q->consumed);
   }
   for (auto& q : g->bslot) {
-    if (q.pinned) hipHostFree(q.pinned);
-    if (q.device) hipFree(q.device);
     if (q.uploaded) hipEventDestroy(q.uploaded);
     if (q.consumed) hipEventDestroy(q.consumed);
   }
@@ -406,7 +391,7 @@ static int run_prefetched(suma_pipeline* s, int32_t fixed_iterations, bool begin
     }
   }
   const uint32_t n = q->n;
-  const suma_float4* dp = (const suma_float4*)q->device;
+  const suma_float4* dp = (const suma_float4*)q->device.p;
   const float* dl = q->labels ? (const float*)(q->device + labels_offset(n)) : nullptr;
   const float* dq = q->probs ? (const float*)(q->device + probs_offset(n)) : nullptr;
   /* the stream that runs the scan's preprocessing waits for the upload (device-side dependency) */
@@ -420,12 +405,7 @@ static int run_prefetched(suma_pipeline* s, int32_t fixed_iterations, bool begin
     q->state = 0;
     g->head += 1;
   }
-  if (r == SUMA_OK && !begin_only) {
-    r = pipeline_update_pose_impl(s, fixed_iterations);
-    if (r == SUMA_OK) r = pipeline_update_map_impl(s);
-  }
-  if (r != SUMA_OK) s->phase = 0;
-  return r;
+  return pipeline_finish_scan(s, r, fixed_iterations, begin_only);
 }
 extern "C" int suma_pipeline_process_prefetched(suma_pipeline* s, int32_t fixed_iterations) {
   return run_prefetched(s, fixed_iterations, false);
@@ -476,7 +456,7 @@ int ingest_stage_blocking(suma_ctx* c, const suma_float4* points, const float* l
   IngestSlot* q = &g->bslot[g->bnext++ & 1u];
   long long t0 = mono_ns();
   if (q->consumed_valid) HIP_TRY(c, hipEventSynchronize(q->consumed)); /* the scan before last has read this slot */
-  HIP_TRY(c, slot_reserve(g, q, n));
+  HIP_TRY(c, slot_reserve(q, n));
   long long t1 = mono_ns();
   c->het.slot_wait_s += 1e-9 * (double)(t1 - t0);
   if (n > 0) {
@@ -510,7 +490,7 @@ int ingest_stage_blocking(suma_ctx* c, const suma_float4* points, const float* l
   }
   HIP_TRY(c, hipEventRecord(q->uploaded, g->copy_stream));
   c->het.enqueue_s += 1e-9 * (double)(mono_ns() - t1);
-  *d_points = (const suma_float4*)q->device;
+  *d_points = (const suma_float4*)q->device.p;
   *d_labels = labels ? (const float*)(q->device + labels_offset(n)) : nullptr;
   *d_probs = probs ? (const float*)(q->device + probs_offset(n)) : nullptr;
   *uploaded = q->uploaded;
@@ -560,11 +540,7 @@ static int run_host_scan(suma_pipeline* s, const suma_float4* points, const floa
   if (r) return r;
   r = pipeline_begin_scan_impl(s, dp, dl, dq, n, up);
   ingest_consumed(c, slot, pipeline_input_stream(s));
-  if (r == SUMA_OK && !begin_only) {
-    r = pipeline_update_pose_impl(s, fixed_iterations);
-    if (r == SUMA_OK) r = pipeline_update_map_impl(s);
-  }
-  if (r != SUMA_OK) s->phase = 0;
+  r = pipeline_finish_scan(s, r, fixed_iterations, begin_only);
   const double dt = 1e-9 * (double)(mono_ns() - t_call);
   c->het.call_s += dt;
   c->het.calls += 1;

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <utility>
@@ -29,6 +30,41 @@
 #define SUMA_EXTRACT_CAPACITY 500000u /* SurfelMap.cpp:279 */
 #define SUMA_MAX_MODEL_WIDTH 5461u /* floor((2^21 - 1) / (1.5 * 256)): k_render's window coordinates */
 #define SUMA_MAX_HYP 64u
+
+/* An owned device (or, with Pinned, pinned host) block of cap elements of T: freed by the destructor, moved but never
+ * copied, and read as a plain T* wherever the block is used.  A failed allocation leaves it empty. */
+template <class T, bool Pinned = false>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p = o.p, cap = o.cap;
+      o.p = nullptr, o.cap = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  operator T*() const { return p; }
+  T* operator->() const { return p; }
+  void reset() {
+    if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr, cap = 0;
+  }
+  /* replaces the block by one of n elements */
+  hipError_t alloc(size_t n) {
+    reset();
+    void* q = nullptr;
+    const hipError_t e = Pinned ? hipHostMalloc(&q, n * sizeof(T), hipHostMallocDefault) : hipMalloc(&q, n * sizeof(T));
+    if (e == hipSuccess) p = (T*)q, cap = n;
+    return e;
+  }
+};
+template <class T>
+using PinnedBuf = DevBuf<T, true>;
 
 /* Counters that live in HBM so that no kernel launch needs a host round trip. */
 struct DevState {
@@ -119,7 +155,8 @@ struct MapConsts {
 struct suma_frame {
   suma_ctx* ctx;
   uint32_t width, height;
-  float4* map[3]; /* vertex, normal, semantic: one allocation */
+  DevBuf<float4> block; /* 3 x width x height */
+  float4* map[3];       /* vertex, normal, semantic: views into block */
   /* bumped by every call of the C-ABI that writes the frame (upload / copy / swap / preprocess / render / touch): what
    * the render de-duplication and the fused K8 products compare instead of assuming that a caller-owned frame changed */
   uint64_t version;
@@ -149,12 +186,6 @@ struct HostEntryTimes {
   uint32_t copy_threads; /* caller + helpers that took a share of the copies */
 };
 
-/* a record image of the KNN back-projection (k_semantic_knn.hip): P x {class, prob bits} then P ranges, cap pixels */
-struct SemKnnScratch {
-  void* buf;
-  uint32_t cap;
-};
-
 struct suma_ctx {
   suma_params p;
   int device;
@@ -162,7 +193,7 @@ struct suma_ctx {
   hipStream_t ls;          /* stream the launchers enqueue on: == stream, except while the scan pipeline enqueues side work */
   hipStream_t side_stream; /* work that is off the critical path of a scan (the next scan's upload + preprocessing) */
   int side_stream_off;     /* SUMA_NO_SIDE_STREAM / a serialising tool: everything on the ctx stream */
-  uint32_t* sync_flags;    /* device: sequence words of the in-memory stream hand-offs (k_sync.hip) */
+  DevBuf<uint32_t> sync_flags; /* device: sequence words of the in-memory stream hand-offs (k_sync.hip) */
   uint32_t pre_seq;        /* preprocessing hand-offs issued so far */
   uint32_t gate_pending;   /* != 0: the ctx stream has not yet waited for this preprocessing hand-off (flush_gate) */
   int gate_by_event;       /* the pending hand-off is a runtime event (pre_event), not the in-memory word: several
@@ -173,7 +204,7 @@ struct suma_ctx {
   bool cache_nothing_stale; /* the last compaction attempt found no stale block: no point in synchronising again */
   const suma_frame* gate_frame; /* the frame the pending side-stream work writes */
   struct Ingest* ingest;   /* pinned double-buffered scan staging + copy stream + helper threads (suma_ingest.hip) */
-  HostResult* h_rec;       /* pinned: results of suma_icp_minimize / suma_icp_jacobian_products ([0] / [1]) */
+  PinnedBuf<HostResult> h_rec; /* results of suma_icp_minimize / suma_icp_jacobian_products ([0] / [1]) */
   uint32_t rec_seq;
   std::string err;
 
@@ -182,38 +213,32 @@ struct suma_ctx {
   size_t P, Pm;
 
   /* preprocessing scratch */
-  unsigned long long* zbuf_data; /* P keys: K7 (and K1 outside the scan pipeline's side stream) */
-  unsigned long long* zbuf_k1;   /* P keys: K1 of the scan pipeline -- preprocessing of scan t+1 overlaps K7 / K10 of scan t */
-  float4* eroded;                /* P: raw labels of K1 (scratch between k1_resolve and the fused K2/K3) */
+  DevBuf<unsigned long long> zbuf_data; /* P keys: K7 (and K1 outside the scan pipeline's side stream) */
+  DevBuf<unsigned long long> zbuf_k1;   /* P keys: K1 of the scan pipeline -- preprocessing of scan t+1 overlaps K7 / K10 of scan t */
+  DevBuf<float4> eroded;                /* P: raw labels of K1 (scratch between k1_resolve and the fused K2/K3) */
   /* optional vertex-map filters (k_filters.hip), allocated on first use */
-  float4* filt_temp;             /* P: the reference's temp_vertices_ */
-  unsigned long long* filt_sort; /* 2 x filt_cap keys (pixel << 32 | point index), unsorted / sorted */
-  void* filt_sort_tmp;
-  size_t filt_sort_tmp_bytes;
-  uint32_t filt_cap;
-  float4* scan_points;           /* staging for host scans */
-  float *scan_labels, *scan_probs;
-  uint32_t scan_cap;
+  DevBuf<float4> filt_temp;             /* P: the reference's temp_vertices_ */
+  DevBuf<unsigned long long> filt_sort; /* 2 x (cap / 2) keys (pixel << 32 | point index), unsorted / sorted */
+  DevBuf<char> filt_sort_tmp;           /* rocprim's temporary storage of a sort of filt_sort.cap / 2 keys (cap: bytes) */
+  DevBuf<float4> scan_points;           /* staging for host scans */
+  DevBuf<float> scan_labels, scan_probs;
   /* semantic front end (k_semantic.hip), allocated on first use */
-  unsigned long long* sem_zbuf; /* sem_zbuf_cap keys, left cleared by every resolve */
-  size_t sem_zbuf_cap;
-  float *sem_labels, *sem_probs; /* the back-projection of the scan pipeline's scores entry */
-  uint32_t sem_cap;
-  /* KNN post-processing (k_semantic_knn.hip): [0] suma_semantic_unproject_knn (ctx stream), [1] the pipeline's
-   * scores_knn entry (its input stream); each only grows */
-  SemKnnScratch sem_knn[2];
+  DevBuf<unsigned long long> sem_zbuf;  /* left cleared by every resolve */
+  DevBuf<float> sem_labels, sem_probs;  /* the back-projection of the scan pipeline's scores entry */
+  /* KNN post-processing (k_semantic_knn.hip): record image P x {class, prob bits} then P ranges; [0]
+   * suma_semantic_unproject_knn (ctx stream), [1] the pipeline's scores_knn entry (its input stream); each only grows */
+  DevBuf<char> sem_knn[2];
   /* SurfelMap::draw (k_draw.hip), allocated on first use: z-buffer of the largest image drawn (left cleared by every
    * resolve) and the large-quad queue, max_surfels ids + its counter (left at 0) */
-  unsigned long long* draw_zbuf;
-  size_t draw_zbuf_cap;
-  uint32_t* draw_queue;
+  DevBuf<unsigned long long> draw_zbuf;
+  DevBuf<uint32_t> draw_queue;
 
   /* ICP */
   const suma_frame *icp_current, *icp_model;
   suma_icp_objective obj; /* per-object Frame2Model parameters of the adapter (suma_icp_set_objective) */
   bool obj_set;
-  GnState* gn;        /* 2 x SUMA_MAX_HYP states, alternating with the launch parity */
-  int64_t* gn_partial; /* 3 rotating sets of SUMA_MAX_HYP x ICP_RECORDS x SUMA_ACC_WORDS accumulators (k_icp.hip) */
+  DevBuf<GnState> gn; /* 2 x SUMA_MAX_HYP states, alternating with the launch parity */
+  DevBuf<int64_t> gn_partial; /* 3 rotating sets of SUMA_MAX_HYP x ICP_RECORDS x SUMA_ACC_WORDS accumulators (k_icp.hip) */
   uint32_t gn_part_launch;   /* rotation counter, never reset */
   uint32_t gn_part_dirty[3]; /* hypotheses with possibly non-zero records, per set */
   uint32_t gn_launch;  /* launches since the last gn_init */
@@ -222,50 +247,50 @@ struct suma_ctx {
   uint64_t k8_fused_version; /* suma_frame.version the products were made from */
   uint32_t k8_fused_stamp;
   uint64_t k8_fused_params;
-  float* pose_block;       /* device: 16 floats pose + 16 floats inverse for the post-ICP render */
+  DevBuf<float> pose_block; /* 16 floats pose + 16 floats inverse for the post-ICP render */
   HostEntryTimes het;
   uint32_t icp_iteration0; /* suma_icp_set_iteration: Frame2Model::iteration_ for the NEXT suma_icp_minimize (one shot) */
-  double* gn_history;  /* (max_iterations + 1) x 16 doubles (single minimise only) */
-  double* gn_T0s;      /* SUMA_MAX_HYP x 16 staging for batched starts */
+  DevBuf<double> gn_history; /* (max_iterations + 1) x 16 doubles (single minimise only) */
+  DevBuf<double> gn_T0s;     /* SUMA_MAX_HYP x 16 staging for batched starts */
   uint32_t gn_history_cap;
   uint32_t last_n_hist; /* LieGaussNewton::history() entries of the last suma_icp_minimize */
   uint64_t hist_seq;    /* minimisations that recorded a history on this context (suma_icp_history_sequence) */
   uint32_t icp_blocks;
-  GnState* h_gn; /* pinned */
+  PinnedBuf<GnState> h_gn;
 
   /* surfel map */
-  suma_surfel* surfels[2]; /* double buffer: active map / compaction target */
+  DevBuf<suma_surfel> surfels[2]; /* double buffer: active map / compaction target */
   int cur;
-  float* poses;     /* max_poses x 16 */
-  float* poses_inv; /* max_poses x 16 */
+  DevBuf<float> poses;     /* max_poses x 16 */
+  DevBuf<float> poses_inv; /* max_poses x 16 */
   suma_frame *old_frame, *new_frame, *composed_frame;
-  unsigned long long *zbuf_a, *zbuf_b; /* Pm */
-  float4* radius_conf;                 /* P */
-  float4* pixrec;                      /* P x 4: packed measurement record for K9 (one 64-byte line per pixel) */
-  uint8_t* integrated;                 /* P */
+  DevBuf<unsigned long long> zbuf_a, zbuf_b; /* Pm */
+  DevBuf<float4> radius_conf;                /* P */
+  DevBuf<float4> pixrec;                     /* P x 4: packed measurement record for K9 (one 64-byte line per pixel) */
+  DevBuf<uint8_t> integrated;                /* P */
   /* one byte per surfel of the compaction target: "lies in the submap tile that is extracted right after this update"
    * (written by K9 / K10 at the surfel's final index, read by K12 instead of a pass over the whole map) */
-  uint8_t* extract_flags;              /* max_surfels */
+  DevBuf<uint8_t> extract_flags;       /* max_surfels */
   struct {
     bool valid;                        /* the last update flagged the tile (i, j) */
     int32_t i, j;
     bool fused;    /* ... and K9 / K10 have already written and committed the tile's cache block (slot below) */
     uint32_t slot;
   } flagged;
-  uint32_t* index_map;                 /* P: K7 winners as surfel id + 1 (exported by K10) */
-  unsigned long long* tile_status;     /* look-back status words */
-  unsigned long long* tile_group;      /* 2 x group_words, per 64 tiles: {arrived, sum}; launches alternate halves */
+  DevBuf<uint32_t> index_map;            /* P: K7 winners as surfel id + 1 (exported by K10) */
+  DevBuf<unsigned long long> tile_status; /* look-back status words */
+  DevBuf<unsigned long long> tile_group;  /* 2 x group_words, per 64 tiles: {arrived, sum}; launches alternate halves */
   uint32_t group_words;
   uint32_t n_tiles_cap;
   uint32_t epoch;
-  DevState* ds;
-  DevState* h_ds; /* pinned */
+  DevBuf<DevState> ds;
+  PinnedBuf<DevState> h_ds;
   uint32_t timestamp; /* SurfelMap::timestamp_ (host copy; kernels get it by value) */
   /* submaps (SurfelMap.cpp:744-824): caches live in a device arena, the index on the host */
   int32_t origin_i, origin_j;
-  suma_surfel* cache_arena;
+  DevBuf<suma_surfel> cache_arena;
   uint32_t cache_cap;
-  CacheSlot* cache_slots; /* device table */
+  DevBuf<CacheSlot> cache_slots; /* device table */
   uint32_t cache_compactions; /* times the arena has been compacted (cache_compact, suma_api.hip) */
   uint64_t cache_bound;       /* host-side upper bound of DevState.cache_used: exact value at the last read-back + the
                                  most every extraction since can have added */
@@ -324,7 +349,7 @@ struct suma_pipeline {
   uint32_t track_loss;
   /* the statistics pass of updatePose (SurfelMapping.cpp:411-423) is read back lazily: its copy is
    * enqueued, and resolved at the next synchronisation point instead of stalling the scan */
-  HostResult* h_res; /* pinned: [0] minimisation result, [1..2] statistics pass (alternating) */
+  PinnedBuf<HostResult> h_res; /* [0] minimisation result, [1..2] statistics pass (alternating) */
   uint32_t res_seq, stats_seq;
   bool stats_pending;
   uint32_t stats_slot;
@@ -337,11 +362,18 @@ int pipeline_begin_scan_impl(suma_pipeline* s, const suma_float4* d_points, cons
                              uint32_t n, hipEvent_t upload_done);
 int pipeline_update_pose_impl(suma_pipeline* s, int32_t fixed_iterations);
 int pipeline_update_map_impl(suma_pipeline* s);
+/* closes a scan whose begin returned r: update_pose + update_map unless r failed or begin_only; a failed scan resets
+ * the phase, so that it does not wedge the phase check */
+int pipeline_finish_scan(suma_pipeline* s, int r, int32_t fixed_iterations, bool begin_only);
 /* the stream behind which a scan's input buffers are free again (the preprocessing that read them runs there) */
 hipStream_t pipeline_input_stream(suma_pipeline* s);
+/* sets c->err and returns code */
+int fail(suma_ctx* c, int code, const std::string& msg);
 /* k_semantic.hip: parameter check of the semantic entries (sets c->err) */
-int sem_fail(suma_ctx* c, int code, const std::string& msg);
 int semantic_check(suma_ctx* c, const suma_semantic_params* sp);
+/* the scan input of the pipeline's scores entries: the phase check, sem_labels / sem_probs for n points and the wait
+ * for the scores' producer; *st = the stream the back-projection and the preprocessing run on */
+int semantic_scan_input(suma_pipeline* s, uint32_t n, void* producer_event, hipStream_t* st);
 /* suma_ingest.hip */
 void ingest_destroy(suma_ctx* c);
 void ingest_drain(suma_ctx* c);
@@ -367,6 +399,19 @@ int pipeline_process_host_scan(suma_pipeline* s, const suma_float4* points, cons
       return SUMA_ERR_HIP;                                                                       \
     }                                                                                            \
   } while (0)
+
+/* Makes b hold at least n elements: nothing if it already does; else the streams in drain that exist are synchronised
+ * (work there may still use the block; only if there is one), the block is freed and one of alloc (default: n) elements
+ * is made.  Returns 1 for a new block, 0 for none, SUMA_ERR_HIP with c->err set on failure (b is then empty). */
+template <class T, bool Pinned>
+int grow(suma_ctx* c, DevBuf<T, Pinned>& b, size_t n, std::initializer_list<hipStream_t> drain, size_t alloc = 0) {
+  if (n <= b.cap) return 0;
+  if (b)
+    for (hipStream_t st : drain)
+      if (st) HIP_TRY(c, hipStreamSynchronize(st));
+  HIP_TRY(c, b.alloc(alloc ? alloc : n));
+  return 1;
+}
 
 /* profiling scope: brackets the launches of one named kernel with events on the ctx stream */
 int prof_begin(suma_ctx* c, const char* name, double bytes, uint32_t launches);

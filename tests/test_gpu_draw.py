@@ -124,6 +124,23 @@ def test_empty_map_gives_the_clear_colour_and_repeats_bit_for_bit():
     assert (a[1] >= 0).sum() > 1000
 
 
+def test_draw_after_the_z_buffer_grows(shim):
+    """a fresh context draws the smaller image first: the larger one needs a new z-buffer on a used context"""
+    p = params_with_size(900, 64)
+    smap = core.SurfelMap(core.Context(p))
+    s, poses = dc.planar_map(5000)
+    smap.upload(s, 4)
+    smap.updatePoses(poses)
+    surf, table = smap.getAllSurfels(), smap.poses()
+    for W, H in reversed(SIZES):
+        mvp, eye = dc.chase_camera(np.eye(4), W, H)
+        img, ids = smap.draw(mvp, W, H, eye, color_mode=2, ids=True)
+        want, want_ids = dc.shim_draw(shim, surf, table, dc.params(mvp, eye, W, H, 2), n_poses=p.max_poses)
+        np.testing.assert_array_equal(ids, want_ids[::-1], err_msg=f"{W}x{H}: ids")
+        assert img.tobytes() == want[::-1].tobytes(), f"{W}x{H}: rgba"
+        assert (ids >= 0).sum() > 1000
+
+
 def test_draw_device_into_torch_buffers():
     ctx = core.Context(params_with_size(900, 64))
     smap = core.SurfelMap(ctx)

@@ -73,6 +73,17 @@ GEOMETRIES = [dict(width=2048, height=64, fov_up=3.0, fov_down=-25.0),
 
 @pytest.mark.parametrize("geo", GEOMETRIES, ids=["64x2048", "32x1024"])
 def test_projection_bit_equal_to_host(ctx, shim, geo):
+    check_projection(ctx, shim, geo)
+
+
+def test_projection_after_the_z_buffer_grows(shim):
+    """a fresh context projects the smaller image first: the larger one needs a new z-buffer on a used context"""
+    ctx = core.Context(params_with_size(N_AZ), device=0)
+    for geo in reversed(GEOMETRIES):
+        check_projection(ctx, shim, geo)
+
+
+def check_projection(ctx, shim, geo):
     sp = make_params(**geo)
     fe = SemanticFrontEnd(ctx, sp)
     for k in (0, 3):
@@ -176,6 +187,19 @@ def test_pipeline_scores_entry_equals_host_labels(ctx, monkeypatch, side, w):
         same_state(a, b)
         labels = a.map.getAllSurfels()["r"]
         assert len(np.unique(labels)) > 5  # the scores' labels reached the map
+
+
+def test_pipeline_scores_entry_after_its_labels_grow(ctx):
+    """a second scan with every point twice: the scores entry's labels grow on a pipeline that has used them"""
+    sp = make_params(width=1024, height=64)
+    rng = np.random.default_rng(12)
+    scans = [scan_points(k, N_AZ)[0] for k in range(4)]
+    scans[1] = np.concatenate([scans[1], scans[1]])
+    assert scans[1].shape[0] > scans[0].shape[0] * 5 // 4 + 1024
+    scores = [random_scores(rng, 20, 64, 1024) for _ in scans]
+    a = run_scores_pipeline(sp, scans, scores, False)
+    b = run_host_pipeline(sp, ctx, scans, scores, False, w_one=True)
+    same_state(a, b)
 
 
 @pytest.mark.parametrize("side", ["side_stream", "one_stream"])

@@ -34,7 +34,17 @@ def ctx():
 @pytest.mark.parametrize("logits", [False, True], ids=["probs", "logits"])
 @pytest.mark.parametrize("geo", GEOMETRIES, ids=["64x2048", "32x1024"])
 def test_knn_bit_equal_to_host(ctx, shim, geo, logits, kp):
-    kp = semantic_knn(*kp)
+    check_knn(ctx, shim, geo, logits, semantic_knn(*kp))
+
+
+def test_knn_after_its_scratch_grows(shim):
+    """a fresh context votes on the smaller image first: the larger one needs a new record image on a used context"""
+    ctx = core.Context(params_with_size(N_AZ), device=0)
+    for geo in reversed(GEOMETRIES):
+        check_knn(ctx, shim, geo, False, semantic_knn(*KNN[0]))
+
+
+def check_knn(ctx, shim, geo, logits, kp):
     sp = make_params(**geo)
     fe = SemanticFrontEnd(ctx, sp)
     rng = np.random.default_rng(kp.search * 10 + int(logits))
@@ -148,10 +158,11 @@ def labelled_scans(sp, ctx, count, rng, logits=False):
     return scans, scores
 
 
-def run_knn_pipeline(sp, kp, scans, scores, logits):
+def run_knn_pipeline(sps, kp, scans, scores, logits):
+    """sps: the semantic parameters of every scan"""
     hp = core.SurfelMapping(params_with_size(N_AZ), device=0)
-    fe = SemanticFrontEnd(hp, sp)
-    for pts, sc in zip(scans, scores):
+    for sp, pts, sc in zip(sps, scans, scores):
+        fe = SemanticFrontEnd(hp, sp)
         d_pts = cuda(pts)
         fe.project(d_pts)
         d_sc = cuda(sc)
@@ -162,10 +173,10 @@ def run_knn_pipeline(sp, kp, scans, scores, logits):
     return hp
 
 
-def run_standalone_then_device(sp, kp, ctx, scans, scores, logits):
+def run_standalone_then_device(sps, kp, ctx, scans, scores, logits):
     hp = core.SurfelMapping(params_with_size(N_AZ), device=0)
-    fe = SemanticFrontEnd(ctx, sp)
-    for pts, sc in zip(scans, scores):
+    for sp, pts, sc in zip(sps, scans, scores):
+        fe = SemanticFrontEnd(ctx, sp)
         d_pts = cuda(pts)
         fe.project(d_pts)
         labels, probs = fe.unproject(cuda(sc)[None], logits=logits, knn=kp)
@@ -183,10 +194,27 @@ def test_pipeline_knn_entry_equals_standalone_then_device(ctx, monkeypatch, side
     kp = semantic_knn()
     for logits in (False, True):
         scans, scores = labelled_scans(sp, ctx, 5, np.random.default_rng(6), logits)
-        a = run_knn_pipeline(sp, kp, scans, scores, logits)
-        b = run_standalone_then_device(sp, kp, ctx, scans, scores, logits)
+        a = run_knn_pipeline([sp] * len(scans), kp, scans, scores, logits)
+        b = run_standalone_then_device([sp] * len(scans), kp, ctx, scans, scores, logits)
         same_state(a, b)
         assert len(np.unique(a.map.getAllSurfels()["r"])) > 2  # the voted labels reached the map
+
+
+def test_pipeline_knn_entry_after_its_buffers_grow(ctx):
+    """a first scan on a narrower image, then a second one with every point twice: the record image and the labels of
+    the scores_knn entry grow on a pipeline that has used them"""
+    narrow, sp = make_params(width=512, height=64), make_params(width=1024, height=64)
+    kp = semantic_knn()
+    rng = np.random.default_rng(13)
+    scans, scores = labelled_scans(narrow, ctx, 1, rng)
+    more = labelled_scans(sp, ctx, 4, rng)
+    scans, scores = scans + more[0][1:], scores + more[1][1:]
+    scans[1] = np.concatenate([scans[1], scans[1]])
+    assert scans[1].shape[0] > scans[0].shape[0] * 5 // 4 + 1024
+    sps = [narrow] + [sp] * (len(scans) - 1)
+    a = run_knn_pipeline(sps, kp, scans, scores, False)
+    b = run_standalone_then_device(sps, kp, ctx, scans, scores, False)
+    same_state(a, b)
 
 
 def test_front_end_process_scan_with_knn_equals_the_manual_path():
@@ -218,7 +246,7 @@ def test_knn_entry_waits_for_the_producer_on_the_device(ctx, monkeypatch, side):
     sp = make_params(width=1024, height=64)
     kp = semantic_knn()
     scans, scores = labelled_scans(sp, ctx, 3, np.random.default_rng(9))
-    ref = run_knn_pipeline(sp, kp, scans, scores, False)
+    ref = run_knn_pipeline([sp] * len(scans), kp, scans, scores, False)
 
     hp = core.SurfelMapping(params_with_size(N_AZ), device=0)
     fe = SemanticFrontEnd(hp, sp)
