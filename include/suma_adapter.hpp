@@ -446,5 +446,65 @@ class SurfelMapping {
   std::map<std::string, double> statistics_;
 };
 
+/* Posegraph (src/core/Posegraph.h:10-78) on the device optimiser (suma_posegraph_*): the same method names and
+ * meaning, Eigen::Matrix4d / Matrix6d replaced by column-major double* (Matrix::data()).  Not needed by SurfelMapping
+ * and not provided: setMEstimator, save / load (empty in the reference, Posegraph.cpp:118-119), graph() / initial() /
+ * result() (gtsam types). */
+class Posegraph {
+ public:
+  typedef std::shared_ptr<Posegraph> Ptr;
+  typedef std::shared_ptr<const Posegraph> ConstPtr;
+
+  explicit Posegraph(int device = 0, uint32_t node_capacity = 1u << 17, uint32_t edge_capacity = 1u << 18) {
+    if (suma_posegraph_create(device, node_capacity, edge_capacity, &g_) != SUMA_OK)
+      throw std::runtime_error(std::string("suma_posegraph_create: ") + suma_posegraph_last_error(nullptr));
+  }
+  ~Posegraph() { suma_posegraph_destroy(g_); }
+  Posegraph(const Posegraph&) = delete;
+  Posegraph& operator=(const Posegraph&) = delete;
+
+  Ptr clone() const {
+    suma_posegraph* c = nullptr;
+    check(suma_posegraph_clone(g_, &c), "Posegraph::clone");
+    return Ptr(new Posegraph(c));
+  }
+  double error() const {
+    double e = 0.0;
+    check(suma_posegraph_error(g_, &e), "Posegraph::error");
+    return e;
+  }
+  void clear() { check(suma_posegraph_clear(g_), "Posegraph::clear"); }
+  void setInitial(int32_t id, const double* initial_estimate16) {
+    check(suma_posegraph_set_initial(g_, id, initial_estimate16), "Posegraph::setInitial");
+  }
+  void addEdge(int32_t from, int32_t to, const double* measurement16, const double* information36) {
+    check(suma_posegraph_add_edge(g_, from, to, measurement16, information36), "Posegraph::addEdge");
+  }
+  void pose(int32_t id, double* out16) const { check(suma_posegraph_pose(g_, id, out16), "Posegraph::pose"); }
+  /* size() x 16 doubles, sorted by id */
+  std::vector<double> poses() const {
+    std::vector<double> out(16 * (size_t)size());
+    uint32_t n = 0;
+    check(suma_posegraph_poses(g_, out.data(), (uint32_t)size(), &n), "Posegraph::poses");
+    return out;
+  }
+  int32_t size() const { return suma_posegraph_size(g_); }
+  void reinitialize() { check(suma_posegraph_reinitialize(g_), "Posegraph::reinitialize"); }
+  bool optimize(uint32_t num_iters) {
+    check(suma_posegraph_optimize(g_, num_iters, nullptr, &stats_), "Posegraph::optimize");
+    return true;
+  }
+  const suma_posegraph_stats& lastStats() const { return stats_; }
+  suma_posegraph* handle() const { return g_; }
+
+ private:
+  explicit Posegraph(suma_posegraph* g) : g_(g) {}
+  void check(int rc, const char* what) const {
+    if (rc != SUMA_OK) throw std::runtime_error(std::string(what) + ": " + suma_posegraph_last_error(g_));
+  }
+  suma_posegraph* g_ = nullptr;
+  suma_posegraph_stats stats_{};
+};
+
 }  // namespace suma_hip
 #endif

@@ -472,6 +472,78 @@ int suma_device_free(suma_ctx* ctx, void* d_ptr);
 int suma_device_upload(suma_ctx* ctx, void* d_dst, const void* host_src, uint64_t bytes);
 int suma_device_download(suma_ctx* ctx, void* host_dst, const void* d_src, uint64_t bytes);
 
+/* ---- pose graph (Posegraph, src/core/Posegraph.cpp): the optimiser between addEdge and integrateLoopClosures ----
+ * A PriorFactor on the first node (identity, information 1e6 I) plus BetweenFactor<Pose3> edges with Gaussian
+ * information, optimised by Levenberg-Marquardt in fp64 on the device (k_posegraph.hip; the mathematics is DESIGN.md
+ * "Pose graph").  A graph is its own handle with its own HIP stream on `hip_device` (not a suma_ctx), so one host
+ * thread may optimise it while another drives a pipeline on the same device (SurfelMapping.cpp:658 runs it under
+ * std::async).  Calls on one graph are serialised by the caller; the entries that launch make the graph's device the
+ * calling thread's current device.  Errors: the library's codes, text in suma_posegraph_last_error(graph) (NULL: the
+ * last failed create).  Matrices are column-major: poses double[16], information double[36] in gtsam's tangent order
+ * [omega, v] (rotation first).  Only the top 3 x 4 of a pose is read.  Non-finite input is SUMA_ERR_INVALID. */
+typedef struct suma_posegraph suma_posegraph;
+
+/* gtsam's LevenbergMarquardtParams defaults (suma_posegraph_default_params) and the inner CG solver's settings */
+typedef struct suma_posegraph_params {
+  double lambda_initial;     /* 1e-5 */
+  double lambda_factor;      /* 10: lambda * factor on a rejected step, / factor on an accepted one */
+  double lambda_upper_bound; /* 1e5: give up once lambda reaches it */
+  double lambda_lower_bound; /* 0 */
+  double min_model_fidelity; /* 1e-3: accept when (actual decrease) / (linearised decrease) exceeds it */
+  double relative_error_tol; /* 1e-5 */
+  double absolute_error_tol; /* 1e-5 */
+  double error_tol;          /* 0 */
+  double cg_tolerance;       /* 1e-10: stop CG when sqrt(r'M^-1 r / r0'M^-1 r0) <= this */
+  uint32_t cg_max_iterations; /* 1000 per damped solve */
+  uint32_t reserved;
+} suma_posegraph_params;
+
+enum {
+  SUMA_PG_MAX_ITERATIONS = 0, /* max_iterations reached (also: max_iterations == 0) */
+  SUMA_PG_CONVERGED = 1,      /* relative or absolute error decrease at or below its tolerance */
+  SUMA_PG_LAMBDA_BOUND = 2,   /* no acceptable step below lambda_upper_bound */
+  SUMA_PG_ERROR_TOL = 3       /* error at or below error_tol */
+};
+
+typedef struct suma_posegraph_stats {
+  uint32_t iterations;    /* LM iterations (linearisations) */
+  uint32_t termination;   /* SUMA_PG_* */
+  uint32_t cg_iterations; /* CG iterations summed over all damped solves */
+  uint32_t linear_solves; /* damped solves (accepted + rejected steps) */
+  double lambda;          /* final lambda */
+  double initial_error, final_error;
+} suma_posegraph_stats;
+
+void suma_posegraph_default_params(suma_posegraph_params* p);
+const char* suma_posegraph_last_error(const suma_posegraph* g);
+int suma_posegraph_create(int hip_device, uint32_t node_capacity, uint32_t edge_capacity, suma_posegraph** out);
+void suma_posegraph_destroy(suma_posegraph* g);
+int suma_posegraph_clear(suma_posegraph* g);                               /* Posegraph::clear */
+int suma_posegraph_clone(const suma_posegraph* g, suma_posegraph** out);   /* Posegraph::clone (:20-22) */
+/* Posegraph::setInitial (:25-46): sets the initial estimate AND the current result of node id; the first node also
+ * gets the prior.  Ids are dense: id == size appends (SUMA_ERR_CAPACITY beyond node_capacity), id < size updates. */
+int suma_posegraph_set_initial(suma_posegraph* g, int32_t id, const double T[16]);
+/* Posegraph::addEdge (:48-59): measurement Z of Xfrom^-1 Xto; from != to, both < size; either direction.  The
+ * information matrix is symmetrised, (I + I^T) / 2.  SUMA_ERR_CAPACITY beyond edge_capacity. */
+int suma_posegraph_add_edge(suma_posegraph* g, int32_t from, int32_t to, const double Z[16], const double information[36]);
+int suma_posegraph_pose(const suma_posegraph* g, int32_t id, double T[16]);  /* Posegraph::pose */
+/* Posegraph::poses: *n = size; SUMA_ERR_CAPACITY (nothing written) when capacity < size */
+int suma_posegraph_poses(const suma_posegraph* g, double* poses16, uint32_t capacity, uint32_t* n);
+int32_t suma_posegraph_size(const suma_posegraph* g);                        /* Posegraph::size */
+uint32_t suma_posegraph_edge_count(const suma_posegraph* g);
+int suma_posegraph_error(suma_posegraph* g, double* error);                  /* Posegraph::error: 0.5 sum e' I e */
+int suma_posegraph_reinitialize(suma_posegraph* g);                          /* Posegraph::reinitialize */
+/* Posegraph::optimize (:92-104): blocking; params NULL = the defaults.  The result replaces the current poses. */
+int suma_posegraph_optimize(suma_posegraph* g, uint32_t max_iterations, const suma_posegraph_params* params,
+                            suma_posegraph_stats* stats);
+/* the linear system at the current poses, as the optimiser builds it (for tests): factor_errors 6 per factor (factor 0
+ * the prior, then the edges in insertion order), gradient 6 per node, diag_blocks 36 per node, band_blocks 36 per
+ * node i < size - 1 (block (i, i+1)), off_blocks / off_pairs the blocks (a, b), a < b, b > a + 1, in order of the
+ * first edge between a and b.  Any output may be NULL. */
+int suma_posegraph_linearize(suma_posegraph* g, double* factor_errors, double* gradient, double* diag_blocks,
+                             double* band_blocks, double* off_blocks, int32_t* off_pairs, uint32_t off_capacity,
+                             uint32_t* n_off);
+
 /* ---- per-kernel timing (rv::Stopwatch / SurfelMapping::Stats, SurfelMapping.cpp:183-207):
  *      on = 1: every kernel group is bracketed by HIP events on the ctx stream; on = 2: only the
  *      Gauss-Newton chain (the kernel with the largest share of GPU time), which costs two event

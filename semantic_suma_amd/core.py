@@ -9,6 +9,7 @@ stand for (PRBonn/semantic_suma, src/core):
     LieGaussNewton   src/core/LieGaussNewton.h:25-76         minimize(objective, T0), pose(), history()
     SurfelMap        src/core/SurfelMap.h:36-78              update / render* / *MapFrame / updatePoses / size / draw
     SurfelMapping    src/core/SurfelMapping.h:47             processScan(scan)
+    Posegraph        src/core/Posegraph.h:10-78              setInitial / addEdge / optimize / poses
 
 Everything here is plumbing: numpy arrays in, ctypes calls into ``libsuma_hip.so`` (hand-written
 gfx950 kernels), numpy arrays out.  There is no CPU fallback -- if the library is missing or no
@@ -24,7 +25,7 @@ import os
 import numpy as np
 
 from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX_LIGHTS, SURFEL_DTYPE, DrawParams,
-                    IcpStats, SemanticKnnParams, SemanticParams, SumaParams)
+                    IcpStats, PosegraphParams, PosegraphStats, SemanticKnnParams, SemanticParams, SumaParams)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -95,6 +96,25 @@ def lib():
     vp, u32, i32, f32 = C.c_void_p, C.c_uint32, C.c_int32, C.c_float
     pp = C.POINTER(vp)
     L.suma_version.restype = C.c_char_p
+    L.suma_posegraph_last_error.restype = C.c_char_p
+    L.suma_posegraph_last_error.argtypes = [vp]
+    L.suma_posegraph_create.argtypes = [C.c_int, u32, u32, pp]
+    L.suma_posegraph_destroy.argtypes = [vp]
+    L.suma_posegraph_destroy.restype = None
+    L.suma_posegraph_clear.argtypes = [vp]
+    L.suma_posegraph_clone.argtypes = [vp, pp]
+    L.suma_posegraph_set_initial.argtypes = [vp, i32, vp]
+    L.suma_posegraph_add_edge.argtypes = [vp, i32, i32, vp, vp]
+    L.suma_posegraph_pose.argtypes = [vp, i32, vp]
+    L.suma_posegraph_poses.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_posegraph_size.argtypes = [vp]
+    L.suma_posegraph_size.restype = i32
+    L.suma_posegraph_edge_count.argtypes = [vp]
+    L.suma_posegraph_edge_count.restype = u32
+    L.suma_posegraph_error.argtypes = [vp, C.POINTER(C.c_double)]
+    L.suma_posegraph_reinitialize.argtypes = [vp]
+    L.suma_posegraph_optimize.argtypes = [vp, u32, C.POINTER(PosegraphParams), C.POINTER(PosegraphStats)]
+    L.suma_posegraph_linearize.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, C.POINTER(u32)]
     L.suma_last_error.restype = C.c_char_p
     L.suma_last_error.argtypes = [vp]
     L.suma_ctx_create.argtypes = [C.POINTER(SumaParams), C.c_int, pp]
@@ -1194,6 +1214,112 @@ class SurfelMapping:
             self.L.suma_pipeline_destroy(self.h)
             self.h = None
             self.ctx.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Posegraph:
+    """Posegraph (src/core/Posegraph.h:10-78) on the device: a prior on the first node plus BetweenFactor<Pose3> edges,
+    optimised by Levenberg-Marquardt in fp64 (suma_posegraph_*, k_posegraph.hip).  Poses are row-major 4x4 numpy
+    arrays; information matrices are 6x6 in gtsam's tangent order [omega, v].  Its own HIP stream: it may be optimised
+    on one thread while another drives a SurfelMapping on the same device."""
+
+    def __init__(self, device: int = 0, node_capacity: int = 1 << 17, edge_capacity: int = 1 << 18, handle=None):
+        self.L = lib()
+        self.device, self.node_capacity, self.edge_capacity = device, node_capacity, edge_capacity
+        if handle is None:
+            h = C.c_void_p()
+            rc = self.L.suma_posegraph_create(device, node_capacity, edge_capacity, C.byref(h))
+            if rc != 0:
+                raise SumaError(f"suma_posegraph_create failed ({rc}): {self.L.suma_posegraph_last_error(None).decode()}")
+            handle = h
+        self.h = handle
+        self.last_stats = None
+
+    def check(self, rc: int, what: str = ""):
+        if rc != 0:
+            raise SumaError(f"{what} failed ({rc}): {self.L.suma_posegraph_last_error(self.h).decode()}")
+
+    def clone(self) -> "Posegraph":
+        h = C.c_void_p()
+        self.check(self.L.suma_posegraph_clone(self.h, C.byref(h)), "suma_posegraph_clone")
+        return Posegraph(self.device, self.node_capacity, self.edge_capacity, handle=h)
+
+    def clear(self):
+        self.check(self.L.suma_posegraph_clear(self.h), "suma_posegraph_clear")
+
+    def setInitial(self, id: int, initial_estimate):
+        T = _cm(initial_estimate, np.float64)
+        self.check(self.L.suma_posegraph_set_initial(self.h, id, _ptr(T)), "suma_posegraph_set_initial")
+
+    def addEdge(self, from_: int, to: int, measurement, information):
+        Z = _cm(measurement, np.float64)
+        Om = np.ascontiguousarray(np.asarray(information, dtype=np.float64).reshape(6, 6).T)
+        self.check(self.L.suma_posegraph_add_edge(self.h, from_, to, _ptr(Z), _ptr(Om)), "suma_posegraph_add_edge")
+
+    def pose(self, id: int):
+        T = np.zeros((4, 4), dtype=np.float64)
+        self.check(self.L.suma_posegraph_pose(self.h, id, _ptr(T)), "suma_posegraph_pose")
+        return T.T.copy()
+
+    def poses(self):
+        n = self.size()
+        out = np.zeros((max(n, 1), 4, 4), dtype=np.float64)
+        got = C.c_uint32()
+        self.check(self.L.suma_posegraph_poses(self.h, _ptr(out), n, C.byref(got)), "suma_posegraph_poses")
+        return out[:got.value].transpose(0, 2, 1).copy()
+
+    def size(self) -> int:
+        return int(self.L.suma_posegraph_size(self.h))
+
+    def edgeCount(self) -> int:
+        return int(self.L.suma_posegraph_edge_count(self.h))
+
+    def error(self) -> float:
+        e = C.c_double()
+        self.check(self.L.suma_posegraph_error(self.h, C.byref(e)), "suma_posegraph_error")
+        return e.value
+
+    def reinitialize(self):
+        self.check(self.L.suma_posegraph_reinitialize(self.h), "suma_posegraph_reinitialize")
+
+    def optimize(self, num_iters: int, params: PosegraphParams = None) -> bool:
+        """Posegraph::optimize (Posegraph.cpp:92-104); params None = gtsam's LevenbergMarquardtParams defaults.
+        The statistics of the run are kept in ``last_stats`` (PosegraphStats)."""
+        st = PosegraphStats()
+        self.check(self.L.suma_posegraph_optimize(self.h, num_iters, None if params is None else C.byref(params),
+                                                  C.byref(st)), "suma_posegraph_optimize")
+        self.last_stats = st
+        return True
+
+    def linearize(self):
+        """the optimiser's linear system at the current poses: dict of factor errors (m x 6, factor 0 = the prior),
+        gradient (n x 6), diagonal blocks (n x 6 x 6), band blocks (n-1 x 6 x 6, block (i, i+1)), off-band blocks
+        (k x 6 x 6) and their pairs (k x 2)"""
+        n, m = self.size(), self.edgeCount() + 1
+        e = np.zeros((m, 6))
+        g = np.zeros((n, 6))
+        D = np.zeros((n, 6, 6))
+        U = np.zeros((max(n - 1, 1), 6, 6))
+        no = C.c_uint32()
+        self.check(self.L.suma_posegraph_linearize(self.h, _ptr(e), _ptr(g), _ptr(D), _ptr(U), None, None, 0,
+                                                   C.byref(no)), "suma_posegraph_linearize")
+        O = np.zeros((max(no.value, 1), 6, 6))
+        P = np.zeros((max(no.value, 1), 2), dtype=np.int32)
+        self.check(self.L.suma_posegraph_linearize(self.h, None, None, None, None, _ptr(O), _ptr(P), no.value,
+                                                   C.byref(no)), "suma_posegraph_linearize")
+        t = lambda B: B.transpose(0, 2, 1).copy()  # column-major blocks -> row-major numpy
+        return dict(errors=e, gradient=g, diag=t(D), band=t(U)[:max(n - 1, 0)], off=t(O)[:no.value],
+                    off_pairs=P[:no.value])
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.suma_posegraph_destroy(self.h)
+            self.h = None
 
     def __del__(self):
         try:

@@ -138,3 +138,32 @@ def default_params(**overrides) -> SumaParams:
 def params_with_size(width: int, height: int = 64, **overrides) -> SumaParams:
     """default.xml with data and model images of ``width x height`` (BASELINE configs use 64x900 / 64x2048)."""
     return default_params(data_width=width, data_height=height, model_width=width, model_height=height, **overrides)
+
+
+class PosegraphParams(C.Structure):
+    """suma_posegraph_params (include/suma_hip.h); ``PosegraphParams.defaults()`` = gtsam's LevenbergMarquardtParams"""
+    _fields_ = [("lambda_initial", f64), ("lambda_factor", f64), ("lambda_upper_bound", f64),
+                ("lambda_lower_bound", f64), ("min_model_fidelity", f64), ("relative_error_tol", f64),
+                ("absolute_error_tol", f64), ("error_tol", f64), ("cg_tolerance", f64),
+                ("cg_max_iterations", u32), ("reserved", u32)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "PosegraphParams":
+        p = cls(lambda_initial=1e-5, lambda_factor=10.0, lambda_upper_bound=1e5, lambda_lower_bound=0.0,
+                min_model_fidelity=1e-3, relative_error_tol=1e-5, absolute_error_tol=1e-5, error_tol=0.0,
+                cg_tolerance=1e-10, cg_max_iterations=1000)
+        for k, v in overrides.items():
+            setattr(p, k, v)
+        return p
+
+
+PG_MAX_ITERATIONS, PG_CONVERGED, PG_LAMBDA_BOUND, PG_ERROR_TOL = 0, 1, 2, 3
+
+
+class PosegraphStats(C.Structure):
+    """suma_posegraph_stats (include/suma_hip.h)"""
+    _fields_ = [("iterations", u32), ("termination", u32), ("cg_iterations", u32), ("linear_solves", u32),
+                ("lambda_", f64), ("initial_error", f64), ("final_error", f64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
