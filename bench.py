@@ -6,16 +6,19 @@ Gauss-Newton ICP iterations + the statistics pass, map update K7-K11, post-updat
 64x2048 range image with semantic-weighted ICP (BASELINE.json configs[1]); scans are synthetic
 (semantic_suma_amd/synth.py) and already resident in HBM when the timed region starts.  configs[1] is a FULL
 sequence, so the timed steps come after an untimed pre-roll of the same sequence (--preroll, default 300 scans)
-that brings the map to its steady size; the rate of the first scans is reported beside it as `cold_start`.
+that brings the map to its steady size; with --full the rate of the first scans is reported beside it as `cold_start`.
 N > 1: one process per GPU under torch.distributed.run -- started by the driver, or by bench.py itself when
 `python bench.py --gpus N` is run without a launcher (no WORLD_SIZE in the environment: the process re-executes
 itself through `python -m torch.distributed.run --nproc-per-node N`, see self_launch_if_needed).  Every rank runs
 its own independent sequence (sequence sharding, weak scaling) and the poses are gathered once over RCCL; the JSON
 line carries `rccl_ranks` (the process group's world size), `backend` and the device index of every rank.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run (no --full) does what the headline needs and nothing else: it generates and
+uploads the scans, runs the warm-up and the pre-roll, times the K steps, writes --dump-outputs and prints the line with
   roofline     -- dominant kernel: algorithmic bytes per launch / average launch duration, measured with
-                  HIP events on the ctx stream over the timed region
+                  HIP events on the ctx stream over the timed region (part of the timed steps, not a run of its own)
+--full adds every other leg (each with its own switch, see FULL_ONLY): `cold_start`, `host_vector_entry`, the per-kernel
+table (--kernels-json), `loop_closure_verify`, `reference_mode`, `config.odometry_error`, `adapter_path` and
   cpu_baseline -- the CPU oracle (a port of the reference path, oracle/; OpenMP over pixels / surfels, and once
                   more on one thread) timed on a bounded sample of the
                   same workload on the host cores (rank 0, N = 1 only)
@@ -56,6 +59,21 @@ def hbm_traffic(label, width, height):
         return None if k is None else float(k["hbm_bytes_per_launch"])
     except (OSError, ValueError, KeyError):
         return None
+
+
+# legs of --mode single that take scans, runs or processes of their own: argparse destination -> the value that switches
+# the leg off.  Only a --full run takes them (and `cold_start` and `config.odometry_error`, which have no switch).
+FULL_ONLY = {"cpu_scans": 0, "reference_gl_scans": 0, "adapter_scans": 0, "no_kernel_events": True, "no_host_vectors": True,
+             "no_reference_mode": True, "no_loop_closure": True}
+
+
+def plain_run(args):
+    """Without --full a --mode single run is lean: every leg of FULL_ONLY is off whatever its own switch says, so the
+    sequence is only as long as the pre-roll and the timed steps need.  With --full the switches mean what they say."""
+    if not args.full and args.mode == "single":
+        for dest, off in FULL_ONLY.items():
+            setattr(args, dest, off)
+    return args
 
 
 DUMP_BYTES = 64 << 20     # --dump-outputs writes at most this much
@@ -123,13 +141,13 @@ def _gen_job(args):
 
 
 def generate_scans(ks, W, H):
-    """synthetic scans for the indices ks (in order); long runs (the literal 4541-scan sequence) are generated by a pool
-    of worker processes -- one scan is ~25 ms of single-threaded numpy"""
+    """synthetic scans for the indices ks (in order); all but short stretches (so the 300-scan pre-roll of a default run
+    too: 8 s in one process) are generated by a pool of worker processes -- one scan is ~25 ms of single-threaded numpy"""
     ks = list(ks)
     # every rank of an N-GPU run generates its own stretch at the same time: the host's CPUs (what the cgroup grants, not
     # what the box shows -- the pool's boxes show 256 cores and grant 16) are shared between the ranks' pools
     workers = min(32, max(1, usable_cpus() // max(1, int(os.environ.get("WORLD_SIZE", "1")))))
-    if len(ks) < 400 or workers < 2:
+    if len(ks) < 100 or workers < 2:
         for k in ks:
             yield cached_scan(k, W, H)
         return
@@ -316,6 +334,11 @@ def main():
     ap.add_argument("--width", type=int, default=2048)
     ap.add_argument("--height", type=int, default=64)
     ap.add_argument("--icp-iterations", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="single mode: besides the headline, take every other leg (cold start, host-vector entry, per-kernel "
+                         "table, loop-closure verification, reference mode, odometry error, adapter path, CPU baselines); each "
+                         "leg's own switch below only counts with --full.  Off by default: a plain run sets up, warms up, "
+                         "times the steps, writes --dump-outputs and prints the line")
     ap.add_argument("--cpu-scans", type=int, default=20, help="scans of the CPU-oracle baseline sample (0 = skip)")
     ap.add_argument("--reference-gl-scans", type=int, default=3,
                     help="scans of the optional cpu_baseline_reference_gl leg (the reference's GLSL in Mesa llvmpipe; runs only "
@@ -347,7 +370,7 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="single mode: write what the timed path computed in its last step as DIR/<name>.npy (rank 0, "
                          "at most 64 MB; see dump_outputs)")
-    args = ap.parse_args()
+    args = plain_run(ap.parse_args())
     if args.dump_outputs and args.mode != "single":
         ap.error("--dump-outputs is implemented for --mode single only")
     rc = self_launch_if_needed(args)
@@ -421,17 +444,19 @@ def main():
         return native.gather(a) if native is not None and native.ok else gather_poses(a, device=coll_dev)
 
     # ---- synthetic sequence of this rank (its own stretch of the trajectory), uploaded to HBM
-    # Order of a run: Wu warm-up scans | K scans timed from the cold start (extra key `cold_start`) | untimed pre-roll
-    # until `--preroll` scans have gone through (the map reaches its steady size: the active area is bounded by the
-    # submap window, SurfelMap.cpp:667-677) | the K TIMED scans of the contract (`value`) | E scans with every kernel
-    # group bracketed.  BASELINE configs[1] is a FULL sequence: its rate is the steady-state rate, not the rate of
-    # the first scans on a near-empty map (round-2 review).  --preroll 0 times the sequence from its first scan.
+    # Order of a run: Wu warm-up scans | untimed pre-roll until `--preroll` scans have gone through (the map reaches its
+    # steady size: the active area is bounded by the submap window, SurfelMap.cpp:667-677; with --full its first K scans
+    # are timed from the cold start, extra key `cold_start`) | the K TIMED scans of the contract (`value`) | with --full:
+    # the host-vector stretch, E scans with every kernel group bracketed, the reference-mode stretch.  A plain run
+    # generates no scan behind the timed region.  BASELINE configs[1] is a FULL sequence: its rate is the steady-state
+    # rate, not the rate of the first scans on a near-empty map (round-2 review).  --preroll 0 times the sequence from
+    # its first scan.
     k0 = 400 * rank
     scans = []
     t_gen = time.perf_counter()
     E = 0 if args.no_kernel_events else max(0, min(args.profile_scans, K))
     PR = max(0, args.preroll)
-    cold = PR >= Wu + K + 20          # room for a separate cold-start measurement in front of the pre-roll
+    cold = args.full and PR >= Wu + K + 20  # room for a separate cold-start measurement in front of the pre-roll
     n_before = max(PR, Wu)            # scans processed before the timed region starts
     # scans of the host-vector entry, timed right behind the contract's region: at least 100 (the driver runs --steps 20:
     # a 20-scan sample is 7 ms, one host hiccup of a few ms moves it by a third -- round-4 review, weak point 3)
@@ -453,7 +478,7 @@ def main():
     for k, (pts, lab, prob) in enumerate(source):
         # host arrays are kept where a host-side consumer needs them: the host-vector entry (every rank), and on rank 0
         # the CPU baseline and the adapter path, which replay the sequence from its first scan up to their sample
-        keep = (n_before - 3 <= k < n_before) or (n_before + K <= k < n_before + K + HVW + HV) or \
+        keep = (HV > 0 and n_before - 3 <= k < n_before) or (n_before + K <= k < n_before + K + HVW + HV) or \
                (rank == 0 and world == 1 and (args.cpu_scans > 0 or args.adapter_scans > 0) and k < n_before + K + HVW + HV)
         scans.append((ctx.device_array(pts), ctx.device_array(lab), ctx.device_array(prob), pts.shape[0],
                       (pts, lab, prob) if keep else None))
@@ -641,7 +666,7 @@ def main():
     #      of 100 .. 800 m, from the pose table of the map (one pose per integrated scan) against the ground truth --
     #      the synthetic trajectory, or <dataset>/poses/XX.txt for a KITTI directory that has one
     odometry = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             from semantic_suma_amd import kitti as kitti_io
             est = pipe.map.poses().astype(np.float64)

@@ -284,6 +284,29 @@ def test_bench_launches_its_own_ranks():
     assert len(calls) == 1
 
 
+def test_bench_plain_run_switches_every_other_leg_off():
+    """without --full a --mode single run takes no leg besides the headline, whatever the legs' own switches say; with
+    --full, and in the other modes (--mode adapter reads --adapter-scans), the switches mean what they say"""
+    import argparse
+    import importlib.util
+    import subprocess
+    import sys
+    spec = importlib.util.spec_from_file_location("suma_bench_full", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    asked = dict(cpu_scans=20, reference_gl_scans=3, adapter_scans=120, no_kernel_events=False, no_host_vectors=False,
+                 no_reference_mode=False, no_loop_closure=False)
+    assert set(bench.FULL_ONLY) == set(asked)
+    plain = bench.plain_run(argparse.Namespace(full=False, mode="single", steps=20, warmup=5, **asked))
+    assert {k: getattr(plain, k) for k in asked} == bench.FULL_ONLY and plain.steps == 20 and plain.warmup == 5
+    assert plain.cpu_scans == 0 and plain.adapter_scans == 0 and plain.no_host_vectors and plain.no_kernel_events
+    for full, mode in ((True, "single"), (False, "adapter"), (False, "hypotheses")):
+        ns = bench.plain_run(argparse.Namespace(full=full, mode=mode, **asked))
+        assert {k: getattr(ns, k) for k in asked} == asked
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0 and "--full" in res.stdout
+
+
 def test_bench_refuses_a_world_size_other_than_gpus():
     """`--gpus 4` under a launcher that started 2 ranks: a scaling point measured on another number of ranks than it
     claims is worthless, so bench.py exits non-zero instead of "using 2" (round-4 review, item 9)."""

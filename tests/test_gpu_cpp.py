@@ -162,3 +162,45 @@ def test_bench_reads_a_kitti_format_directory(hip, tmp_path):
         a.processScan(pts, lab, prob, fixed_iterations=6)
         b.processScan(mem[k][0], mem[k][1], np.ones_like(prob), fixed_iterations=6)
     assert np.array_equal(a.getCurrentPose(), b.getCurrentPose()) and a.getCurrentPose()[0, 3] > 3.0
+
+
+def test_bench_plain_run_is_lean_and_full_run_takes_every_leg(tmp_path):
+    """`bench.py --steps K --warmup W` without --full prints the headline and what the timed steps themselves measure, and
+    nothing that takes scans, runs or processes of its own -- whatever the legs' own switches say; with --full every leg
+    is on the line and the per-kernel table is written.  Both runs time the same steps on the same inputs: what
+    --dump-outputs writes is the same to the bit."""
+    import json
+    import sys
+    legs = ["cold_start", "host_vector_entry", "loop_closure_verify", "reference_mode", "cpu_baseline",
+            "cpu_baseline_single_thread", "adapter_path"]
+    headline = ["metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"]
+    size = ["--gpus", "1", "--steps", "5", "--warmup", "2", "--width", "900", "--preroll", "30", "--cpu-scans", "4",
+            "--adapter-scans", "10", "--host-vector-scans", "5", "--profile-scans", "3"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        kj = tmp_path / (name + "_kernels.json")
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + size + extra +
+                             ["--kernels-json", str(kj), "--dump-outputs", str(tmp_path / name)],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, name + out.stderr[-2000:]
+        d = lines[name] = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert all(k in d for k in headline), (name, sorted(d))
+        assert d["metric"] == "scans_per_sec" and d["unit"] == "scans/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["steps"] == 5 and d["warmup"] == 2 and abs(d["value"] - 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert d["roofline"]["kernel"] == "k6_icp_step" and d["roofline"]["launches_in_timed_region"] == 50
+        assert d["config"]["preroll_scans"] == 30 and d["timed_call_us"]["median"] > 0
+        if name == "plain":
+            assert [k for k in legs if k in d] == [] and d["config"]["odometry_error"] is None and not kj.exists()
+        else:
+            assert [k for k in legs if k not in d] == []
+            assert d["cold_start"]["scans"] == 5 and d["host_vector_entry"]["scans"] == 5 and d["reference_mode"]["scans"] == 39
+            assert d["adapter_path"] is not None and d["cpu_baseline"]["value"] > 0
+            assert len(json.loads(kj.read_text())["kernels"]) > 5
+    # the same timed region: map sizes, drift, workload (points_per_scan is the mean over the scans a run generated)
+    same = dict(odometry_error=None, points_per_scan=None)
+    assert dict(lines["plain"]["config"], **same) == dict(lines["full"]["config"], **same)
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full")) and "surfels.npy" in names and "pose.npy" in names
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), n

@@ -4,7 +4,7 @@
 out=${1:-gpurun_out/r06_host_entry_cpus.jsonl}
 : > "$out"
 for cpus in 0-15 0-7 0-3 0-1; do
-  taskset -c $cpus python bench.py --cpu-scans 0 --adapter-scans 0 --no-kernel-events --no-loop-closure 2>/dev/null | python -c "
+  taskset -c $cpus python bench.py --full --cpu-scans 0 --adapter-scans 0 --no-kernel-events --no-loop-closure 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.readline())
 h = d['host_vector_entry']

@@ -9,6 +9,6 @@ SUMA_SEQ_CONCURRENT=2 timeout 400 python bench.py --mode sequences11 2>/dev/null
 timeout 300 python bench.py --mode adapter --adapter-scans 300 2>/dev/null | tail -1 > "$O/adapter_path_300_scans.json"
 timeout 300 python tools/ingest_bench.py 2>/dev/null | tail -1 > "$O/ingest.json"
 timeout 300 python tools/multi_seq.py 4 60 2>/dev/null | tail -1 > "$O/multi_seq.txt"
-SUMA_BENCH_FORCE_DEVICE=0 timeout 300 python bench.py --gpus 2 --backend gloo --steps 20 --cpu-scans 0 --adapter-scans 0 --no-kernel-events 2>/dev/null | tail -1 > "$O/bench_gpus2_self_launched_gloo.json"
+SUMA_BENCH_FORCE_DEVICE=0 timeout 300 python bench.py --full --gpus 2 --backend gloo --steps 20 --cpu-scans 0 --adapter-scans 0 --no-kernel-events 2>/dev/null | tail -1 > "$O/bench_gpus2_self_launched_gloo.json"
 timeout 300 python tools/gn_timeline.py 2>&1 | tail -14 > "$O/gn_timeline.txt"
 for f in bench_hypotheses bench_sequences11 adapter_path_300_scans ingest bench_gpus2_self_launched_gloo; do echo "$f: $(cut -c1-160 $O/$f.json)"; done; cat "$O/multi_seq.txt" | cut -c1-200; tail -12 "$O/gn_timeline.txt"
