@@ -4,7 +4,11 @@
  * (KITTI devkit format: the upper 3x4 of the sensor pose, row-major).
  *
  *   cc -O2 -Iinclude examples/odometry.c -Lsemantic_suma_amd -lsuma_hip -Wl,-rpath,$PWD/semantic_suma_amd -o odometry
- *   ./odometry /data/kitti/sequences/00/velodyne 4541 [labels_dir]
+ *   ./odometry [--close-loops] /data/kitti/sequences/00/velodyne 4541 [labels_dir]
+ *
+ * --close-loops: the reference's close-loops = true (config/default.xml:71).  The pipeline keeps a pose graph, verifies
+ * loop closures and integrates the optimised trajectory while it runs; the poses are then printed once, at the end, from
+ * the pose graph (SurfelMapping::getOptimizedPoses) instead of scan by scan from the odometry.
  *
  * Scan files: <dir>/%06d.bin, N x 4 float32 (x, y, z, remission) as read by the reference's
  * KITTIReader (src/io/KITTIReader.cpp:140-167).  Optional SemanticKITTI labels: <labels_dir>/%06d.label,
@@ -25,9 +29,20 @@ static size_t file_size(FILE* f) {
   return n < 0 ? 0 : (size_t)n;
 }
 
+static void print_pose(const double* T) { /* column-major in, KITTI row-major 3 x 4 out */
+  printf("%.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", T[0], T[4], T[8], T[12], T[1], T[5], T[9],
+         T[13], T[2], T[6], T[10], T[14]);
+}
+
 int main(int argc, char** argv) {
+  int close_loops = 0;
+  const char* prog = argv[0];
+  if (argc > 1 && strcmp(argv[1], "--close-loops") == 0) {
+    close_loops = 1;
+    --argc, ++argv;
+  }
   if (argc < 3) {
-    fprintf(stderr, "usage: %s <velodyne_dir> <n_scans> [labels_dir]\n", argv[0]);
+    fprintf(stderr, "usage: %s [--close-loops] <velodyne_dir> <n_scans> [labels_dir]\n", prog);
     return 2;
   }
   const char* dir = argv[1];
@@ -42,6 +57,16 @@ int main(int argc, char** argv) {
   if (suma_pipeline_create(&p, /*hip_device=*/0, &pipe) != SUMA_OK) {
     fprintf(stderr, "suma_pipeline_create: %s\n", suma_last_error(NULL));
     return 1;
+  }
+
+  if (close_loops) {
+    suma_loop_params lp;
+    suma_loop_params_default(&lp); /* the reference's thresholds (SurfelMapping.h:221-228) */
+    if (suma_pipeline_enable_loop_closing(pipe, &lp) != SUMA_OK) {
+      fprintf(stderr, "suma_pipeline_enable_loop_closing: %s\n", suma_last_error(suma_pipeline_ctx(pipe)));
+      suma_pipeline_destroy(pipe);
+      return 1;
+    }
   }
 
   suma_float4* pts = NULL;
@@ -86,10 +111,24 @@ int main(int argc, char** argv) {
       fprintf(stderr, "scan %d: %s\n", k, suma_last_error(suma_pipeline_ctx(pipe)));
       break;
     }
+    if (close_loops) {
+      suma_loop_status ls;
+      if (suma_pipeline_loop_status(pipe, &ls) == SUMA_OK && (ls.edges_added || ls.integrated))
+        fprintf(stderr, "scan %d: %u loop edge(s) added%s\n", k, ls.edges_added,
+                ls.integrated ? ", optimised trajectory integrated" : "");
+      continue;
+    }
     double T[16]; /* column-major */
     suma_pipeline_pose(pipe, T);
-    printf("%.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", T[0], T[4], T[8], T[12], T[1], T[5], T[9],
-           T[13], T[2], T[6], T[10], T[14]);
+    print_pose(T);
+  }
+  if (close_loops) { /* the pose graph's poses: optimised up to the last integration, odometry behind it */
+    const suma_posegraph* g = suma_pipeline_posegraph(pipe);
+    const int32_t n = suma_posegraph_size(g);
+    for (int32_t k = 0; k < n; ++k) {
+      double T[16];
+      if (suma_posegraph_pose(g, k, T) == SUMA_OK) print_pose(T);
+    }
   }
   fprintf(stderr, "frame-to-frame fallbacks: %u\n", suma_pipeline_track_loss(pipe));
   free(pts);

@@ -226,7 +226,8 @@ int suma_pipeline_process_scan_async(suma_pipeline* s, const suma_float4* points
  *      statistics and render de-duplication -- a host with loop closures on loses none of them.
  *      Between update_pose and update_map the host may call suma_pipeline_verify_loop_closure /
  *      suma_pipeline_track_loop_closure (the device sides of checkLoopClosure) and suma_pipeline_set_pose_old;
- *      before begin_scan, suma_pipeline_integrate_loop_closures. */
+ *      before begin_scan, suma_pipeline_integrate_loop_closures.  Or it enables the pipeline's own loop closing
+ *      (suma_pipeline_enable_loop_closing) and calls suma_pipeline_check_loop_closure there. */
 int suma_pipeline_begin_scan(suma_pipeline* s, const suma_float4* points, const float* labels, const float* probs,
                              uint32_t n);
 int suma_pipeline_begin_scan_device(suma_pipeline* s, const suma_float4* d_points, const float* d_labels,
@@ -277,8 +278,8 @@ suma_frame* suma_pipeline_frame(suma_pipeline* s, int which);
  *      identity against it.  Faithful to the reference's sequencing, including its quirk that after
  *      a passing guess the objective keeps pointing at the composed frame for the remaining guesses
  *      (setData is called once before the loop, :693, and again inside the branch, :719).
- *      The candidate search, thresholds on the returned ratios and the pose-graph edges stay with the
- *      caller (SurfelMapping / gtsam are out of scope). */
+ *      The candidate search, thresholds on the returned ratios and the pose-graph edges are the caller's here;
+ *      suma_pipeline_enable_loop_closing (below) is the pipeline doing all of it itself. */
 typedef struct suma_loop_result {
   double gn_pose[16];            /* LieGaussNewton::pose() of this guess (relative to pose_prior) */
   suma_icp_stats after_minimize; /* jacobianProducts at that pose (:705): valid / outlier ratios */
@@ -543,6 +544,87 @@ int suma_posegraph_optimize(suma_posegraph* g, uint32_t max_iterations, const su
 int suma_posegraph_linearize(suma_posegraph* g, double* factor_errors, double* gradient, double* diag_blocks,
                              double* band_blocks, double* off_blocks, int32_t* off_pairs, uint32_t off_capacity,
                              uint32_t* n_off);
+
+/* a graph's capacities raised to at least these (they never shrink).  Capacities are limits on the host record only: the
+ * device blocks are sized by the graph itself and double when it outgrows them. */
+int suma_posegraph_reserve(suma_posegraph* g, uint32_t node_capacity, uint32_t edge_capacity);
+/* edge `index` in insertion order (Posegraph::save walks them): any output may be NULL; information as it is stored,
+ * symmetrised */
+int suma_posegraph_edge(const suma_posegraph* g, uint32_t index, int32_t* from, int32_t* to, double Z[16],
+                        double information[36]);
+
+/* ---- loop closing inside the scan pipeline: SurfelMapping::checkLoopClosure and the pose-graph bookkeeping around it
+ *      (SurfelMapping.cpp:42-60, :212-253, :461-471, :478-518, :527-795, :819-826), opt-in.  Once enabled, the pipeline
+ *      owns a suma_posegraph: every scan appends its node and odometry edge (updatePose, :461-471), begin_scan* first
+ *      integrates a finished optimisation (integrateLoopClosures, :179), and the whole-scan entries run
+ *      checkLoopClosure between updatePose and updateMap (:196).  Hosts on the phase calls place
+ *      suma_pipeline_check_loop_closure there themselves.  The state machine is the reference's statement for
+ *      statement (DESIGN.md 9 lists the quirks that are kept); its host-side 4x4 products and rigid inverses use the
+ *      library's one fixed operation order.  (Kept here, not in suma_types.h, for the reason given at
+ *      suma_semantic_params.) */
+typedef struct suma_loop_params {
+  float residual_threshold;      /* loop-residual-threshold, 1.05 (SurfelMapping.h:225) */
+  float outlier_threshold;       /* loop-outlier-threshold, 1.1 */
+  float valid_threshold;         /* loop-valid-threshold, 0.9 */
+  float search_distance;         /* loop-search-distance, 20 */
+  float min_trajectory_distance; /* loop-min-trajectory-distance, 200 */
+  int32_t min_verifications;     /* loop-min-verifications, 3 */
+  int32_t delta_timestamp;       /* loopDetlaTimestamp_, 100 */
+  int32_t optimize_wait;         /* 1: an optimisation started in scan k is waited for and integrated at the start of scan
+                                    k + 1 + integrate_lag (deterministic); 0: the reference's polling -- integrated at the
+                                    first scan start that finds it finished, no wait, integrate_lag ignored */
+  /* the gates the reference writes as literals (:567, :713): 0.2, 0.85, 0.1 */
+  double min_valid_ratio, max_outlier_ratio, max_increment_difference;
+  double information[36];        /* info_ of every edge (:49-59), column-major, gtsam order [omega, v]; identity */
+  uint32_t optimize_iterations;  /* Posegraph::optimize(100), :825 */
+  uint32_t integrate_lag;        /* 0 */
+  uint32_t node_capacity;        /* initial capacity of the pipeline's graph (it grows by doubling), 1024 */
+  uint32_t reserved;
+} suma_loop_params;
+
+/* what one scan's loop closing did; the persistent members are the values after the scan's last loop-closing step */
+typedef struct suma_loop_status {
+  int32_t found_candidate;  /* foundLoopClosureCandidate_ */
+  int32_t use_candidate;    /* useLoopClosureCandidate_ */
+  int32_t candidate_to;     /* `to` of the candidate this scan queued, -1: none */
+  uint32_t n_unverified;    /* unverifiedLoopClosures_.size() */
+  int32_t already_verified; /* alreadyVerifiedLoopClosure_ */
+  int32_t loop_count;       /* loopCount_ */
+  uint32_t time_without_loop_closure;
+  int32_t currently_optimizing;
+  int32_t started_optimization; /* this scan cloned the graph and started the optimiser (:655-660) */
+  int32_t integrated;           /* this scan's start integrated an optimised graph (:212-253) */
+  uint32_t edges_added;         /* loop edges added by this scan (:649) */
+  float result_old_outlier_ratio;
+  suma_icp_stats result_old;    /* result_old_: error, inlier_residual (already divided by inlier, :583 / :747), counters;
+                                   iterations / converged unused */
+  double result_old_residual;
+  float loop_valid_ratio, loop_outlier_ratio, loop_relative_error_all; /* :784-786 */
+  float reserved;
+  double posegraph_error;       /* posegraph_->error(), :793 */
+} suma_loop_status;
+
+void suma_loop_params_default(suma_loop_params* p);
+/* NULL switches loop closing off (and frees the graph).  Only between scans; a running optimisation is joined first.
+ * Enabling (again) starts from the constructor's state: node 0 at identity (:43), no candidates; the graph's
+ * later nodes are numbered by the pipeline's timestamp, so enable it before the first scan or after a reset. */
+int suma_pipeline_enable_loop_closing(suma_pipeline* s, const suma_loop_params* params);
+/* checkLoopClosure (:527-795): between suma_pipeline_update_pose and suma_pipeline_update_map, once per scan; does
+ * nothing at timestamp 0 (:190) */
+int suma_pipeline_check_loop_closure(suma_pipeline* s);
+int suma_pipeline_loop_status(const suma_pipeline* s, suma_loop_status* out);
+/* the pipeline's graph, borrowed (NULL when loop closing is off): read it with suma_posegraph_pose / _poses / _edge
+ * between scans; getOptimizedPoses() = suma_posegraph_poses */
+suma_posegraph* suma_pipeline_posegraph(suma_pipeline* s);
+/* trajectory_distances_ (:461-471, :242-250): *n = entries, min(*n, capacity) copied */
+int suma_pipeline_trajectory_distances(const suma_pipeline* s, float* out, uint32_t capacity, uint32_t* n);
+/* getCandidateIndexes / getClosestIndex (:478-518) as a pure host function: j runs down from timestamp -
+ * delta_timestamp, distance = float(|t(current_pose) - t(poses16[j])|), strict <, and trajectory_distances[timestamp] -
+ * trajectory_distances[j] > min_trajectory_distance.  poses16: column-major 4x4 doubles, only the translation is read.
+ * Returns the index or -1. */
+int32_t suma_loop_find_candidate(const double* poses16, const float* trajectory_distances, uint32_t timestamp,
+                                 const double current_pose[16], float radius, float min_trajectory_distance,
+                                 int32_t delta_timestamp);
 
 /* ---- per-kernel timing (rv::Stopwatch / SurfelMapping::Stats, SurfelMapping.cpp:183-207):
  *      on = 1: every kernel group is bracketed by HIP events on the ctx stream; on = 2: only the

@@ -25,7 +25,8 @@ import os
 import numpy as np
 
 from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX_LIGHTS, SURFEL_DTYPE, DrawParams,
-                    IcpStats, PosegraphParams, PosegraphStats, SemanticKnnParams, SemanticParams, SumaParams)
+                    IcpStats, LoopParams, LoopStatus, PosegraphParams, PosegraphStats, SemanticKnnParams,
+                    SemanticParams, SumaParams)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -115,6 +116,18 @@ def lib():
     L.suma_posegraph_reinitialize.argtypes = [vp]
     L.suma_posegraph_optimize.argtypes = [vp, u32, C.POINTER(PosegraphParams), C.POINTER(PosegraphStats)]
     L.suma_posegraph_linearize.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, C.POINTER(u32)]
+    L.suma_posegraph_reserve.argtypes = [vp, u32, u32]
+    L.suma_posegraph_edge.argtypes = [vp, u32, C.POINTER(i32), C.POINTER(i32), vp, vp]
+    L.suma_loop_params_default.argtypes = [C.POINTER(LoopParams)]
+    L.suma_loop_params_default.restype = None
+    L.suma_pipeline_enable_loop_closing.argtypes = [vp, C.POINTER(LoopParams)]
+    L.suma_pipeline_check_loop_closure.argtypes = [vp]
+    L.suma_pipeline_loop_status.argtypes = [vp, C.POINTER(LoopStatus)]
+    L.suma_pipeline_posegraph.argtypes = [vp]
+    L.suma_pipeline_posegraph.restype = vp
+    L.suma_pipeline_trajectory_distances.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_loop_find_candidate.argtypes = [vp, vp, u32, vp, f32, f32, i32]
+    L.suma_loop_find_candidate.restype = i32
     L.suma_last_error.restype = C.c_char_p
     L.suma_last_error.argtypes = [vp]
     L.suma_ctx_create.argtypes = [C.POINTER(SumaParams), C.c_int, pp]
@@ -950,12 +963,26 @@ def run_hypotheses_native(params: SumaParams, scans, perturbations, rank: int = 
     return poses[:n].reshape(n, 4, 4).transpose(0, 2, 1).copy(), [int(w) for w in winners[:n]]
 
 
+def loop_find_candidate(poses, trajectory_distances, timestamp: int, current_pose, radius: float,
+                        min_trajectory_distance: float, delta_timestamp: int) -> int:
+    """getCandidateIndexes / getClosestIndex (SurfelMapping.cpp:478-518) as the library runs it on the host
+    (suma_loop_find_candidate); poses: n x 4 x 4 row-major doubles.  Returns the index or -1."""
+    P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1))
+    d = np.ascontiguousarray(trajectory_distances, dtype=np.float32)
+    cur = _cm(current_pose, np.float64)
+    return int(lib().suma_loop_find_candidate(_ptr(P), _ptr(d), timestamp, _ptr(cur), radius, min_trajectory_distance,
+                                              delta_timestamp))
+
+
 class SurfelMapping:
     """SurfelMapping::processScan (SurfelMapping.cpp:175-210).  processScan* run a scan in one call; beginScan /
-    updatePose / updateMap are its phases for hosts that run loop closures between them (verifyLoopClosure,
-    trackLoopClosure, setPoseOld, integrateLoopClosures).  The candidate search and the pose graph stay with the host."""
+    updatePose / updateMap are its phases.  With ``loop_params`` (types.LoopParams) the pipeline closes loops itself, as
+    the reference does with close-loops = true: it keeps the pose graph (``posegraph``), every beginScan* first
+    integrates a finished optimisation, processScan* run checkLoopClosure between updatePose and updateMap, and hosts
+    on the phase calls place ``checkLoopClosure()`` there.  Without it, a host may still script closures by hand
+    (verifyLoopClosure, trackLoopClosure, setPoseOld, integrateLoopClosures)."""
 
-    def __init__(self, params: SumaParams, device: int = 0):
+    def __init__(self, params: SumaParams, device: int = 0, loop_params: LoopParams = None):
         self.L = lib()
         self.params = params
         h = C.c_void_p()
@@ -966,6 +993,52 @@ class SurfelMapping:
         self.ctx = Context(params, handle=C.c_void_p(self.L.suma_pipeline_ctx(h)), owner=self)
         self.map = SurfelMap(self.ctx)
         self._staged = []
+        self.device = device
+        self.posegraph = None
+        if loop_params is not None:
+            self.enableLoopClosing(loop_params)
+
+    # ---- loop closing inside the pipeline (suma_pipeline_enable_loop_closing ...)
+    def enableLoopClosing(self, loop_params: LoopParams = None):
+        """None switches it off; only between scans.  A ``posegraph`` handed out before is dead afterwards: the
+        pipeline has destroyed the graph behind it."""
+        old, self.posegraph = self.posegraph, None
+        rc = self.L.suma_pipeline_enable_loop_closing(self.h, None if loop_params is None else C.byref(loop_params))
+        h = self.L.suma_pipeline_posegraph(self.h)
+        if old is not None:
+            if rc != 0 and h is not None and h == old.h.value:
+                self.posegraph = old  # refused: the pipeline has kept its graph
+            else:
+                old.h = None
+        self.ctx.check(rc, "suma_pipeline_enable_loop_closing")
+        if loop_params is not None:
+            g = Posegraph(self.device, handle=C.c_void_p(h))
+            g.borrowed = True  # the pipeline destroys it
+            self.posegraph = g
+
+    def checkLoopClosure(self):
+        """SurfelMapping::checkLoopClosure, between updatePose and updateMap"""
+        self.ctx.check(self.L.suma_pipeline_check_loop_closure(self.h), "suma_pipeline_check_loop_closure")
+
+    def loopStatus(self) -> LoopStatus:
+        st = LoopStatus()
+        self.ctx.check(self.L.suma_pipeline_loop_status(self.h, C.byref(st)), "suma_pipeline_loop_status")
+        return st
+
+    def trajectoryDistances(self) -> np.ndarray:
+        n = C.c_uint32()
+        self.ctx.check(self.L.suma_pipeline_trajectory_distances(self.h, None, 0, C.byref(n)),
+                       "suma_pipeline_trajectory_distances")
+        out = np.zeros(max(n.value, 1), dtype=np.float32)
+        self.ctx.check(self.L.suma_pipeline_trajectory_distances(self.h, _ptr(out), n.value, C.byref(n)),
+                       "suma_pipeline_trajectory_distances")
+        return out[:n.value]
+
+    def getOptimizedPoses(self) -> np.ndarray:
+        """SurfelMapping::getOptimizedPoses: the pose graph's poses"""
+        if self.posegraph is None:
+            raise SumaError("getOptimizedPoses: loop closing is not enabled")
+        return self.posegraph.poses()
 
     def processScan(self, points, labels=None, probs=None, fixed_iterations: int = 0):
         points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
@@ -1211,6 +1284,8 @@ class SurfelMapping:
 
     def close(self):
         if getattr(self, "h", None):
+            if getattr(self, "posegraph", None) is not None:
+                self.posegraph.h = None
             self.L.suma_pipeline_destroy(self.h)
             self.h = None
             self.ctx.h = None
@@ -1239,10 +1314,26 @@ class Posegraph:
             handle = h
         self.h = handle
         self.last_stats = None
+        self.borrowed = False  # a pipeline's own graph (SurfelMapping.posegraph): not destroyed here
 
     def check(self, rc: int, what: str = ""):
         if rc != 0:
             raise SumaError(f"{what} failed ({rc}): {self.L.suma_posegraph_last_error(self.h).decode()}")
+
+    def reserve(self, node_capacity: int, edge_capacity: int):
+        self.check(self.L.suma_posegraph_reserve(self.h, node_capacity, edge_capacity), "suma_posegraph_reserve")
+
+    def edge(self, index: int):
+        """(from, to, measurement 4x4, information 6x6) of edge ``index`` in insertion order"""
+        a, b = C.c_int32(), C.c_int32()
+        Z = np.zeros((4, 4), dtype=np.float64)
+        Om = np.zeros((6, 6), dtype=np.float64)
+        self.check(self.L.suma_posegraph_edge(self.h, index, C.byref(a), C.byref(b), _ptr(Z), _ptr(Om)),
+                   "suma_posegraph_edge")
+        return a.value, b.value, Z.T.copy(), Om.T.copy()
+
+    def edges(self):
+        return [self.edge(k) for k in range(self.edgeCount())]
 
     def clone(self) -> "Posegraph":
         h = C.c_void_p()
@@ -1318,7 +1409,8 @@ class Posegraph:
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.suma_posegraph_destroy(self.h)
+            if not self.borrowed:
+                self.L.suma_posegraph_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -683,10 +683,13 @@ int pg_fail(const suma_posegraph* g, int code, const std::string& msg) {
     if (e__ != hipSuccess) return pg_fail(g, SUMA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
   } while (0)
 
+/* A first allocation is exact (a clone is prepared once, at its final size); a block that has to grow doubles, so a
+ * graph that gains a node and an edge between two preparations -- the scan pipeline's -- allocates and frees nothing in
+ * all but O(log n) of them.  hipFree waits for the whole device, the optimiser's stream included. */
 template <class T>
 hipError_t pg_grow(DevBuf<T>& b, size_t n) {
   n = std::max<size_t>(n, 1);
-  return n <= b.cap ? hipSuccess : b.alloc(n);
+  return n <= b.cap ? hipSuccess : b.alloc(std::max(n, 2 * b.cap));
 }
 
 bool finite_n(const double* a, size_t n) {
@@ -1011,6 +1014,25 @@ int suma_posegraph_poses(const suma_posegraph* g, double* out, uint32_t capacity
   return SUMA_OK;
 }
 
+int suma_posegraph_reserve(suma_posegraph* g, uint32_t node_capacity, uint32_t edge_capacity) {
+  if (!g) return SUMA_ERR_INVALID;
+  if (node_capacity > (1u << 30) || edge_capacity > (1u << 29)) return pg_fail(g, SUMA_ERR_INVALID, "reserve: bad argument");
+  g->node_cap = std::max(g->node_cap, node_capacity);
+  g->edge_cap = std::max(g->edge_cap, edge_capacity);
+  return SUMA_OK;
+}
+
+int suma_posegraph_edge(const suma_posegraph* g, uint32_t index, int32_t* from, int32_t* to, double Z[16],
+                        double information[36]) {
+  if (!g) return SUMA_ERR_INVALID;
+  if (index >= g->efrom.size()) return pg_fail(g, SUMA_ERR_INVALID, "edge: index must be < edge count");
+  if (from) *from = g->efrom[index];
+  if (to) *to = g->eto[index];
+  if (Z) from_rigid(g->eZ.data() + 12 * (size_t)index, Z);
+  if (information) std::copy(g->eOm.begin() + 36 * (size_t)index, g->eOm.begin() + 36 * (size_t)(index + 1), information);
+  return SUMA_OK;
+}
+
 int suma_posegraph_reinitialize(suma_posegraph* g) {
   if (!g) return SUMA_ERR_INVALID;
   g->result = g->initial;
@@ -1158,3 +1180,15 @@ int suma_posegraph_optimize(suma_posegraph* g, uint32_t max_iterations, const su
 }
 
 }  // extern "C"
+
+/* for the scan pipeline's loop closing (suma_loop.hip): the poses where they lie, rigid R (row-major) | t, 12 doubles a
+ * node.  device: the optimiser's result buffer, valid behind a suma_posegraph_optimize of a non-empty graph (its
+ * stream has been synchronised when that returns). */
+const double* posegraph_host_poses(const suma_posegraph* g, uint32_t* n) {
+  *n = (uint32_t)(g->result.size() / 12);
+  return g->result.data();
+}
+const double* posegraph_device_poses(const suma_posegraph* g, uint32_t* n) {
+  *n = g->n_dev;
+  return g->X.p;
+}

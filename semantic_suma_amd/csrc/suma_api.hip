@@ -1662,6 +1662,7 @@ extern "C" int suma_pipeline_create(const suma_params* params, int hip_device, s
 }
 extern "C" void suma_pipeline_destroy(suma_pipeline* s) {
   if (!s) return;
+  loop_destroy(s); /* joins a running pose-graph optimisation (SurfelMapping.cpp:64-66) */
   ingest_destroy(s->c); /* its threads use the frames and streams freed below */
   if (s->c && s->c->stream) hipStreamSynchronize(s->c->stream);
   suma_frame_destroy(s->last_frame);
@@ -1881,6 +1882,10 @@ int pipeline_begin_scan_impl(suma_pipeline* s, const suma_float4* d_points, cons
   suma_ctx* c = s->c;
   if (s->phase != 0) return fail(c, SUMA_ERR_INVALID, "suma_pipeline_begin_scan: the previous scan has not been closed with suma_pipeline_update_map");
   c->obj_set = false; /* the pipeline's objective_ runs on the ctx parameters (suma_params), not on a stale adapter object's */
+  if (s->loop) { /* integrateLoopClosures(), :179: in front of everything that reads the poses */
+    int ri = loop_integrate(s);
+    if (ri) return ri;
+  }
   /* initialize(), SurfelMapping.cpp:323-331 */
   std::swap(s->last_frame, s->current_frame);
   std::swap(s->last_model, s->current_model);
@@ -1918,6 +1923,7 @@ int pipeline_update_pose_impl(suma_pipeline* s, int32_t fixed_iterations) {
   if (s->timestamp > 0) { /* :190 */
     int r = update_pose(s, fixed_iterations);
     if (r) return r;
+    if (s->loop && (r = loop_odometry_edge(s)) != SUMA_OK) return r; /* :461-471 */
   }
   s->phase = 2;
   return SUMA_OK;
@@ -1948,6 +1954,7 @@ int pipeline_process_scan_impl(suma_pipeline* s, const suma_float4* d_points, co
 }
 int pipeline_finish_scan(suma_pipeline* s, int r, int32_t fixed_iterations, bool begin_only) {
   if (r == SUMA_OK && !begin_only) r = pipeline_update_pose_impl(s, fixed_iterations);
+  if (r == SUMA_OK && !begin_only && s->loop && s->timestamp > 0) r = loop_check(s); /* :196 */
   if (r == SUMA_OK && !begin_only) r = pipeline_update_map_impl(s);
   if (r != SUMA_OK && s) s->phase = 0; /* a failed scan does not wedge the phase check */
   return r;
@@ -1972,6 +1979,8 @@ extern "C" int suma_pipeline_reset(suma_pipeline* s) {
   host_synced(c);
   ingest_drain(c); /* scans staged ahead by a sequence that ended early are not this pipeline's next scans */
   r = map_reset_impl(c); /* also clears an index-map splat nobody will consume */
+  if (r) return r;
+  r = loop_reset(s); /* posegraph_->clear(), node 0 at identity, no candidates (:158-164) */
   if (r) return r;
   s->stats_pending = false;
   memset(&s->stats, 0, sizeof(s->stats));
@@ -2024,6 +2033,10 @@ extern "C" int suma_pipeline_apply_increment(suma_pipeline* s, const double incr
   memcpy(s->pose_old, np, sizeof(np));
   memcpy(s->pose_new, np, sizeof(np));
   memcpy(s->last_increment, increment, 16 * sizeof(double));
+  if (s->loop) { /* :461-471 */
+    int r = loop_odometry_edge(s);
+    if (r) return r;
+  }
   s->phase = 2;
   return SUMA_OK;
 }

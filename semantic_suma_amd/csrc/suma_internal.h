@@ -354,6 +354,7 @@ struct suma_pipeline {
   bool stats_pending;
   uint32_t stats_slot;
   suma_icp_stats stats_mst;
+  struct LoopState* loop; /* suma_pipeline_enable_loop_closing; NULL: off, and nothing of the loop closing runs */
 };
 
 int pipeline_process_scan_impl(suma_pipeline* s, const suma_float4* d_points, const float* d_labels, const float* d_probs,
@@ -470,6 +471,21 @@ hipError_t launch_signal(suma_ctx* c, hipStream_t st, uint32_t word, uint32_t se
 hipError_t launch_gate(suma_ctx* c, hipStream_t st, uint32_t word, uint32_t seq);
 /* makes the ctx stream wait for the pending preprocessing hand-off (one-wave gate kernel) */
 hipError_t flush_gate(suma_ctx* c);
+
+/* k_posegraph.hip: a graph's poses where they lie (12 doubles a node, R row-major | t) */
+const double* posegraph_host_poses(const suma_posegraph* g, uint32_t* n);
+const double* posegraph_device_poses(const suma_posegraph* g, uint32_t* n);
+/* k_loop.hip: integrateLoopClosures' pose table (SurfelMapping.cpp:219-233) written on the ctx stream: rows < n_opt =
+ * float(opt), rows n_opt .. n_opt + n_tail - 1 = float(difference * tail) */
+hipError_t launch_loop_integrate(suma_ctx* c, const double* d_opt12, uint32_t n_opt, const double* d_tail16,
+                                 uint32_t n_tail, const double difference[16]);
+/* suma_loop.hip: the loop-closing state of a pipeline (NULL: off) and its three hooks */
+struct LoopState;
+int loop_integrate(suma_pipeline* s);               /* integrateLoopClosures, at the start of every begin_scan */
+int loop_odometry_edge(suma_pipeline* s);           /* SurfelMapping.cpp:461-471, at the end of updatePose */
+int loop_check(suma_pipeline* s);                   /* checkLoopClosure */
+void loop_destroy(suma_pipeline* s);                /* joins the worker, frees the graph */
+int loop_reset(suma_pipeline* s);                   /* the constructor's state */
 
 /* host helper shared by api + pipeline */
 void rigid_inverse_f(const float* m, float* out);

@@ -167,3 +167,42 @@ class PosegraphStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class LoopParams(C.Structure):
+    """suma_loop_params (include/suma_hip.h); ``LoopParams.defaults()`` = suma_loop_params_default: the reference's
+    values (SurfelMapping.h:221-228), the literal gates of checkLoopClosure, identity information"""
+    _fields_ = [("residual_threshold", f32), ("outlier_threshold", f32), ("valid_threshold", f32),
+                ("search_distance", f32), ("min_trajectory_distance", f32), ("min_verifications", i32),
+                ("delta_timestamp", i32), ("optimize_wait", i32), ("min_valid_ratio", f64), ("max_outlier_ratio", f64),
+                ("max_increment_difference", f64), ("information", f64 * 36), ("optimize_iterations", u32),
+                ("integrate_lag", u32), ("node_capacity", u32), ("reserved", u32)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "LoopParams":
+        p = cls(residual_threshold=1.05, outlier_threshold=1.1, valid_threshold=0.9, search_distance=20.0,
+                min_trajectory_distance=200.0, min_verifications=3, delta_timestamp=100, optimize_wait=1,
+                min_valid_ratio=0.2, max_outlier_ratio=0.85, max_increment_difference=0.1, optimize_iterations=100,
+                integrate_lag=0, node_capacity=1024)
+        for k in range(6):
+            p.information[7 * k] = 1.0
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise KeyError(f"unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+
+class LoopStatus(C.Structure):
+    """suma_loop_status (include/suma_hip.h): what one scan's loop closing did"""
+    _fields_ = [("found_candidate", i32), ("use_candidate", i32), ("candidate_to", i32), ("n_unverified", u32),
+                ("already_verified", i32), ("loop_count", i32), ("time_without_loop_closure", u32),
+                ("currently_optimizing", i32), ("started_optimization", i32), ("integrated", i32), ("edges_added", u32),
+                ("result_old_outlier_ratio", f32), ("result_old", IcpStats), ("result_old_residual", f64),
+                ("loop_valid_ratio", f32), ("loop_outlier_ratio", f32), ("loop_relative_error_all", f32),
+                ("reserved", f32), ("posegraph_error", f64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("result_old", "reserved")}
+        d["result_old"] = self.result_old.as_dict()
+        return d
