@@ -320,12 +320,49 @@ class SurfelMap {
     check(ctx_.get(), suma_map_download(ctx_.get(), out.data(), (uint32_t)out.size(), &n), "SurfelMap::getAllSurfels");
     return out;
   }
+  /* the (i, j) of every parked submap tile that holds records, ascending by (i, then j) */
+  std::vector<std::pair<int32_t, int32_t>> cachedTiles() {
+    uint32_t n = 0;
+    check(ctx_.get(), suma_map_cached_tiles(ctx_.get(), nullptr, 0, &n), "SurfelMap::cachedTiles");
+    std::vector<int32_t> ij(2 * (size_t)n);
+    if (n) check(ctx_.get(), suma_map_cached_tiles(ctx_.get(), ij.data(), n, &n), "SurfelMap::cachedTiles");
+    std::vector<std::pair<int32_t, int32_t>> out;
+    for (uint32_t k = 0; k < n && 2 * (size_t)k + 1 < ij.size(); ++k) out.emplace_back(ij[2 * k], ij[2 * k + 1]);
+    return out;
+  }
+  /* the whole map (active surfels and every parked tile) in the world frame, filtered and optionally fused to voxels
+   * (suma_map_export_world); computed on the device, returned on the host */
+  std::vector<suma_world_surfel> exportWorld(const suma_world_params& wp, suma_world_stats* stats = nullptr) {
+    /* once into a buffer of a guessed size (what the last export needed, with headroom), again only if it was too small */
+    suma_world_stats st;
+    std::vector<suma_world_surfel> out;
+    uint32_t cap = world_capacity_ > 65536u ? world_capacity_ : 65536u;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      void* d = nullptr;
+      check(ctx_.get(), suma_device_alloc(ctx_.get(), (uint64_t)cap * sizeof(suma_world_surfel), &d), "SurfelMap::exportWorld");
+      int rc = suma_map_export_world(ctx_.get(), &wp, (suma_world_surfel*)d, cap, &st);
+      const bool fits = rc == SUMA_OK && st.n_out <= cap;
+      if (fits) {
+        out.resize(st.n_out);
+        if (st.n_out) rc = suma_device_download(ctx_.get(), out.data(), d, (uint64_t)st.n_out * sizeof(suma_world_surfel));
+      }
+      suma_device_free(ctx_.get(), d);
+      check(ctx_.get(), rc, "SurfelMap::exportWorld");
+      if (fits) break;
+      if (attempt) throw std::runtime_error("SurfelMap::exportWorld: the map changed between two exports");
+      cap = st.n_out;
+    }
+    world_capacity_ = st.n_out + st.n_out / 4;
+    if (stats) *stats = st;
+    return out;
+  }
 
  private:
   std::shared_ptr<Frame> borrowed(int which) {
     return std::make_shared<Frame>(ctx_, suma_map_frame(ctx_.get(), which));
   }
   Context& ctx_;
+  uint32_t world_capacity_ = 0; /* exportWorld's next buffer size, in records */
 };
 
 /* src/core/SurfelMapping.h: the per-scan sequencing (SurfelMapping.cpp:175-210) on the scan pipeline of the library --

@@ -467,6 +467,53 @@ void suma_draw_params_default(suma_draw_params* dp);
  *   message and launch nothing. */
 int suma_map_draw(suma_ctx* ctx, const suma_draw_params* dp, void* d_rgba8, int32_t* d_ids);
 
+/* ---- the whole surfel map in the world frame: the active map and every parked submap tile, filtered, optionally fused
+ *      to one record per voxel with a label vote (k_world.hip states the specification; tests/world_shim.c restates it
+ *      on the host, and the export equals it byte for byte). */
+typedef struct suma_world_surfel {   /* 48 bytes */
+  float x, y, z, radius;             /* world frame */
+  float nx, ny, nz, confidence;
+  uint32_t label;                    /* 0 .. 259 */
+  float prob;
+  uint32_t timestamp;                /* last update (voxel mode: the latest of the members) */
+  uint32_t support;                  /* source surfels behind this record; 1 without voxel fusion */
+} suma_world_surfel;
+
+typedef struct suma_world_params {
+  float voxel_size;                  /* 0: one record per surfel; > 0: one record per occupied voxel (metres) */
+  float min_confidence;              /* keep iff confidence > min_confidence; default -INFINITY (a NaN confidence never passes) */
+  uint8_t keep_label[SUMA_DRAW_COLORS]; /* keep iff keep_label[label] != 0; default all 1 */
+} suma_world_params;
+
+typedef struct suma_world_stats {
+  uint32_t n_active, n_tiles, n_parked;   /* sources: active surfels, non-empty parked tiles, their surfels */
+  uint32_t n_passed;                      /* after the confidence and label filters */
+  uint32_t n_dropped;                     /* passed, but world position non-finite or (voxel mode) outside the grid */
+  uint32_t n_out;                         /* records the export has in total (may exceed capacity) */
+} suma_world_stats;
+
+void suma_world_params_default(suma_world_params* wp);
+/* the (i, j) of every parked tile that holds records, ascending by (i, then j), as pairs ij[2 k], ij[2 k + 1]; *n = how
+ * many exist (the first min(*n, capacity) are written; ij may be NULL when capacity is 0) */
+int suma_map_cached_tiles(suma_ctx* ctx, int32_t* ij, uint32_t capacity, uint32_t* n);
+/* suma_map_export_world: the source sequence (the active map in buffer order, then every non-empty parked tile ascending
+ *   by (i, j), each in its stored order) taken to the world frame through the pose table, on the ctx stream, behind the
+ *   last update / upload / update_poses.  Writes the first min(n_out, capacity) records to the DEVICE buffer d_out (may be
+ *   NULL when capacity is 0: a size query) and fills *stats; SUMA_OK even when n_out > capacity (suma_map_download's
+ *   convention).  Blocking, twice: it reads the map's counters and the tiles' slots to size its launches (the sorts take
+ *   their size on the host), and waits for the result to fill *stats.
+ *   Like suma_map_draw it leaves the map, the pose table, the cache arena, every counter and the render de-duplication
+ *   untouched.  Scratch, kept by the ctx and grown by its one rule: 8 bytes per source surfel with voxel_size == 0,
+ *   48 bytes with voxel_size > 0 (a 16-byte vote record and the double buffers of the two sorts: keys 2 x 8, labels
+ *   2 x 4, indices 2 x 4), plus the sorts' histograms (they sort in place in those double buffers and take no copy of
+ *   their input) and 16 bytes per parked tile.  Two calls on the same state give the same bytes.  A map that an
+ *   overflow of max_surfels or of the cache arena has truncated is exported, and SUMA_ERR_CAPACITY returned, as the
+ *   downloads do.
+ *   A NULL wp or stats, a negative / NaN / infinite voxel_size, a NaN min_confidence and a NULL d_out with capacity > 0
+ *   return SUMA_ERR_INVALID with a message and launch nothing. */
+int suma_map_export_world(suma_ctx* ctx, const suma_world_params* wp, suma_world_surfel* d_out, uint32_t capacity,
+                          suma_world_stats* stats);
+
 /* ---- device scratch for callers that keep scans resident in HBM (bench, replay) */
 int suma_device_alloc(suma_ctx* ctx, uint64_t bytes, void** d_ptr);
 int suma_device_free(suma_ctx* ctx, void* d_ptr);

@@ -26,7 +26,7 @@ import numpy as np
 
 from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX_LIGHTS, SURFEL_DTYPE, DrawParams,
                     IcpStats, LoopParams, LoopStatus, PosegraphParams, PosegraphStats, SemanticKnnParams,
-                    SemanticParams, SumaParams)
+                    SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -242,6 +242,10 @@ def lib():
     L.suma_pipeline_begin_scan_scores_knn.argtypes = [vp, sp, kp, vp, vp, C.c_int, vp, vp, u32, vp]
     L.suma_pipeline_process_scan_scores_knn.argtypes = [vp, sp, kp, vp, vp, C.c_int, vp, vp, u32, vp, i32]
     L.suma_map_draw.argtypes = [vp, C.POINTER(DrawParams), vp, vp]
+    L.suma_world_params_default.argtypes = [C.POINTER(WorldParams)]
+    L.suma_world_params_default.restype = None
+    L.suma_map_cached_tiles.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_map_export_world.argtypes = [vp, C.POINTER(WorldParams), vp, u32, C.POINTER(WorldStats)]
     L.suma_device_alloc.argtypes = [vp, C.c_uint64, pp]
     L.suma_device_free.argtypes = [vp, vp]
     L.suma_device_upload.argtypes = [vp, vp, vp, C.c_uint64]
@@ -828,6 +832,52 @@ class SurfelMap:
         if n.value:
             self.ctx.check(self.ctx.L.suma_map_download_cached_tile(self.ctx.h, i, j, _ptr(out), n.value, C.byref(n)))
         return out
+
+    def cached_tiles(self):
+        """the (i, j) of every parked submap tile that holds records, ascending by (i, then j) (suma_map_cached_tiles)"""
+        n = C.c_uint32(0)
+        self.ctx.check(self.ctx.L.suma_map_cached_tiles(self.ctx.h, None, 0, C.byref(n)), "suma_map_cached_tiles")
+        ij = np.zeros((n.value, 2), dtype=np.int32)
+        if n.value:
+            self.ctx.check(self.ctx.L.suma_map_cached_tiles(self.ctx.h, _ptr(ij), n.value, C.byref(n)),
+                           "suma_map_cached_tiles")
+        return [(int(i), int(j)) for i, j in ij[:n.value]]
+
+    def export_world_device(self, params: WorldParams, d_out, capacity: int) -> WorldStats:
+        """suma_map_export_world into a caller-owned device buffer of ``capacity`` 48-byte records (``d_out`` may be None
+        with capacity 0: a size query); the stats tell how many records exist (n_out)"""
+        st = WorldStats()
+        self.ctx.check(self.ctx.L.suma_map_export_world(self.ctx.h, C.byref(params), _dev(d_out), capacity, C.byref(st)),
+                       "suma_map_export_world")
+        return st
+
+    def export_world(self, voxel_size: float = 0.0, min_confidence=None, keep_labels=None, stats: bool = False):
+        """The whole map -- active surfels and every parked tile -- in the world frame as WORLD_SURFEL_DTYPE records:
+        one per surfel with ``confidence > min_confidence`` and a label in ``keep_labels`` (None: all), or with
+        ``voxel_size > 0`` one per occupied voxel (the most confident member, a weighted label vote, the member count
+        in ``support``).  Computed on the device (k_world.hip states the rules).  ``stats=True``: (records, dict)."""
+        wp = WorldParams.defaults(voxel_size, min_confidence, keep_labels)
+        L, h = self.ctx.L, self.ctx.h
+        # the export runs once into a buffer of a guessed size (what the last export of this map needed, with headroom),
+        # and a second time only when that was too small
+        cap = max(int(getattr(self, "_world_capacity", 0)), 1 << 16)
+        for attempt in range(2):
+            d = C.c_void_p()
+            self.ctx.check(L.suma_device_alloc(h, cap * WORLD_SURFEL_DTYPE.itemsize, C.byref(d)), "suma_device_alloc")
+            try:
+                st = self.export_world_device(wp, d.value, cap)
+                if st.n_out <= cap:
+                    out = np.zeros(st.n_out, dtype=WORLD_SURFEL_DTYPE)
+                    if st.n_out:
+                        self.ctx.check(L.suma_device_download(h, _ptr(out), d, out.nbytes), "suma_device_download")
+                    break
+            finally:
+                L.suma_device_free(h, d)
+            if attempt:
+                raise SumaError("suma_map_export_world: the map changed between two exports")
+            cap = st.n_out
+        self._world_capacity = st.n_out + st.n_out // 4
+        return (out, st.as_dict()) if stats else out
 
     def counts(self):
         """(S' survivors of K9, D new surfels of K10, surfels parked in submap caches, submap origin)"""

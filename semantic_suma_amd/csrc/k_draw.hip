@@ -63,6 +63,7 @@
 #include <cstring>
 
 #include "suma_internal.h"
+#include "draw_vertex.h"
 
 #define DRAW_THREADS 256
 #define DRAW_LANE_TESTS 64 /* a quad with more pixel tests than this goes to the block-cooperative queue */
@@ -103,35 +104,11 @@ struct dvtx {
   float z, iw, su, sv;
 };
 
-SDEV bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 SDEV v3 nrm3(v3 a) { return divs3(a, len3(a)); }
-SDEV float4 mat_vec(const float* m, float4 v) {
-  return f4(SDEV_FMA(m[12], v.w, SDEV_FMA(m[8], v.z, SDEV_FMA(m[4], v.y, m[0] * v.x))),
-            SDEV_FMA(m[13], v.w, SDEV_FMA(m[9], v.z, SDEV_FMA(m[5], v.y, m[1] * v.x))),
-            SDEV_FMA(m[14], v.w, SDEV_FMA(m[10], v.z, SDEV_FMA(m[6], v.y, m[2] * v.x))),
-            SDEV_FMA(m[15], v.w, SDEV_FMA(m[11], v.z, SDEV_FMA(m[7], v.y, m[3] * v.x))));
-}
 SDEV uint32_t unorm8(float x) {
   x = (x > 0.0f) ? x : 0.0f;
   x = (x < 1.0f) ? x : 1.0f;
   return (uint32_t)__builtin_rintf(x * 255.0f);
-}
-
-/* draw_surfels.vert: p = M * (x, y, z, 1), n = M * (n, 0) with M = poses[int(count)] */
-SDEV void draw_vertex(const DrawArgs& a, const float4& s0, const float4& s1, float count, float4* p, float4* n) {
-  const uint32_t k = (count >= 0.0f) ? ((count < (float)a.n_poses) ? (uint32_t)(int32_t)count : a.n_poses - 1u) : 0u;
-  const float4* src = reinterpret_cast<const float4*>(a.poses + 16 * (size_t)k);
-  float M[16];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const float4 col = src[c];
-    M[4 * c] = col.x;
-    M[4 * c + 1] = col.y;
-    M[4 * c + 2] = col.z;
-    M[4 * c + 3] = col.w;
-  }
-  *p = mat_vec(M, f4(s0.x, s0.y, s0.z, 1.0f));
-  *n = mat_vec(M, f4(s1.x, s1.y, s1.z, 0.0f));
 }
 
 /* draw_surfels.geom up to the four clip-space corners; false: the surfel emits nothing */
@@ -139,7 +116,7 @@ SDEV bool quad_setup(const DrawArgs& a, uint32_t id, cvtx cv[4]) {
   const float4* sf = reinterpret_cast<const float4*>(a.surfels) + 4 * (size_t)id;
   const float4 s0 = sf[0], s1 = sf[1], s2 = sf[2], s3 = sf[3];
   float4 p, n;
-  draw_vertex(a, s0, s1, s2.w, &p, &n);
+  draw_vertex(a.poses, a.n_poses, s0, s1, s2.w, &p, &n);
   const float c = s1.w;
   float radius = s0.w, alpha = 1.0f;
   bool valid = (c > a.conf) || !a.use_stability;
@@ -413,7 +390,7 @@ SDEV uint32_t draw_shade(const DrawArgs& a, const ShadeArgs& sh, uint32_t id) {
   const float4* sf = reinterpret_cast<const float4*>(a.surfels) + 4 * (size_t)id;
   const float4 s0 = sf[0], s1 = sf[1], s2 = sf[2], s3 = sf[3];
   float4 p, n;
-  draw_vertex(a, s0, s1, s2.w, &p, &n);
+  draw_vertex(a.poses, a.n_poses, s0, s1, s2.w, &p, &n);
   const float c = s1.w;
   const v3 pp = mk3(p.x, p.y, p.z), nn = mk3(n.x, n.y, n.z);
   if (a.mode == 1) {

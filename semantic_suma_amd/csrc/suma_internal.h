@@ -83,6 +83,12 @@ struct DevState {
   uint32_t pad[4];
 };
 
+/* one stretch of the world export's source sequence: count records at base, the first with source index start */
+struct WorldSpan {
+  const suma_surfel* base;
+  uint32_t start, count;
+};
+
 /* one cached submap tile in the device arena */
 struct CacheSlot {
   uint32_t offset, count;
@@ -232,6 +238,13 @@ struct suma_ctx {
    * resolve) and the large-quad queue, max_surfels ids + its counter (left at 0) */
   DevBuf<unsigned long long> draw_zbuf;
   DevBuf<uint32_t> draw_queue;
+  /* suma_map_export_world (k_world.hip), allocated on first use: the span table of the source sequence, the per-source
+   * scratch (8 bytes a source surfel, 48 with voxel fusion), the library sort / scan's temporary storage (histograms and
+   * partial sums: the sorts run in double buffers inside the scratch), the counters */
+  DevBuf<struct WorldSpan> world_spans;
+  DevBuf<char> world_scratch, world_tmp;
+  DevBuf<uint32_t> world_counters;
+  PinnedBuf<uint32_t> world_counters_h;
 
   /* ICP */
   const suma_frame *icp_current, *icp_model;
@@ -370,6 +383,8 @@ int pipeline_finish_scan(suma_pipeline* s, int r, int32_t fixed_iterations, bool
 hipStream_t pipeline_input_stream(suma_pipeline* s);
 /* sets c->err and returns code */
 int fail(suma_ctx* c, int code, const std::string& msg);
+/* the overflow bits of the counters last read into c->h_ds: SUMA_OK, or the error every download reports (sets c->err) */
+int check_overflow(suma_ctx* c);
 /* k_semantic.hip: parameter check of the semantic entries (sets c->err) */
 int semantic_check(suma_ctx* c, const suma_semantic_params* sp);
 /* the scan input of the pipeline's scores entries: the phase check, sem_labels / sem_probs for n points and the wait

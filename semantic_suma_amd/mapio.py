@@ -1,0 +1,86 @@
+"""Files of an exported map: SurfelMap.export_world's records as a binary little-endian PLY point cloud.
+
+    write_ply(path, world_surfels, color_map=None)   x y z nx ny nz radius confidence label prob support + red green blue
+    read_ply(path) -> (world_surfels, rgb)           the round trip (timestamp, which the file does not carry, reads 0)
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import kitti
+from .types import WORLD_SURFEL_DTYPE
+
+# the PLY vertex: name, PLY type, numpy type
+_PLY_FIELDS = [("x", "float", "<f4"), ("y", "float", "<f4"), ("z", "float", "<f4"),
+               ("nx", "float", "<f4"), ("ny", "float", "<f4"), ("nz", "float", "<f4"),
+               ("radius", "float", "<f4"), ("confidence", "float", "<f4"), ("label", "uint", "<u4"),
+               ("prob", "float", "<f4"), ("support", "uint", "<u4"),
+               ("red", "uchar", "u1"), ("green", "uchar", "u1"), ("blue", "uchar", "u1")]
+_PLY_DTYPE = np.dtype([(n, t) for n, _, t in _PLY_FIELDS])
+_PLY_NP = {"float": "<f4", "float32": "<f4", "uint": "<u4", "uint32": "<u4", "uchar": "u1", "uint8": "u1",
+           "int": "<i4", "int32": "<i4", "double": "<f8", "float64": "<f8", "ushort": "<u2", "uint16": "<u2",
+           "short": "<i2", "int16": "<i2", "char": "i1", "int8": "i1"}
+
+
+def write_ply(path: str, world_surfels: np.ndarray, color_map=None) -> None:
+    """``world_surfels``: WORLD_SURFEL_DTYPE records; ``color_map``: uint8 [260, 3] RGB by label id (default
+    kitti.semantic_color_map()); a label outside the map is black"""
+    ws = np.ascontiguousarray(world_surfels, dtype=WORLD_SURFEL_DTYPE)
+    cmap = np.asarray(kitti.semantic_color_map() if color_map is None else color_map, dtype=np.uint8).reshape(-1, 3)
+    v = np.zeros(ws.shape[0], dtype=_PLY_DTYPE)
+    for name, _, _ in _PLY_FIELDS[:-3]:
+        v[name] = ws[name]
+    inside = ws["label"] < cmap.shape[0]
+    rgb = np.where(inside[:, None], cmap[np.where(inside, ws["label"], 0)], 0).astype(np.uint8)
+    v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    header = ["ply", "format binary_little_endian 1.0", "comment semantic surfel map, world frame",
+              f"element vertex {ws.shape[0]}"]
+    header += [f"property {t} {n}" for n, t, _ in _PLY_FIELDS] + ["end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(v.tobytes())
+
+
+def read_ply(path: str):
+    """-> (WORLD_SURFEL_DTYPE records, uint8 [n, 3] RGB) of a binary little-endian PLY whose vertex element holds scalar
+    properties (any order; those write_ply does not know are skipped, those missing read 0)"""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        n, props, in_vertex, fmt = 0, [], False, None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: no end_header")
+            w = line.decode("ascii").split()
+            if not w or w[0] == "comment":
+                continue
+            if w[0] == "end_header":
+                break
+            if w[0] == "format":
+                fmt = w[1]
+            elif w[0] == "element":
+                in_vertex = w[1] == "vertex"
+                if in_vertex:
+                    n = int(w[2])
+                elif not props:
+                    raise ValueError(f"{path}: element {w[1]} in front of the vertices")
+            elif w[0] == "property" and in_vertex:
+                if w[1] == "list" or w[1] not in _PLY_NP:
+                    raise ValueError(f"{path}: vertex property {' '.join(w[1:])} is not a known scalar")
+                props.append((w[2], _PLY_NP[w[1]]))
+        if fmt != "binary_little_endian":
+            raise ValueError(f"{path}: format {fmt!r} (only binary_little_endian is read)")
+        dt = np.dtype(props)
+        v = np.frombuffer(f.read(n * dt.itemsize), dtype=dt)
+    if v.shape[0] != n:
+        raise ValueError(f"{path}: {v.shape[0]} of {n} vertices")
+    ws = np.zeros(n, dtype=WORLD_SURFEL_DTYPE)
+    for name in WORLD_SURFEL_DTYPE.names:
+        if name in dt.names:
+            ws[name] = v[name]
+    rgb = np.zeros((n, 3), dtype=np.uint8)
+    for k, name in enumerate(("red", "green", "blue")):
+        if name in dt.names:
+            rgb[:, k] = v[name]
+    return ws, rgb

@@ -91,6 +91,39 @@ class DrawParams(C.Structure):
     ]
 
 
+# numpy view of the 48-byte world-frame record (``struct suma_world_surfel``, SurfelMap.export_world)
+WORLD_SURFEL_DTYPE = np.dtype([
+    ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("radius", "<f4"),
+    ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("confidence", "<f4"),
+    ("label", "<u4"), ("prob", "<f4"), ("timestamp", "<u4"), ("support", "<u4"),
+])
+assert WORLD_SURFEL_DTYPE.itemsize == 48
+
+
+class WorldParams(C.Structure):
+    """``struct suma_world_params``: voxel size (0: one record per surfel), confidence and label filters of
+    SurfelMap.export_world; ``WorldParams.defaults()`` = suma_world_params_default"""
+    _fields_ = [("voxel_size", f32), ("min_confidence", f32), ("keep_label", C.c_uint8 * DRAW_COLORS)]
+
+    @classmethod
+    def defaults(cls, voxel_size: float = 0.0, min_confidence=None, keep_labels=None) -> "WorldParams":
+        """``keep_labels``: None (all), or the label ids to keep"""
+        p = cls(voxel_size=voxel_size, min_confidence=float("-inf") if min_confidence is None else min_confidence)
+        keep = set(range(DRAW_COLORS)) if keep_labels is None else {int(l) for l in keep_labels}
+        for l in range(DRAW_COLORS):
+            p.keep_label[l] = 1 if l in keep else 0
+        return p
+
+
+class WorldStats(C.Structure):
+    """``struct suma_world_stats``: what one export read, filtered, dropped and produced"""
+    _fields_ = [("n_active", u32), ("n_tiles", u32), ("n_parked", u32), ("n_passed", u32), ("n_dropped", u32),
+                ("n_out", u32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # SurfelMap's constructor (SurfelMap.cpp:195-229): the value each uniform of draw_surfels_ is left with.  Only light 0
 # is used (num_lights = 1); lights 1-4 are the "evenly distributed sun light" it also sets.
 DRAW_LIGHTS = [

@@ -1,0 +1,89 @@
+#!/usr/bin/env python
+"""The finished map as a point cloud: runs a synthetic sequence (semantic_suma_amd/synth.py) or a KITTI directory
+(velodyne/*.bin, optionally labels/*.label) through SurfelMapping, optionally closing loops, then exports the whole map
+-- active surfels and every parked submap tile -- in the world frame on the GPU (SurfelMap.export_world,
+csrc/k_world.hip) and writes it as a binary PLY (semantic_suma_amd/mapio.py).  Prints the export's stats and the wall
+time of the export alone; --compare also times the host route (getAllSurfels + per-tile downloads + a numpy transform).
+Needs a GPU.
+    python tools/export_map.py --out map.ply [--scans 40] [--kitti sequences/08] [--voxel 0.2] [--min-confidence 0]
+                               [--close-loops] [--width 2048] [--compare]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from semantic_suma_amd import core, kitti, mapio, synth  # noqa: E402
+from semantic_suma_amd.types import SURFEL_DTYPE, LoopParams, params_with_size  # noqa: E402
+
+
+def scans(args):
+    if args.kitti:
+        bins = sorted(f for f in os.listdir(os.path.join(args.kitti, "velodyne")) if f.endswith(".bin"))[:args.scans]
+        for b in bins:
+            pts = kitti.read_velodyne(os.path.join(args.kitti, "velodyne", b))
+            lp = os.path.join(args.kitti, "labels", b[:-4] + ".label")
+            lab, prob = kitti.read_labels(lp, pts.shape[0]) if os.path.exists(lp) else (None, None)
+            yield pts, lab, prob
+    else:
+        for k in range(args.scans):
+            pts, lab, prob, _ = synth.generate_scan(k, n_azimuth=args.width, height=64)
+            yield pts, lab, prob
+
+
+def host_route(smap, max_poses):
+    """what a consumer had to do before: download every source record and redo the pose lookup in numpy (fp64 here: a
+    host has no reason to restate the fma chain) -- the positions only, no filter, no voxels"""
+    parts = [smap.getAllSurfels()]
+    for i, j in smap.cached_tiles():
+        parts.append(np.ascontiguousarray(smap.cached_tile(i, j)).view(SURFEL_DTYPE).reshape(-1))
+    s = np.concatenate(parts)
+    table = np.tile(np.eye(4), (max_poses, 1, 1))
+    poses = smap.poses()
+    table[:len(poses)] = poses
+    c = s["count"]
+    k = np.where(c >= 0, np.where(c < max_poses, np.nan_to_num(c, nan=0.0), max_poses - 1), 0).astype(np.int64)
+    M = table[k]
+    p = np.einsum("nij,nj->ni", M[:, :3, :3], np.stack([s["x"], s["y"], s["z"]], 1).astype(np.float64)) + M[:, :3, 3]
+    return p.astype(np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="map.ply")
+    ap.add_argument("--scans", type=int, default=40)
+    ap.add_argument("--kitti", default=None, help="a sequences/XX directory")
+    ap.add_argument("--width", type=int, default=2048, help="data image width (64 rows)")
+    ap.add_argument("--voxel", type=float, default=0.0, help="voxel size in metres; 0: one record per surfel")
+    ap.add_argument("--min-confidence", type=float, default=None)
+    ap.add_argument("--close-loops", action="store_true")
+    ap.add_argument("--repeat", type=int, default=3, help="timed exports (the first one allocates the scratch)")
+    ap.add_argument("--compare", action="store_true", help="also time the host route")
+    args = ap.parse_args()
+    p = params_with_size(args.width, 64)
+    pipe = core.SurfelMapping(p, loop_params=LoopParams.defaults() if args.close_loops else None)
+    for pts, lab, prob in scans(args):
+        pipe.processScan(pts, lab, prob)
+    smap = pipe.map
+    times = []
+    for _ in range(max(1, args.repeat)):
+        t = time.perf_counter()
+        world, st = smap.export_world(voxel_size=args.voxel, min_confidence=args.min_confidence, stats=True)
+        times.append(time.perf_counter() - t)
+    mapio.write_ply(args.out, world)
+    res = dict(stats=st, voxel_size=args.voxel, export_wall_ms=[round(1e3 * x, 3) for x in times], out=args.out,
+               bytes=os.path.getsize(args.out))
+    if args.compare:
+        t = time.perf_counter()
+        pts = host_route(smap, p.max_poses)
+        res["host_route_wall_ms"] = round(1e3 * (time.perf_counter() - t), 3)
+        res["host_route_points"] = int(pts.shape[0])
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
