@@ -13,6 +13,7 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -440,6 +441,36 @@ class SurfelMapping {
   }
   /* SurfelMapping::reset(), SurfelMapping.cpp:131-169 */
   void reset() { chk(suma_pipeline_reset(s_), "SurfelMapping::reset"); }
+  /* ---- checkpoint / resume (suma_pipeline_checkpoint_save / _load): nothing in the reference to mirror -- its
+   *      Posegraph::save / load are empty (Posegraph.cpp:118-119) and its tile cache cannot be written out.  Between
+   *      two processScan calls only.  The file is written under a temporary name and renamed, so `path` never holds
+   *      half an image; loadCheckpoint needs a SurfelMapping made with the parameters the image was saved with
+   *      (suma_checkpoint_params reads them from an image) and leaves it untouched when the image is refused. ---- */
+  void saveCheckpoint(const std::string& path) {
+    uint64_t need = 0, written = 0;
+    chk(suma_pipeline_checkpoint_size(s_, &need), "SurfelMapping::saveCheckpoint");
+    std::vector<char> image((size_t)need);
+    chk(suma_pipeline_checkpoint_save(s_, image.data(), image.size(), &written), "SurfelMapping::saveCheckpoint");
+    const std::string tmp = path + ".tmp";
+    FILE* f = std::fopen(tmp.c_str(), "wb");
+    if (!f) throw std::runtime_error("SurfelMapping::saveCheckpoint: cannot write " + tmp);
+    const bool ok = std::fwrite(image.data(), 1, (size_t)written, f) == (size_t)written;
+    if (std::fclose(f) != 0 || !ok || std::rename(tmp.c_str(), path.c_str()) != 0) {
+      std::remove(tmp.c_str());
+      throw std::runtime_error("SurfelMapping::saveCheckpoint: cannot write " + path);
+    }
+  }
+  void loadCheckpoint(const std::string& path) {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) throw std::runtime_error("SurfelMapping::loadCheckpoint: cannot read " + path);
+    std::vector<char> image;
+    char block[65536];
+    for (size_t n; (n = std::fread(block, 1, sizeof(block), f)) > 0;) image.insert(image.end(), block, block + n);
+    const bool ok = std::ferror(f) == 0;
+    std::fclose(f);
+    if (!ok) throw std::runtime_error("SurfelMapping::loadCheckpoint: cannot read " + path);
+    chk(suma_pipeline_checkpoint_load(s_, image.data(), image.size()), "SurfelMapping::loadCheckpoint");
+  }
   /* ---- device parts of checkLoopClosure ---- */
   /* :546-574, a tracked closure verified again; on success the caller sets currentPose_old_ = out.pose_old (:581) */
   suma_loop_track trackLoopClosure(double min_valid = 0.2, double max_outlier = 0.85, double max_diff = 0.1) {

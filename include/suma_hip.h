@@ -170,7 +170,8 @@ int suma_map_download(suma_ctx* ctx, suma_surfel* host, uint32_t cap, uint32_t* 
  * dropped).  INTEGRATION.md shows the hipGraphicsGLRegisterBuffer recipe. */
 int suma_map_export_surfels(suma_ctx* ctx, void** d_ptr, uint32_t* n);
 int suma_map_export_data_surfels(suma_ctx* ctx, void** d_ptr, uint32_t* first, uint32_t* n_data);
-/* checkpoint / resume: replace the active map */
+/* replace the active map alone (tests, map surgery); a whole session is saved and resumed with
+ * suma_pipeline_checkpoint_save / _load below */
 int suma_map_upload(suma_ctx* ctx, const suma_surfel* host, uint32_t n, uint32_t timestamp);
 /* intermediates of the last update, for stage-by-stage parity tests */
 int suma_map_download_index_map(suma_ctx* ctx, uint32_t* host);      /* P, surfel id + 1 (uint32, not float) */
@@ -672,6 +673,70 @@ int suma_pipeline_trajectory_distances(const suma_pipeline* s, float* out, uint3
 int32_t suma_loop_find_candidate(const double* poses16, const float* trajectory_distances, uint32_t timestamp,
                                  const double current_pose[16], float radius, float min_trajectory_distance,
                                  int32_t delta_timestamp);
+
+/* ---- checkpoint / resume of a whole pipeline: one canonical byte image of the logical state between two scans -- map,
+ *      parked tiles, pose table, the pipeline's poses and last frame, loop-closing state, pose graph, an optimisation in
+ *      flight -- such that a pipeline that loads it continues as the uninterrupted run does, to the bit (DESIGN.md 11;
+ *      csrc/k_checkpoint.hip states the image, csrc/checkpoint_format.h the container).  The reference has nothing like
+ *      it: Posegraph::save / load are empty stubs (Posegraph.cpp) and its tile cache lives in host RAM only.
+ *      The surfel sections are packed and digested on the device (kc_pack), verified there before a load writes
+ *      anything (kc_verify), and unpacked into a compact arena (kc_unpack).  All entries are blocking and run on the ctx
+ *      stream; none is on the scan path.  The staged image (a device block as large as the largest image saved or
+ *      loaded so far) stays allocated for the next save and is given back only when the ctx is destroyed
+ *      (suma_pipeline_destroy); suma_pipeline_reset keeps it.  A process that saves once and needs the memory back
+ *      has no entry for that.
+ *      (Kept here, not in suma_types.h, for the reason given at suma_semantic_params.) */
+#define SUMA_CHECKPOINT_VERSION 1u
+#define SUMA_CHECKPOINT_MAX_SECTIONS 16
+enum { /* section ids, in image order */
+  SUMA_CKPT_PARAMS = 1, SUMA_CKPT_PIPELINE, SUMA_CKPT_MAP_STATE, SUMA_CKPT_POSES, SUMA_CKPT_ACTIVE, SUMA_CKPT_FRAME,
+  SUMA_CKPT_TILE_DIR, SUMA_CKPT_TILES, SUMA_CKPT_LOOP, SUMA_CKPT_GRAPH, SUMA_CKPT_OPT
+};
+typedef struct suma_checkpoint_section {
+  uint32_t id, reserved;
+  uint64_t bytes;  /* payload bytes, without the padding to 64 */
+  uint64_t digest; /* as the directory states it */
+} suma_checkpoint_section;
+/* a struct tag only (no typedef): the entry that fills it has the same name */
+struct suma_checkpoint_info {
+  uint32_t version;
+  uint32_t timestamp;  /* scans processed */
+  uint32_t n_active;   /* records of the active map */
+  uint32_t n_tiles;    /* non-empty parked tiles */
+  uint64_t n_parked;   /* their records */
+  uint32_t n_nodes, n_edges; /* pose graph; 0 without LOOP */
+  int32_t has_loop, has_opt;
+  uint32_t n_sections, reserved;
+  uint64_t total_bytes;
+  suma_checkpoint_section sections[SUMA_CHECKPOINT_MAX_SECTIONS];
+};
+/* the size the image would have now.  Only between scans (SUMA_ERR_INVALID otherwise, as the save). */
+int suma_pipeline_checkpoint_size(suma_pipeline* s, uint64_t* bytes);
+/* writes the image to host_dst; *written = its size.  SUMA_ERR_INVALID between suma_pipeline_begin_scan and
+ * suma_pipeline_update_map, or while a scan staged with suma_pipeline_prefetch_scan is pending; SUMA_ERR_CAPACITY with
+ * the needed size in *written when capacity is too small (nothing is written; capacity 0 is a size query), or when the
+ * map has overflowed one of its capacities.  Resolves a pending statistics record and joins a running pose-graph
+ * optimisation; changes nothing else: a pipeline that saves computes what one that never does computes.  A save refused
+ * with SUMA_ERR_INVALID has not joined the optimisation; one refused with SUMA_ERR_CAPACITY has, as the size it reports
+ * needs the optimisation's result to be final. */
+int suma_pipeline_checkpoint_save(suma_pipeline* s, void* host_dst, uint64_t capacity, uint64_t* written);
+/* replaces the state of s by the image's.  The image is parsed and bounds-checked on the host, then staged and its
+ * section digests verified on the device, BEFORE anything of the pipeline is written: a refused load leaves the pipeline
+ * exactly as it was.  SUMA_ERR_INVALID: wrong phase, malformed image, unsupported version, digest mismatch (the message
+ * names the section), parameters that differ from the pipeline's (the message names the first such field);
+ * SUMA_ERR_CAPACITY: n_active > max_surfels, parked records beyond the arena, more tiles than slots, timestamp >
+ * max_poses.  A successful load joins and drops a running optimisation, drains the ingest, resets what
+ * suma_pipeline_reset resets, installs the state, clears every de-duplication cache, and switches loop closing on with
+ * the stored parameters if the image has a LOOP section, off if not (a graph handle borrowed before is dead). */
+int suma_pipeline_checkpoint_load(suma_pipeline* s, const void* image, uint64_t bytes);
+/* host only, no device: parses an image (the same checks as the load's first step) and reports what it holds; on failure
+ * the text is suma_last_error(NULL) */
+int suma_checkpoint_info(const void* image, uint64_t bytes, struct suma_checkpoint_info* out);
+/* the PARAMS section of a valid image (suma_pipeline_create with them gives a pipeline that can load it) */
+int suma_checkpoint_params(const void* image, uint64_t bytes, suma_params* out);
+/* host only: the digest of a payload read as little-endian 64-bit words w[k], a shorter tail zero-extended:
+ * sum over k of (w[k] + 0x9E3779B97F4A7C15) * (2 k + 1) mod 2^64 */
+uint64_t suma_checkpoint_digest(const void* payload, uint64_t bytes);
 
 /* ---- per-kernel timing (rv::Stopwatch / SurfelMapping::Stats, SurfelMapping.cpp:183-207):
  *      on = 1: every kernel group is bracketed by HIP events on the ctx stream; on = 2: only the

@@ -26,7 +26,7 @@ import numpy as np
 
 from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX_LIGHTS, SURFEL_DTYPE, DrawParams,
                     IcpStats, LoopParams, LoopStatus, PosegraphParams, PosegraphStats, SemanticKnnParams,
-                    SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats)
+                    SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats, CheckpointInfo)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -252,6 +252,14 @@ def lib():
     L.suma_profile_enable.argtypes = [vp, C.c_int]
     L.suma_profile_reset.argtypes = [vp]
     L.suma_profile_get.argtypes = [vp, C.POINTER(KernelTime), u32]
+    u64p = C.POINTER(C.c_uint64)
+    L.suma_pipeline_checkpoint_size.argtypes = [vp, u64p]
+    L.suma_pipeline_checkpoint_save.argtypes = [vp, vp, C.c_uint64, u64p]
+    L.suma_pipeline_checkpoint_load.argtypes = [vp, vp, C.c_uint64]
+    L.suma_checkpoint_info.argtypes = [vp, C.c_uint64, C.POINTER(CheckpointInfo)]
+    L.suma_checkpoint_params.argtypes = [vp, C.c_uint64, C.POINTER(SumaParams)]
+    L.suma_checkpoint_digest.argtypes = [vp, C.c_uint64]
+    L.suma_checkpoint_digest.restype = C.c_uint64
     _LIB = L
     return L
 
@@ -1024,6 +1032,39 @@ def loop_find_candidate(poses, trajectory_distances, timestamp: int, current_pos
                                               delta_timestamp))
 
 
+def _image_bytes(path_or_bytes) -> bytes:
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        return bytes(path_or_bytes)
+    with open(path_or_bytes, "rb") as f:
+        return f.read()
+
+
+def checkpoint_info(path_or_bytes) -> dict:
+    """suma_checkpoint_info of an image (host only, no device): version, timestamp, n_active, tiles, parked records,
+    graph size, whether LOOP / OPT are present, and every section's id, bytes and digest"""
+    img = _image_bytes(path_or_bytes)
+    info = CheckpointInfo()
+    rc = lib().suma_checkpoint_info(img, len(img), C.byref(info))
+    if rc != 0:
+        raise SumaError(f"suma_checkpoint_info failed ({rc}): {lib().suma_last_error(None).decode()}")
+    return info.as_dict()
+
+
+def checkpoint_params(path_or_bytes) -> SumaParams:
+    """the suma_params an image was made with"""
+    img = _image_bytes(path_or_bytes)
+    p = SumaParams()
+    rc = lib().suma_checkpoint_params(img, len(img), C.byref(p))
+    if rc != 0:
+        raise SumaError(f"suma_checkpoint_params failed ({rc}): {lib().suma_last_error(None).decode()}")
+    return p
+
+
+def checkpoint_digest(payload) -> int:
+    payload = bytes(payload)
+    return lib().suma_checkpoint_digest(payload, len(payload))
+
+
 class SurfelMapping:
     """SurfelMapping::processScan (SurfelMapping.cpp:175-210).  processScan* run a scan in one call; beginScan /
     updatePose / updateMap are its phases.  With ``loop_params`` (types.LoopParams) the pipeline closes loops itself, as
@@ -1283,6 +1324,52 @@ class SurfelMapping:
     def reset(self):
         """SurfelMapping::reset (SurfelMapping.cpp:131-169)"""
         self.ctx.check(self.L.suma_pipeline_reset(self.h), "suma_pipeline_reset")
+
+    # ---- checkpoint / resume (suma_pipeline_checkpoint_*; the image is specified in csrc/k_checkpoint.hip)
+    def save(self, path=None) -> bytes:
+        """the canonical image of the pipeline's state between two scans; also written to ``path`` if given (to a
+        temporary name first, then renamed).  A pipeline that loads it continues as this one would, to the bit."""
+        n = C.c_uint64()
+        self.ctx.check(self.L.suma_pipeline_checkpoint_size(self.h, C.byref(n)), "suma_pipeline_checkpoint_size")
+        buf = np.empty(n.value, dtype=np.uint8)
+        self.ctx.check(self.L.suma_pipeline_checkpoint_save(self.h, _ptr(buf), n.value, C.byref(n)),
+                       "suma_pipeline_checkpoint_save")
+        img = buf[:n.value].tobytes()
+        if path is not None:
+            tmp = f"{path}.tmp"
+            with open(tmp, "wb") as f:
+                f.write(img)
+            os.replace(tmp, path)
+        return img
+
+    def load(self, path_or_bytes):
+        """replaces this pipeline's state by an image's (a path or the bytes).  Refused -- and the pipeline left as it
+        was -- unless the image is well formed, its digests hold and it was made with this pipeline's parameters.
+        Loop closing is switched on with the image's parameters if it holds a LOOP section, off if not."""
+        img = _image_bytes(path_or_bytes)
+        old, self.posegraph = self.posegraph, None
+        had = self.L.suma_pipeline_posegraph(self.h)
+        rc = self.L.suma_pipeline_checkpoint_load(self.h, img, len(img))
+        h = self.L.suma_pipeline_posegraph(self.h)
+        if old is not None:
+            if rc != 0 and h is not None and h == had:
+                self.posegraph = old  # refused before anything was written: the pipeline has kept its graph
+            else:
+                old.h = None
+        self.ctx.check(rc, "suma_pipeline_checkpoint_load")
+        self._staged = []
+        if h is not None:
+            g = Posegraph(self.device, handle=C.c_void_p(h))
+            g.borrowed = True
+            self.posegraph = g
+
+    @classmethod
+    def restore(cls, path_or_bytes, device: int = 0) -> "SurfelMapping":
+        """a new pipeline with the image's parameters, holding the image's state"""
+        img = _image_bytes(path_or_bytes)
+        pipe = cls(checkpoint_params(img), device=device)
+        pipe.load(img)
+        return pipe
 
     def minimizeHypotheses(self, starts, fixed_iterations: int = 0):
         """n Gauss-Newton chains as one batch against the rendered model, between beginScan and applyIncrement"""

@@ -1192,3 +1192,23 @@ const double* posegraph_device_poses(const suma_posegraph* g, uint32_t* n) {
   *n = g->n_dev;
   return g->X.p;
 }
+const double* posegraph_host_initial(const suma_posegraph* g, uint32_t* n) {
+  *n = (uint32_t)(g->initial.size() / 12);
+  return g->initial.data();
+}
+/* for a restored checkpoint (suma_loop.hip): the nodes as they were saved.  to_device: the graph is prepared and its
+ * stream synchronised, so that X holds `result` as it does behind suma_posegraph_optimize */
+int posegraph_install_nodes(suma_posegraph* g, const double* initial12, const double* result12, uint32_t n, bool to_device) {
+  if (!g || (n && (!initial12 || !result12))) return SUMA_ERR_INVALID;
+  if (n > g->node_cap) return pg_fail(g, SUMA_ERR_CAPACITY, "install_nodes: node capacity exceeded");
+  if (!finite_n(initial12, 12 * (size_t)n) || !finite_n(result12, 12 * (size_t)n))
+    return pg_fail(g, SUMA_ERR_INVALID, "install_nodes: non-finite pose");
+  g->initial.assign(initial12, initial12 + 12 * (size_t)n);
+  g->result.assign(result12, result12 + 12 * (size_t)n);
+  g->structure_dirty = true;
+  if (!to_device || n == 0) return SUMA_OK;
+  const int rc = pg_prepare(g);
+  if (rc != SUMA_OK) return rc;
+  PG_HIP(g, hipStreamSynchronize(g->stream));
+  return SUMA_OK;
+}

@@ -28,6 +28,10 @@ static thread_local std::string g_create_error;
 
 extern "C" const char* suma_version(void) { return "suma-hip 0.1 (gfx950)"; }
 extern "C" const char* suma_last_error(const suma_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
+int fail_without_ctx(int code, const std::string& msg) {
+  g_create_error = msg;
+  return code;
+}
 
 /* ---------------------------------------------------------------------------------------------
  * helpers

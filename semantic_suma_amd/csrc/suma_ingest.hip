@@ -342,6 +342,13 @@ void ingest_drain(suma_ctx* c) {
   for (auto& q : g->slot) q.consumed_valid = false;
 }
 
+uint32_t ingest_pending(suma_ctx* c) {
+  Ingest* g = c ? c->ingest : nullptr;
+  if (!g) return 0;
+  std::lock_guard<std::mutex> lk(g->mu);
+  return g->tail - g->head;
+}
+
 extern "C" int suma_pipeline_prefetch_scan(suma_pipeline* s, const suma_float4* points, const float* labels,
                                            const float* probs, uint32_t n) {
   if (!s || (n > 0 && !points)) return SUMA_ERR_INVALID;

@@ -245,6 +245,11 @@ struct suma_ctx {
   DevBuf<char> world_scratch, world_tmp;
   DevBuf<uint32_t> world_counters;
   PinnedBuf<uint32_t> world_counters_h;
+  /* suma_pipeline_checkpoint_save / _load (k_checkpoint.hip), allocated on first use: the staged image, the span table
+   * of kc_pack and one digest word per section */
+  DevBuf<char> ckpt_image;
+  DevBuf<struct WorldSpan> ckpt_spans;
+  DevBuf<unsigned long long> ckpt_digests;
 
   /* ICP */
   const suma_frame *icp_current, *icp_model;
@@ -383,6 +388,8 @@ int pipeline_finish_scan(suma_pipeline* s, int r, int32_t fixed_iterations, bool
 hipStream_t pipeline_input_stream(suma_pipeline* s);
 /* sets c->err and returns code */
 int fail(suma_ctx* c, int code, const std::string& msg);
+/* the same for entries without a ctx: the text suma_last_error(NULL) returns on this thread */
+int fail_without_ctx(int code, const std::string& msg);
 /* the overflow bits of the counters last read into c->h_ds: SUMA_OK, or the error every download reports (sets c->err) */
 int check_overflow(suma_ctx* c);
 /* k_semantic.hip: parameter check of the semantic entries (sets c->err) */
@@ -393,6 +400,8 @@ int semantic_scan_input(suma_pipeline* s, uint32_t n, void* producer_event, hipS
 /* suma_ingest.hip */
 void ingest_destroy(suma_ctx* c);
 void ingest_drain(suma_ctx* c);
+/* scans staged with suma_pipeline_prefetch_scan that have not been processed */
+uint32_t ingest_pending(suma_ctx* c);
 /* host scan -> pinned staging -> copy stream; *d_base = device block (points | labels | probs), *uploaded = the event the
  * consumer stream waits for, *slot = token for ingest_consumed */
 int ingest_stage_blocking(suma_ctx* c, const suma_float4* points, const float* labels, const float* probs, uint32_t n,
@@ -487,9 +496,21 @@ hipError_t launch_gate(suma_ctx* c, hipStream_t st, uint32_t word, uint32_t seq)
 /* makes the ctx stream wait for the pending preprocessing hand-off (one-wave gate kernel) */
 hipError_t flush_gate(suma_ctx* c);
 
+/* k_checkpoint.hip (the image and the kernels are specified there).  Spans are in units of 16 bytes. */
+hipError_t launch_kc_pack(suma_ctx* c, const WorldSpan* d_spans, uint32_t n_spans, uint32_t n_quads, void* d_dst,
+                          unsigned long long* d_digest);
+hipError_t launch_kc_verify(suma_ctx* c, const void* d_src, uint64_t bytes, unsigned long long* d_digest);
+/* counters: n_updated, n_kept_updated, n_data, n_kept_data */
+hipError_t launch_kc_unpack(suma_ctx* c, const void* d_tiles, uint32_t n_parked, const void* d_tile_dir, uint32_t n_tiles,
+                            uint32_t n_active, const uint32_t counters[4]);
+
 /* k_posegraph.hip: a graph's poses where they lie (12 doubles a node, R row-major | t) */
 const double* posegraph_host_poses(const suma_posegraph* g, uint32_t* n);
 const double* posegraph_device_poses(const suma_posegraph* g, uint32_t* n);
+const double* posegraph_host_initial(const suma_posegraph* g, uint32_t* n);
+/* replaces a graph's nodes by n nodes with these initial values and current estimates (12 doubles a node); to_device:
+ * also prepares the device side, so that posegraph_device_poses holds `result` (a restored optimisation result) */
+int posegraph_install_nodes(suma_posegraph* g, const double* initial12, const double* result12, uint32_t n, bool to_device);
 /* k_loop.hip: integrateLoopClosures' pose table (SurfelMapping.cpp:219-233) written on the ctx stream: rows < n_opt =
  * float(opt), rows n_opt .. n_opt + n_tail - 1 = float(difference * tail) */
 hipError_t launch_loop_integrate(suma_ctx* c, const double* d_opt12, uint32_t n_opt, const double* d_tail16,
@@ -501,6 +522,16 @@ int loop_odometry_edge(suma_pipeline* s);           /* SurfelMapping.cpp:461-471
 int loop_check(suma_pipeline* s);                   /* checkLoopClosure */
 void loop_destroy(suma_pipeline* s);                /* joins the worker, frees the graph */
 int loop_reset(suma_pipeline* s);                   /* the constructor's state */
+/* checkpoint (suma_checkpoint.hip): the LOOP / GRAPH / OPT payloads of checkpoint_format.h.  join: waits for a running
+ * optimisation; write: appends the payloads (opt stays empty when none is in flight); check: everything that can refuse
+ * the payloads, without touching the pipeline; install: on a pipeline whose loop closing has just been enabled with the
+ * stored parameters */
+void loop_ckpt_join(suma_pipeline* s);
+uint64_t loop_ckpt_sizes(const suma_pipeline* s, uint64_t* graph_bytes, uint64_t* opt_bytes);
+int loop_ckpt_write(suma_pipeline* s, std::vector<char>* loop, std::vector<char>* graph, std::vector<char>* opt);
+int loop_ckpt_check(suma_ctx* c, const char* loop, const char* graph, const char* opt, uint32_t timestamp,
+                    suma_loop_params* params);
+int loop_ckpt_install(suma_pipeline* s, const char* loop, const char* graph, const char* opt);
 
 /* host helper shared by api + pipeline */
 void rigid_inverse_f(const float* m, float* out);

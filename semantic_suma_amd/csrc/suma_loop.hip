@@ -571,3 +571,246 @@ extern "C" int suma_pipeline_check_loop_closure(suma_pipeline* s) {
   }
   return loop_check(s);
 }
+
+/* ---- checkpoint: the LOOP / GRAPH / OPT payloads (checkpoint_format.h; k_checkpoint.hip states the image) ---- */
+#include "checkpoint_format.h"
+
+static_assert(sizeof(suma_loop_params) % 8 == 0, "the LOOP payload keeps its doubles aligned");
+
+namespace {
+
+template <class T>
+void put(std::vector<char>* v, const T* p, size_t n = 1) {
+  const char* b = reinterpret_cast<const char*>(p);
+  v->insert(v->end(), b, b + n * sizeof(T));
+}
+void put_candidates(std::vector<char>* v, const std::vector<LoopCandidate>& cs) {
+  for (const LoopCandidate& q : cs) {
+    ckpt::Candidate o;
+    o.from = q.from, o.to = q.to;
+    memcpy(o.rel_pose, q.rel_pose, sizeof(o.rel_pose));
+    put(v, &o);
+  }
+}
+bool finite_all(const double* a, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(a[i])) return false;
+  return true;
+}
+bool loop_params_ok(const suma_loop_params& p) {
+  return finite_all(p.information, 36) && p.node_capacity != 0 && p.node_capacity <= (1u << 30) && p.delta_timestamp >= 0 &&
+         p.min_verifications >= 0;
+}
+void rigid12_to_mat4(const double* o, double* T) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) T[j * 4 + i] = o[i * 3 + j];
+    T[12 + i] = o[9 + i];
+    T[i * 4 + 3] = 0.0;
+  }
+  T[15] = 1.0;
+}
+
+}  // namespace
+
+void loop_ckpt_join(suma_pipeline* s) {
+  if (s->loop) join_worker(s->loop);
+}
+
+uint64_t loop_ckpt_sizes(const suma_pipeline* s, uint64_t* graph_bytes, uint64_t* opt_bytes) {
+  const LoopState* L = s->loop;
+  *graph_bytes = *opt_bytes = 0;
+  if (!L) return 0;
+  uint32_t n = 0, n_opt = 0;
+  (void)posegraph_host_poses(L->graph, &n);
+  *graph_bytes = sizeof(ckpt::GraphHead) + 192ull * n + (uint64_t)sizeof(ckpt::Edge) * suma_posegraph_edge_count(L->graph);
+  if (L->optimizing && L->opt_graph) {
+    (void)posegraph_host_poses(L->opt_graph, &n_opt);
+    *opt_bytes = sizeof(ckpt::OptHead) + 96ull * n_opt;
+  }
+  return sizeof(ckpt::LoopHead) + sizeof(suma_loop_params) + ((4ull * L->trajectory_distances.size() + 7) & ~7ull) +
+         (uint64_t)sizeof(ckpt::Candidate) * (L->unverified.size() + L->verified.size());
+}
+
+int loop_ckpt_write(suma_pipeline* s, std::vector<char>* loop, std::vector<char>* graph, std::vector<char>* opt) {
+  LoopState* L = s->loop;
+  suma_ctx* c = s->c;
+  ckpt::LoopHead h;
+  memset(&h, 0, sizeof(h));
+  h.params_bytes = (uint32_t)sizeof(suma_loop_params);
+  h.n_traj = (uint32_t)L->trajectory_distances.size();
+  h.n_unverified = (uint32_t)L->unverified.size(), h.n_verified = (uint32_t)L->verified.size();
+  h.already_verified = L->already_verified;
+  h.loop_count = L->loop_count, h.time_without = L->time_without;
+  h.found = L->found, h.use = L->use, h.started = L->started, h.integrated = L->integrated;
+  h.candidate_to = L->candidate_to, h.edges_added = L->edges_added;
+  h.result_old_outlier_ratio = L->result_old.outlier_ratio;
+  h.loop_valid_ratio = L->loop_valid_ratio, h.loop_outlier_ratio = L->loop_outlier_ratio;
+  h.loop_relative_error_all = L->loop_relative_error_all;
+  h.result_old_inlier = L->result_old.inlier, h.result_old_outlier = L->result_old.outlier;
+  h.result_old_valid = L->result_old.valid, h.result_old_invalid = L->result_old.invalid;
+  h.result_old_error = L->result_old.error, h.result_old_residual = L->result_old.residual;
+  h.result_old_inlier_residual = L->result_old.inlier_residual;
+  h.posegraph_error = L->posegraph_error;
+  put(loop, &h);
+  put(loop, &L->p);
+  put(loop, L->trajectory_distances.data(), L->trajectory_distances.size());
+  if (L->trajectory_distances.size() & 1u) {
+    const float zero = 0.0f;
+    put(loop, &zero);
+  }
+  put_candidates(loop, L->unverified);
+  put_candidates(loop, L->verified);
+
+  uint32_t n = 0, ni = 0;
+  const double* R = posegraph_host_poses(L->graph, &n);
+  const double* I = posegraph_host_initial(L->graph, &ni);
+  if (ni != n) return fail(c, SUMA_ERR_INVALID, "checkpoint: the pose graph's initial values and estimates differ in number");
+  ckpt::GraphHead gh;
+  gh.n_nodes = n, gh.n_edges = suma_posegraph_edge_count(L->graph);
+  put(graph, &gh);
+  for (uint32_t i = 0; i < n; ++i) {
+    put(graph, I + 12 * (size_t)i, 12);
+    put(graph, R + 12 * (size_t)i, 12);
+  }
+  for (uint32_t e = 0; e < gh.n_edges; ++e) {
+    ckpt::Edge o;
+    double Z[16];
+    PG_TRY(c, L->graph, suma_posegraph_edge(L->graph, e, &o.from, &o.to, Z, o.information));
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) o.Z[i * 3 + j] = Z[j * 4 + i];
+    o.Z[9] = Z[12], o.Z[10] = Z[13], o.Z[11] = Z[14];
+    put(graph, &o);
+  }
+  if (L->optimizing && L->opt_graph) {
+    uint32_t n_opt = 0;
+    const double* X = posegraph_host_poses(L->opt_graph, &n_opt);
+    ckpt::OptHead oh;
+    memset(&oh, 0, sizeof(oh));
+    oh.before_id = L->before_id, oh.before_loop_count = L->before_loop_count, oh.started_at = L->started_at;
+    oh.worker_rc = L->worker_rc, oh.n_opt = n_opt;
+    memcpy(oh.before_pose, L->before_pose, sizeof(oh.before_pose));
+    put(opt, &oh);
+    put(opt, X, 12 * (size_t)n_opt);
+  }
+  return SUMA_OK;
+}
+
+int loop_ckpt_check(suma_ctx* c, const char* loop, const char* graph, const char* opt, uint32_t timestamp,
+                    suma_loop_params* params) {
+  ckpt::LoopHead h;
+  memcpy(&h, loop, sizeof(h));
+  if (h.params_bytes != sizeof(suma_loop_params))
+    return fail(c, SUMA_ERR_INVALID, "checkpoint: section LOOP holds loop parameters of another size");
+  memcpy(params, loop + sizeof(h), sizeof(*params));
+  if (!loop_params_ok(*params)) return fail(c, SUMA_ERR_INVALID, "checkpoint: section LOOP: bad loop parameters");
+  ckpt::GraphHead gh;
+  memcpy(&gh, graph, sizeof(gh));
+  const uint32_t want = timestamp ? timestamp : 1u;
+  if (gh.n_nodes != want || h.n_traj != want)
+    return fail(c, SUMA_ERR_INVALID, "checkpoint: the pose graph is not in step with the timestamp");
+  if (gh.n_nodes > (1u << 30) || gh.n_edges > (1u << 29)) return fail(c, SUMA_ERR_CAPACITY, "checkpoint: pose graph too large");
+  std::vector<double> buf(24 * (size_t)gh.n_nodes);
+  memcpy(buf.data(), graph + sizeof(gh), buf.size() * sizeof(double));
+  if (!finite_all(buf.data(), buf.size())) return fail(c, SUMA_ERR_INVALID, "checkpoint: section GRAPH: non-finite pose");
+  const char* ep = graph + sizeof(gh) + 192 * (size_t)gh.n_nodes;
+  for (uint32_t e = 0; e < gh.n_edges; ++e) {
+    ckpt::Edge o;
+    memcpy(&o, ep + sizeof(o) * (size_t)e, sizeof(o));
+    if (!finite_all(o.Z, 12) || !finite_all(o.information, 36))
+      return fail(c, SUMA_ERR_INVALID, "checkpoint: section GRAPH: non-finite edge");
+  }
+  const char* cp = loop + sizeof(h) + sizeof(suma_loop_params) + ((4 * (size_t)h.n_traj + 7) & ~(size_t)7);
+  for (uint32_t k = 0; k < h.n_unverified + h.n_verified; ++k) {
+    ckpt::Candidate q;
+    memcpy(&q, cp + sizeof(q) * (size_t)k, sizeof(q));
+    if (q.from < 0 || q.to < 0 || (uint32_t)q.from > timestamp || (uint32_t)q.to > timestamp || !finite_all(q.rel_pose, 16))
+      return fail(c, SUMA_ERR_INVALID, "checkpoint: section LOOP: bad candidate");
+  }
+  if (opt) {
+    ckpt::OptHead oh;
+    memcpy(&oh, opt, sizeof(oh));
+    if (oh.n_opt == 0 || !finite_all(oh.before_pose, 16))
+      return fail(c, SUMA_ERR_INVALID, "checkpoint: section OPT: bad record");
+    /* a record the optimiser refused (worker_rc) may hold anything: the integration reports worker_rc before it reads.
+     * One it accepted is installed into the clone, which takes finite poses only -- an uninterrupted run would stop at
+     * the integration with the same code; here the image is refused before anything is written */
+    if (oh.worker_rc == SUMA_OK) {
+      std::vector<double> X(12 * (size_t)oh.n_opt);
+      memcpy(X.data(), opt + sizeof(oh), X.size() * sizeof(double));
+      if (!finite_all(X.data(), X.size())) return fail(c, SUMA_ERR_INVALID, "checkpoint: section OPT: non-finite pose");
+    }
+  }
+  return SUMA_OK;
+}
+
+int loop_ckpt_install(suma_pipeline* s, const char* loop, const char* graph, const char* opt) {
+  LoopState* L = s->loop;
+  suma_ctx* c = s->c;
+  ckpt::LoopHead h;
+  memcpy(&h, loop, sizeof(h));
+  ckpt::GraphHead gh;
+  memcpy(&gh, graph, sizeof(gh));
+  uint32_t nc = L->p.node_capacity ? L->p.node_capacity : 1u;
+  while (nc < gh.n_nodes + 1) nc *= 2;
+  uint32_t ec = 2 * nc;
+  while (ec < gh.n_edges + 1) ec *= 2;
+  PG_TRY(c, L->graph, suma_posegraph_reserve(L->graph, nc, ec));
+  std::vector<double> initial(12 * (size_t)gh.n_nodes), result(12 * (size_t)gh.n_nodes);
+  for (uint32_t i = 0; i < gh.n_nodes; ++i) {
+    memcpy(initial.data() + 12 * (size_t)i, graph + sizeof(gh) + 192 * (size_t)i, 96);
+    memcpy(result.data() + 12 * (size_t)i, graph + sizeof(gh) + 192 * (size_t)i + 96, 96);
+  }
+  PG_TRY(c, L->graph, posegraph_install_nodes(L->graph, initial.data(), result.data(), gh.n_nodes, false));
+  const char* ep = graph + sizeof(gh) + 192 * (size_t)gh.n_nodes;
+  for (uint32_t e = 0; e < gh.n_edges; ++e) { /* through the graph's own entry, in insertion order */
+    ckpt::Edge o;
+    memcpy(&o, ep + sizeof(o) * (size_t)e, sizeof(o));
+    double Z[16];
+    rigid12_to_mat4(o.Z, Z);
+    PG_TRY(c, L->graph, suma_posegraph_add_edge(L->graph, o.from, o.to, Z, o.information));
+  }
+  const char* tp = loop + sizeof(h) + sizeof(suma_loop_params);
+  L->trajectory_distances.resize(h.n_traj);
+  if (h.n_traj) memcpy(L->trajectory_distances.data(), tp, 4 * (size_t)h.n_traj);
+  const char* cp = tp + ((4 * (size_t)h.n_traj + 7) & ~(size_t)7);
+  L->unverified.clear(), L->verified.clear();
+  for (uint32_t k = 0; k < h.n_unverified + h.n_verified; ++k) {
+    ckpt::Candidate q;
+    memcpy(&q, cp + sizeof(q) * (size_t)k, sizeof(q));
+    LoopCandidate cand;
+    cand.from = q.from, cand.to = q.to;
+    memcpy(cand.rel_pose, q.rel_pose, sizeof(cand.rel_pose));
+    (k < h.n_unverified ? L->unverified : L->verified).push_back(cand);
+  }
+  L->already_verified = h.already_verified != 0;
+  L->loop_count = h.loop_count, L->time_without = h.time_without;
+  L->found = h.found != 0, L->use = h.use != 0, L->started = h.started != 0, L->integrated = h.integrated != 0;
+  L->candidate_to = h.candidate_to, L->edges_added = h.edges_added;
+  L->result_old.outlier_ratio = h.result_old_outlier_ratio;
+  L->loop_valid_ratio = h.loop_valid_ratio, L->loop_outlier_ratio = h.loop_outlier_ratio;
+  L->loop_relative_error_all = h.loop_relative_error_all;
+  L->result_old.inlier = h.result_old_inlier, L->result_old.outlier = h.result_old_outlier;
+  L->result_old.valid = h.result_old_valid, L->result_old.invalid = h.result_old_invalid;
+  L->result_old.error = h.result_old_error, L->result_old.residual = h.result_old_residual;
+  L->result_old.inlier_residual = h.result_old_inlier_residual;
+  L->posegraph_error = h.posegraph_error;
+  L->checked = false;
+  if (opt) {
+    /* the clone as the worker left it: only its poses are read by the integration (host record and device buffer) */
+    ckpt::OptHead oh;
+    memcpy(&oh, opt, sizeof(oh));
+    std::vector<double> X(12 * (size_t)oh.n_opt);
+    memcpy(X.data(), opt + sizeof(oh), X.size() * sizeof(double));
+    int rc = suma_posegraph_create(c->device, oh.n_opt, 1, &L->opt_graph);
+    if (rc != SUMA_OK) return fail(c, rc, std::string("suma_posegraph_create: ") + suma_posegraph_last_error(nullptr));
+    /* loop_ckpt_check has seen that an accepted record (worker_rc) is finite; a refused one is never read */
+    if (oh.worker_rc == SUMA_OK)
+      PG_TRY(c, L->opt_graph, posegraph_install_nodes(L->opt_graph, X.data(), X.data(), oh.n_opt, true));
+    L->optimizing = true;
+    L->before_id = oh.before_id, L->before_loop_count = oh.before_loop_count, L->started_at = oh.started_at;
+    memcpy(L->before_pose, oh.before_pose, sizeof(L->before_pose));
+    L->worker_rc = oh.worker_rc;
+    L->worker_done.store(1, std::memory_order_release);
+  }
+  return SUMA_OK;
+}

@@ -239,3 +239,24 @@ class LoopStatus(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("result_old", "reserved")}
         d["result_old"] = self.result_old.as_dict()
         return d
+
+
+CHECKPOINT_VERSION = 1        # SUMA_CHECKPOINT_VERSION
+CHECKPOINT_MAX_SECTIONS = 16  # SUMA_CHECKPOINT_MAX_SECTIONS
+
+
+class CheckpointSection(C.Structure):
+    """``struct suma_checkpoint_section``: one directory entry as suma_checkpoint_info reports it"""
+    _fields_ = [("id", u32), ("reserved", u32), ("bytes", C.c_uint64), ("digest", C.c_uint64)]
+
+
+class CheckpointInfo(C.Structure):
+    """``struct suma_checkpoint_info``: what a checkpoint image holds (core.checkpoint_info)"""
+    _fields_ = [("version", u32), ("timestamp", u32), ("n_active", u32), ("n_tiles", u32), ("n_parked", C.c_uint64),
+                ("n_nodes", u32), ("n_edges", u32), ("has_loop", i32), ("has_opt", i32), ("n_sections", u32),
+                ("reserved", u32), ("total_bytes", C.c_uint64), ("sections", CheckpointSection * CHECKPOINT_MAX_SECTIONS)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("sections", "reserved")}
+        d["sections"] = [dict(id=s.id, bytes=s.bytes, digest=s.digest) for s in self.sections[:self.n_sections]]
+        return d
