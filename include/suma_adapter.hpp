@@ -574,5 +574,57 @@ class Posegraph {
   suma_posegraph_stats stats_{};
 };
 
+/* Localisation in a finished world map, which is left alone (suma_localizer_*, csrc/k_localize.hip): setMap bins the
+ * records of SurfelMap::exportWorld / a map file into submap tiles on the device, setPose gives the start pose (there is
+ * no global relocalisation) and gathers the tiles around it, processScan renders that window from the predicted pose and
+ * minimises the scan against it.  Poses cross as column-major double[16] (Eigen::Matrix4d::data()). */
+class Localizer {
+ public:
+  explicit Localizer(const suma_params& p, const suma_localizer_params* lp = nullptr, int device = 0) {
+    if (suma_localizer_create(&p, lp, device, &l_) != SUMA_OK)
+      throw std::runtime_error(std::string("suma_localizer_create: ") + suma_last_error(nullptr));
+  }
+  ~Localizer() { suma_localizer_destroy(l_); }
+  Localizer(const Localizer&) = delete;
+  Localizer& operator=(const Localizer&) = delete;
+
+  /* returns the records that were dropped (non-finite position, outside the tile grid) */
+  uint32_t setMap(const std::vector<suma_world_surfel>& records) {
+    uint32_t dropped = 0;
+    chk(suma_localizer_set_map(l_, records.data(), (uint32_t)records.size(), &dropped), "Localizer::setMap");
+    return dropped;
+  }
+  uint32_t setMapDevice(const suma_world_surfel* d_records, uint32_t n) {
+    uint32_t dropped = 0;
+    chk(suma_localizer_set_map_device(l_, d_records, n, &dropped), "Localizer::setMapDevice");
+    return dropped;
+  }
+  void setPose(const double T[16]) { chk(suma_localizer_set_pose(l_, T), "Localizer::setPose"); }
+  suma_localizer_result processScan(const suma_float4* points, const float* labels, const float* probs, uint32_t n,
+                                    int32_t fixed_iterations = 0) {
+    suma_localizer_result r;
+    chk(suma_localizer_process_scan(l_, points, labels, probs, n, fixed_iterations, &r), "Localizer::processScan");
+    return r;
+  }
+  /* origin tile, records in the window, gathers since setMap */
+  void window(int32_t origin_ij[2], uint32_t* n_window, uint32_t* rebuilds) {
+    chk(suma_localizer_window(l_, origin_ij, n_window, rebuilds), "Localizer::window");
+  }
+  std::vector<suma_surfel> downloadWindow() {
+    uint32_t n = 0;
+    chk(suma_localizer_window(l_, nullptr, &n, nullptr), "Localizer::downloadWindow");
+    std::vector<suma_surfel> out(n);
+    chk(suma_localizer_download_window(l_, out.data(), n, &n), "Localizer::downloadWindow");
+    out.resize(n < out.size() ? n : out.size());
+    return out;
+  }
+  suma_localizer* get() const { return l_; }
+  suma_ctx* ctx() const { return suma_localizer_ctx(l_); }
+
+ private:
+  void chk(int rc, const char* what) { check(suma_localizer_ctx(l_), rc, what); }
+  suma_localizer* l_ = nullptr;
+};
+
 }  // namespace suma_hip
 #endif

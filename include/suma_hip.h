@@ -738,6 +738,76 @@ int suma_checkpoint_params(const void* image, uint64_t bytes, suma_params* out);
  * sum over k of (w[k] + 0x9E3779B97F4A7C15) * (2 k + 1) mod 2^64 */
 uint64_t suma_checkpoint_digest(const void* payload, uint64_t bytes);
 
+/* ---- localisation in a finished map: "here is yesterday's map (suma_map_export_world / mapio), tell me where the sensor
+ *      is in it, and leave the map alone".  The reference has no such mode; its nearest relative is the loop-closure
+ *      verification, which renders the inactive map from a pose and minimises against it -- and that is what one scan
+ *      does here.  A localiser owns a suma_ctx of its own.  It keeps the world records on the device, binned into the
+ *      reference's submap tiles, and fills that ctx's active surfel buffer with the tiles around the sensor
+ *      (csrc/k_localize.hip states the specification; tests/localize_shim.c restates it on the host).  The window's
+ *      surfels have creation stamp 0 and row 0 of the ctx's pose table is the identity, so the world frame is their
+ *      creation frame; the ctx's timestamp is the constant T_loc = active_timestamps + 10.  Nothing is ever fused: the
+ *      map, the pose table and the world records are not written, and a run has no length limit (max_poses is not
+ *      consumed).  DESIGN.md 12 has the step order and the two limits: a window smaller than the model image's range
+ *      localises on what it has, and there is no global relocalisation -- the start pose is the caller's.
+ *      Calls on one localiser are serialised by the caller.  Errors: the library's codes; the text is
+ *      suma_last_error(suma_localizer_ctx(l)), or suma_last_error(NULL) after a failed create.
+ *      (Kept here, not in suma_types.h, for the reason given at suma_semantic_params.) */
+typedef struct suma_localizer suma_localizer;
+typedef struct suma_localizer_params {
+  float conf_threshold;        /* render threshold; default suma_params.confidence_threshold */
+  float min_valid_ratio;       /* default 0.2  (the reference's closure gate literals, */
+  float max_outlier_ratio;     /* default 0.85  SurfelMapping.cpp:567) */
+  int32_t constant_velocity;   /* default 1: guess = pose * last_increment; 0: guess = pose */
+} suma_localizer_params;
+typedef struct suma_localizer_result {
+  double guess[16], pose[16], increment[16];
+  suma_icp_stats stats;        /* the objective as the minimisation left it */
+  float valid_ratio, outlier_ratio;   /* as closure_gate forms them: valid / (valid + invalid), outlier / (outlier +
+                                         inlier) in fp32; 0 / 0 = NaN, which passes no gate */
+  int32_t tracked;             /* both gates passed */
+  int32_t window_rebuilt;      /* this scan moved the window's origin and gathered the window again */
+  int32_t origin_ij[2];
+  uint32_t n_window;
+} suma_localizer_result;
+
+/* conf_threshold = params->confidence_threshold (0 when params is NULL), 0.2, 0.85, 1 */
+void suma_localizer_params_default(const suma_params* params, suma_localizer_params* lp);
+/* lp NULL = the defaults.  SUMA_ERR_INVALID: a NaN threshold or ratio, submap_dimension < 0 or > 64, a submap_extent
+ * that is not finite and > 0, active_timestamps outside 91 .. 2^31 - 11 (the inactive render selects creation stamps
+ * below T_loc - 100, the reference's literal, SurfelMap.cpp:873: with less, no record of the window would render) */
+int suma_localizer_create(const suma_params* params, const suma_localizer_params* lp, int hip_device, suma_localizer** out);
+void suma_localizer_destroy(suma_localizer* l);
+/* the localiser's own ctx, borrowed: frames (suma_map_frame(ctx, SUMA_FRAME_OLD) is the rendered model), profiling,
+ * the stream, the error text.  Do not update or upload its map. */
+suma_ctx* suma_localizer_ctx(suma_localizer* l);
+/* the map: n records as suma_map_export_world / mapio give them.  Binned once (a key per record, one stable sort, a tile
+ * directory that is read back); blocking, off the scan path.  *n_dropped (optional) = records with a non-finite position
+ * or outside the tile grid, which no window will hold.  The localiser keeps its own copy (48 bytes a kept record); the
+ * caller's buffer is only read.  n = 0 is legal.  A new map forgets the pose: call suma_localizer_set_pose next. */
+int suma_localizer_set_map(suma_localizer* l, const suma_world_surfel* host, uint32_t n, uint32_t* n_dropped);
+int suma_localizer_set_map_device(suma_localizer* l, const suma_world_surfel* d_records, uint32_t n, uint32_t* n_dropped);
+/* the start pose (sensor in the world frame, column-major): resets the increment to identity, puts the window's origin
+ * on the pose's own tile and gathers the window.  SUMA_ERR_CAPACITY when the window holds more than max_surfels
+ * records: detected on the host before anything is launched, the localiser is left exactly as it was. */
+int suma_localizer_set_pose(suma_localizer* l, const double T[16]);
+/* one scan (points / labels / probs as suma_preprocess takes them).  fixed_iterations has the pipeline's meaning.
+ * SUMA_ERR_INVALID before suma_localizer_set_map / _set_pose, or with a NULL result.  An empty window is legal: nothing is
+ * minimised, stats are zero, tracked = 0, pose = guess and the increment stays; the same holds for a chain that ends on
+ * a non-finite pose.
+ * The pose is kept orthonormal (Gram-Schmidt on the rotation's columns after every scan): the increment is formed with
+ * the rigid inverse, which is the inverse of an orthonormal rotation only.
+ * The _device entry reads scan buffers that must be complete when the call is made (suma_preprocess_device). */
+int suma_localizer_process_scan(suma_localizer* l, const suma_float4* points, const float* labels, const float* probs,
+                                uint32_t n, int32_t fixed_iterations, suma_localizer_result* result);
+int suma_localizer_process_scan_device(suma_localizer* l, const suma_float4* d_points, const float* d_labels,
+                                       const float* d_probs, uint32_t n, int32_t fixed_iterations,
+                                       suma_localizer_result* result);
+/* the window now: origin tile, records, and how often it has been gathered since the last suma_localizer_set_map
+ * (suma_localizer_set_pose counts).  Any output may be NULL. */
+int suma_localizer_window(suma_localizer* l, int32_t origin_ij[2], uint32_t* n_window, uint32_t* rebuilds);
+/* the window's surfels as the ctx holds them: *n = their number, min(*n, capacity) are copied */
+int suma_localizer_download_window(suma_localizer* l, suma_surfel* host, uint32_t capacity, uint32_t* n);
+
 /* ---- per-kernel timing (rv::Stopwatch / SurfelMapping::Stats, SurfelMapping.cpp:183-207):
  *      on = 1: every kernel group is bracketed by HIP events on the ctx stream; on = 2: only the
  *      Gauss-Newton chain (the kernel with the largest share of GPU time), which costs two event

@@ -9,6 +9,7 @@ stand for (PRBonn/semantic_suma, src/core):
     LieGaussNewton   src/core/LieGaussNewton.h:25-76         minimize(objective, T0), pose(), history()
     SurfelMap        src/core/SurfelMap.h:36-78              update / render* / *MapFrame / updatePoses / size / draw
     SurfelMapping    src/core/SurfelMapping.h:47             processScan(scan)
+    Localizer        (no counterpart)                        setMap / setPose / processScan in a finished map
     Posegraph        src/core/Posegraph.h:10-78              setInitial / addEdge / optimize / poses
 
 Everything here is plumbing: numpy arrays in, ctypes calls into ``libsuma_hip.so`` (hand-written
@@ -26,7 +27,8 @@ import numpy as np
 
 from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX_LIGHTS, SURFEL_DTYPE, DrawParams,
                     IcpStats, LoopParams, LoopStatus, PosegraphParams, PosegraphStats, SemanticKnnParams,
-                    SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats, CheckpointInfo)
+                    SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats, CheckpointInfo,
+                    LocalizerParams, LocalizerResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -260,6 +262,21 @@ def lib():
     L.suma_checkpoint_params.argtypes = [vp, C.c_uint64, C.POINTER(SumaParams)]
     L.suma_checkpoint_digest.argtypes = [vp, C.c_uint64]
     L.suma_checkpoint_digest.restype = C.c_uint64
+    lpp, lrp = C.POINTER(LocalizerParams), C.POINTER(LocalizerResult)
+    L.suma_localizer_params_default.argtypes = [C.POINTER(SumaParams), lpp]
+    L.suma_localizer_params_default.restype = None
+    L.suma_localizer_create.argtypes = [C.POINTER(SumaParams), lpp, C.c_int, pp]
+    L.suma_localizer_destroy.argtypes = [vp]
+    L.suma_localizer_destroy.restype = None
+    L.suma_localizer_ctx.argtypes = [vp]
+    L.suma_localizer_ctx.restype = vp
+    L.suma_localizer_set_map.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_localizer_set_map_device.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_localizer_set_pose.argtypes = [vp, vp]
+    L.suma_localizer_process_scan.argtypes = [vp, vp, vp, vp, u32, i32, lrp]
+    L.suma_localizer_process_scan_device.argtypes = [vp, vp, vp, vp, u32, i32, lrp]
+    L.suma_localizer_window.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
+    L.suma_localizer_download_window.argtypes = [vp, vp, u32, C.POINTER(u32)]
     _LIB = L
     return L
 
@@ -1424,6 +1441,115 @@ class SurfelMapping:
             if getattr(self, "posegraph", None) is not None:
                 self.posegraph.h = None
             self.L.suma_pipeline_destroy(self.h)
+            self.h = None
+            self.ctx.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Localizer:
+    """Localisation of scans in a finished world map, which is left alone (suma_localizer_*, csrc/k_localize.hip): the
+    map is what SurfelMap.export_world / mapio give.  ``setMap`` bins it into submap tiles on the device, ``setPose``
+    gives the start pose (there is no global relocalisation) and gathers the tiles around it, ``processScan`` renders
+    that window from the predicted pose, minimises the scan against it and returns a dict: guess / pose / increment
+    (row-major 4x4), stats, valid_ratio, outlier_ratio, tracked, window_rebuilt, origin, n_window.  Nothing is fused, so a
+    run has no length limit."""
+
+    def __init__(self, params: SumaParams, loc_params: LocalizerParams = None, device: int = 0):
+        self.L = lib()
+        self.params = params
+        h = C.c_void_p()
+        rc = self.L.suma_localizer_create(C.byref(params), None if loc_params is None else C.byref(loc_params), device,
+                                          C.byref(h))
+        if rc != 0:
+            raise SumaError(f"suma_localizer_create failed ({rc}): {self.L.suma_last_error(None).decode()}")
+        self.h = h
+        self.ctx = Context(params, handle=C.c_void_p(self.L.suma_localizer_ctx(h)), owner=self)
+        self.n_dropped = 0
+
+    @classmethod
+    def from_ply(cls, path: str, params: SumaParams, loc_params: LocalizerParams = None, device: int = 0) -> "Localizer":
+        """a localiser over the map a PLY written by mapio.write_ply / tools/export_map.py holds"""
+        from . import mapio
+        records, _ = mapio.read_ply(path)
+        loc = cls(params, loc_params, device)
+        loc.setMap(records)
+        return loc
+
+    def setMap(self, world_surfels: np.ndarray) -> int:
+        """WORLD_SURFEL_DTYPE records; returns how many were dropped (non-finite position, outside the tile grid)"""
+        ws = np.ascontiguousarray(world_surfels, dtype=WORLD_SURFEL_DTYPE).reshape(-1)
+        nd = C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_set_map(self.h, _ptr(ws) if ws.shape[0] else None, ws.shape[0], C.byref(nd)),
+                       "suma_localizer_set_map")
+        self.n_dropped = nd.value
+        return nd.value
+
+    def setMapDevice(self, d_records, n: int) -> int:
+        """the records already on the device (an address or a torch tensor); they are only read"""
+        nd = C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_set_map_device(self.h, _dev(d_records), n, C.byref(nd)),
+                       "suma_localizer_set_map_device")
+        self.n_dropped = nd.value
+        return nd.value
+
+    def setPose(self, pose):
+        T = _cm(pose, np.float64)
+        self.ctx.check(self.L.suma_localizer_set_pose(self.h, _ptr(T)), "suma_localizer_set_pose")
+
+    @staticmethod
+    def _result(r: LocalizerResult) -> dict:
+        m = lambda a: np.array(a[:], dtype=np.float64).reshape(4, 4).T.copy()  # noqa: E731
+        return dict(guess=m(r.guess), pose=m(r.pose), increment=m(r.increment), stats=r.stats.as_dict(),
+                    valid_ratio=float(r.valid_ratio), outlier_ratio=float(r.outlier_ratio), tracked=bool(r.tracked),
+                    window_rebuilt=bool(r.window_rebuilt), origin=(int(r.origin_ij[0]), int(r.origin_ij[1])),
+                    n_window=int(r.n_window))
+
+    def processScan(self, points, labels=None, probs=None, fixed_iterations: int = 0) -> dict:
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
+        labels = None if labels is None else np.ascontiguousarray(labels, dtype=np.float32)
+        probs = None if probs is None else np.ascontiguousarray(probs, dtype=np.float32)
+        res = LocalizerResult()
+        self.ctx.check(self.L.suma_localizer_process_scan(self.h, _ptr(points), _ptr(labels), _ptr(probs), points.shape[0],
+                                                          fixed_iterations, C.byref(res)), "suma_localizer_process_scan")
+        return self._result(res)
+
+    def processScanDevice(self, d_points, d_labels, d_probs, n: int, fixed_iterations: int = 0) -> dict:
+        """scan already resident in HBM and complete (device addresses from Context.device_array, or torch tensors)"""
+        res = LocalizerResult()
+        self.ctx.check(self.L.suma_localizer_process_scan_device(self.h, _dev(d_points), _dev(d_labels), _dev(d_probs), n,
+                                                                 fixed_iterations, C.byref(res)),
+                       "suma_localizer_process_scan_device")
+        return self._result(res)
+
+    def window(self):
+        """(origin tile (i, j), records in the window, gathers since setMap)"""
+        ij = np.zeros(2, dtype=np.int32)
+        n, rb = C.c_uint32(0), C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_window(self.h, _ptr(ij), C.byref(n), C.byref(rb)), "suma_localizer_window")
+        return (int(ij[0]), int(ij[1])), n.value, rb.value
+
+    def downloadWindow(self) -> np.ndarray:
+        """the window's surfels as the localiser's ctx holds them (SURFEL_DTYPE)"""
+        n = self.window()[1]
+        out = np.zeros(n, dtype=SURFEL_DTYPE)
+        got = C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_download_window(self.h, _ptr(out) if n else None, n, C.byref(got)),
+                       "suma_localizer_download_window")
+        return out[:min(n, got.value)]
+
+    def modelFrame(self) -> Frame:
+        """the window as the last scan's render saw it (the ctx's oldMapFrame)"""
+        p = self.params
+        return Frame(self.ctx, p.model_width, p.model_height, handle=self.L.suma_map_frame(self.ctx.h, 0))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.suma_localizer_destroy(self.h)
             self.h = None
             self.ctx.h = None
 

@@ -820,16 +820,11 @@ static int enqueue_minimize(suma_ctx* c, const GnChain& ch) {
  * length) that the host polls: no copy command and no stream synchronisation behind the minimisation (round 3:
  * hipMemcpyAsync + hipStreamSynchronize, and a second pair for the history).  The pose history is always recorded on
  * the device; it crosses to the host only when asked for -- here, or later through suma_icp_history. */
-extern "C" int suma_icp_minimize(suma_ctx* c, const double T0[16], double T_out[16], double* history,
-                                 uint32_t history_cap, uint32_t* n_hist, suma_icp_stats* stats) {
-  if (!c || !T0 || !T_out) return SUMA_ERR_INVALID;
-  if (!c->icp_current || !c->icp_model) return fail(c, SUMA_ERR_INVALID, "suma_icp_set_data has not been called");
+static int minimize_reported(suma_ctx* c, GnChain ch, double T_out[16], double* history, uint32_t history_cap,
+                             uint32_t* n_hist, suma_icp_stats* stats) {
   HostResult* rec = &c->h_rec[0];
   c->rec_seq += 1;
-  GnChain ch = gn_chain_ctx(c, T0, 1);
   ch.with_history = 1;
-  ch.iteration0 = c->icp_iteration0; /* suma_icp_set_iteration, one shot */
-  c->icp_iteration0 = 0;
   ch.report = rec;
   ch.report_seq = c->rec_seq;
   ch.report_full = 1;
@@ -847,6 +842,29 @@ extern "C" int suma_icp_minimize(suma_ctx* c, const double T0[16], double T_out[
   if (n_hist) *n_hist = rec->n_hist;
   if (history != nullptr && history_cap > 0) return suma_icp_history(c, history, history_cap, nullptr);
   return SUMA_OK;
+}
+
+extern "C" int suma_icp_minimize(suma_ctx* c, const double T0[16], double T_out[16], double* history,
+                                 uint32_t history_cap, uint32_t* n_hist, suma_icp_stats* stats) {
+  if (!c || !T0 || !T_out) return SUMA_ERR_INVALID;
+  if (!c->icp_current || !c->icp_model) return fail(c, SUMA_ERR_INVALID, "suma_icp_set_data has not been called");
+  GnChain ch = gn_chain_ctx(c, T0, 1);
+  ch.iteration0 = c->icp_iteration0; /* suma_icp_set_iteration, one shot */
+  c->icp_iteration0 = 0;
+  return minimize_reported(c, ch, T_out, history, history_cap, n_hist, stats);
+}
+
+int icp_minimize_frames(suma_ctx* c, const suma_frame* current, const suma_frame* model, const double T0[16],
+                        int32_t fixed_iterations, double T_out[16], suma_icp_stats* stats) {
+  int r = suma_icp_set_data(c, current, model);
+  if (r) return r;
+  GnChain ch = gn_chain_ctx(c, T0, 1);
+  if (fixed_iterations > 0) { /* as pipeline_chain */
+    ch.max_iterations = (uint32_t)fixed_iterations;
+    ch.epsilon = 0.0;
+    ch.delta = 0.0;
+  }
+  return minimize_reported(c, ch, T_out, nullptr, 0, nullptr, stats);
 }
 
 extern "C" int suma_icp_set_iteration(suma_ctx* c, uint32_t iteration) {

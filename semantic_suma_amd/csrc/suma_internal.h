@@ -6,6 +6,7 @@
 #define SUMA_INTERNAL_H_
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <initializer_list>
@@ -533,6 +534,35 @@ int loop_ckpt_check(suma_ctx* c, const char* loop, const char* graph, const char
                     suma_loop_params* params);
 int loop_ckpt_install(suma_pipeline* s, const char* loop, const char* graph, const char* opt);
 
+/* k_localize.hip (the specification is there): the world map binned into submap tiles, and the window gather */
+struct LocTile { /* one occupied tile of the directory, ascending by key */
+  unsigned long long key;
+  uint32_t start, count; /* its records in LocMap.sorted */
+};
+struct LocSpan { /* one tile of a window: count records from sorted[src] to the active buffer at dst */
+  uint32_t src, dst, count, pad;
+};
+struct LocMap {
+  DevBuf<float4> sorted;    /* 3 float4 a record: the kept records by (key, source index) */
+  std::vector<LocTile> dir; /* the host's copy of the directory */
+  uint32_t n_kept = 0, n_dropped = 0;
+  DevBuf<LocSpan> spans;    /* the span table of the last gather */
+};
+/* bins n device records (only read) into *m on the ctx stream; blocking.  A failure leaves *m as it was */
+int localize_bin(suma_ctx* c, const suma_world_surfel* d_records, uint32_t n, LocMap* m);
+/* the window's tiles looked up in the directory: spans ascending by (i, then j), *total = records */
+void localize_window_spans(const LocMap& m, int32_t oi, int32_t oj, int32_t dim, std::vector<LocSpan>* spans,
+                           uint64_t* total);
+/* spans -> the ctx's active surfel buffer, DevState.n_surfels = total; total <= max_surfels is the caller's check */
+int localize_gather(suma_ctx* c, LocMap* m, const std::vector<LocSpan>& spans, uint32_t total);
+/* the cell (i, j) of a position; false: non-finite or outside the grid */
+bool localize_cell(float extent, float x, float y, float z, int32_t* i, int32_t* j);
+
+/* suma_api.hip: suma_icp_set_data + suma_icp_minimize on the given frames with processScan's fixed-iteration override
+ * (fixed_iterations > 0: exactly that many iterations, no stopping test) */
+int icp_minimize_frames(suma_ctx* c, const suma_frame* current, const suma_frame* model, const double T0[16],
+                        int32_t fixed_iterations, double T_out[16], suma_icp_stats* stats);
+
 /* host helper shared by api + pipeline */
 void rigid_inverse_f(const float* m, float* out);
 
@@ -553,6 +583,23 @@ static inline void mat4_rigid_inv(const double* m, double* out) {
   for (int r = 0; r < 3; ++r) out[12 + r] = -((m[4 * r] * m[12] + m[4 * r + 1] * m[13]) + m[4 * r + 2] * m[14]);
   out[3] = out[7] = out[11] = 0.0;
   out[15] = 1.0;
+}
+/* makes the rotation of a pose orthonormal again, in one fixed operation order (tests/localize_host.py orthonormalize):
+ * Gram-Schmidt on its columns -- c0 normalised, c1 made orthogonal to c0 and normalised, c2 = c0 x c1; the translation
+ * is kept, the last row becomes 0 0 0 1.  A recursion that inverts poses by mat4_rigid_inv needs it: the transpose is
+ * the inverse of an orthonormal rotation only, and what is missing is fed back (suma_localize.hip) */
+static inline void mat4_orthonormalize(double* T) {
+  double a[3] = {T[0], T[1], T[2]}, b[3] = {T[4], T[5], T[6]};
+  double n = sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+  for (int r = 0; r < 3; ++r) a[r] = a[r] / n;
+  const double d = (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
+  for (int r = 0; r < 3; ++r) b[r] = b[r] - d * a[r];
+  n = sqrt((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]);
+  for (int r = 0; r < 3; ++r) b[r] = b[r] / n;
+  const double c[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+  for (int r = 0; r < 3; ++r) T[r] = a[r], T[4 + r] = b[r], T[8 + r] = c[r];
+  T[3] = T[7] = T[11] = 0.0;
+  T[15] = 1.0;
 }
 static inline void mat4_cast_f(const double* T, float* out) {
   for (int i = 0; i < 16; ++i) out[i] = (float)T[i];

@@ -1,0 +1,284 @@
+/*
+ * suma_localize.hip -- localisation of scans in a finished world map, without changing it (include/suma_hip.h,
+ * suma_localizer_*).  Host code: a localiser is a suma_ctx of its own whose active surfel buffer holds a window of the
+ * binned world map (k_localize.hip states the specification), one data frame, and the pose bookkeeping below.  One scan
+ * is the composition the loop-closure verification uses (SurfelMapping.cpp:546-558): render the inactive map from the
+ * predicted pose, minimise the scan against it from identity, gate on the objective's counters -- through the library's
+ * own entries (suma_preprocess*, suma_map_render_inactive, icp_minimize_frames), which is all the device work there is
+ * besides the window gather.  4x4 products and rigid inverses are mat4_mul / mat4_rigid_inv, the library's one fixed
+ * operation order; tests/localize_host.py is the same sequence over the CPU oracle.
+ */
+#include <math.h>
+#include <string.h>
+
+#include <cmath>
+#include <new>
+#include <vector>
+
+#include "suma_internal.h"
+
+struct suma_localizer {
+  suma_ctx* c = nullptr;
+  suma_frame* frame = nullptr; /* the scan, K1-K3 */
+  suma_localizer_params lp;
+  LocMap map;
+  bool have_map = false, have_pose = false, first = true;
+  double pose[16], increment[16];
+  int32_t oi = 0, oj = 0;
+  uint32_t n_window = 0, rebuilds = 0;
+  std::vector<LocSpan> spans;
+};
+
+namespace {
+
+bool finite16(const double* T) {
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(T[k])) return false;
+  return true;
+}
+
+/* the window around (oi, oj) into the ctx's active buffer; a window beyond max_surfels is refused before anything is
+ * launched or written */
+int gather_window(suma_localizer* l, int32_t oi, int32_t oj) {
+  suma_ctx* c = l->c;
+  uint64_t total = 0;
+  std::vector<LocSpan> spans;
+  localize_window_spans(l->map, oi, oj, c->p.submap_dimension, &spans, &total);
+  if (total > c->p.max_surfels)
+    return fail(c, SUMA_ERR_CAPACITY, "suma_localizer: the window around tile (" + std::to_string(oi) + ", " +
+                                      std::to_string(oj) + ") holds " + std::to_string(total) + " records, max_surfels = " +
+                                      std::to_string(c->p.max_surfels));
+  int r = localize_gather(c, &l->map, spans, (uint32_t)total);
+  if (r) return r;
+  l->spans.swap(spans);
+  l->oi = oi, l->oj = oj;
+  l->n_window = (uint32_t)total;
+  l->rebuilds += 1;
+  return SUMA_OK;
+}
+
+}  // namespace
+
+extern "C" void suma_localizer_params_default(const suma_params* params, suma_localizer_params* lp) {
+  if (!lp) return;
+  lp->conf_threshold = params ? params->confidence_threshold : 0.0f;
+  lp->min_valid_ratio = 0.2f; /* SurfelMapping.cpp:567 */
+  lp->max_outlier_ratio = 0.85f;
+  lp->constant_velocity = 1;
+}
+
+extern "C" int suma_localizer_create(const suma_params* params, const suma_localizer_params* lp, int hip_device,
+                                     suma_localizer** out) {
+  if (!params || !out) return SUMA_ERR_INVALID;
+  *out = nullptr;
+  suma_localizer_params q;
+  suma_localizer_params_default(params, &q);
+  if (lp) q = *lp;
+  if (std::isnan(q.conf_threshold) || std::isnan(q.min_valid_ratio) || std::isnan(q.max_outlier_ratio))
+    return fail_without_ctx(SUMA_ERR_INVALID, "suma_localizer_create: a NaN threshold or ratio");
+  if (params->submap_dimension < 0 || params->submap_dimension > 64)
+    return fail_without_ctx(SUMA_ERR_INVALID, "suma_localizer_create: submap_dimension must be 0 .. 64");
+  if (!(params->submap_extent > 0.0f) || std::isinf(params->submap_extent))
+    return fail_without_ctx(SUMA_ERR_INVALID, "suma_localizer_create: submap_extent must be finite and > 0");
+  if (params->active_timestamps < 91 || params->active_timestamps > 0x7fffffff - 10)
+    return fail_without_ctx(SUMA_ERR_INVALID,
+                            "suma_localizer_create: active_timestamps must be at least 91 (the inactive render selects "
+                            "creation stamps below timestamp - 100)");
+  suma_localizer* l = new (std::nothrow) suma_localizer();
+  if (!l) return fail_without_ctx(SUMA_ERR_NOMEM, "out of host memory");
+  int r = suma_ctx_create(params, hip_device, &l->c); /* leaves its text for suma_last_error(NULL) */
+  if (r) {
+    delete l;
+    return r;
+  }
+  r = suma_frame_create(l->c, params->data_width, params->data_height, &l->frame);
+  if (r) {
+    fail_without_ctx(r, std::string("suma_localizer_create: ") + suma_last_error(l->c));
+    suma_localizer_destroy(l);
+    return r;
+  }
+  l->lp = q;
+  l->c->timestamp = (uint32_t)params->active_timestamps + 10u; /* T_loc (k_localize.hip) */
+  mat4_eye(l->pose);
+  mat4_eye(l->increment);
+  *out = l;
+  return SUMA_OK;
+}
+
+extern "C" void suma_localizer_destroy(suma_localizer* l) {
+  if (!l) return;
+  if (l->c && l->c->stream) hipStreamSynchronize(l->c->stream);
+  l->map = LocMap(); /* device blocks go before the ctx */
+  suma_frame_destroy(l->frame);
+  suma_ctx_destroy(l->c);
+  delete l;
+}
+
+extern "C" suma_ctx* suma_localizer_ctx(suma_localizer* l) { return l ? l->c : nullptr; }
+
+extern "C" int suma_localizer_set_map_device(suma_localizer* l, const suma_world_surfel* d_records, uint32_t n,
+                                             uint32_t* n_dropped) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (n && !d_records) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_map: NULL records with n > 0");
+  if (n && ((uintptr_t)d_records & 15u)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_map: records must be 16-byte aligned");
+  int r = localize_bin(c, d_records, n, &l->map);
+  if (r) return r;
+  l->have_map = true;
+  l->have_pose = false;
+  l->n_window = 0, l->rebuilds = 0;
+  l->spans.clear();
+  if (n_dropped) *n_dropped = l->map.n_dropped;
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_set_map(suma_localizer* l, const suma_world_surfel* host, uint32_t n, uint32_t* n_dropped) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (n && !host) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_map: NULL records with n > 0");
+  DevBuf<suma_world_surfel> staged; /* given back when the call returns: the localiser keeps the binned copy only */
+  if (n) {
+    HIP_TRY(c, staged.alloc(n));
+    HIP_TRY(c, hipMemcpyAsync(staged, host, (size_t)n * sizeof(suma_world_surfel), hipMemcpyHostToDevice, c->stream));
+  }
+  const int r = suma_localizer_set_map_device(l, staged, n, n_dropped);
+  hipStreamSynchronize(c->stream); /* nothing reads `staged` behind this */
+  return r;
+}
+
+extern "C" int suma_localizer_set_pose(suma_localizer* l, const double T[16]) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (!T) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_pose: NULL pose");
+  if (!l->have_map) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_pose: no map (suma_localizer_set_map)");
+  if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_pose: non-finite pose");
+  int32_t i, j;
+  if (!localize_cell(c->p.submap_extent, (float)T[12], (float)T[13], (float)T[14], &i, &j))
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_pose: the pose lies outside the tile grid");
+  int r = gather_window(l, i, j);
+  if (r) return r;
+  memcpy(l->pose, T, sizeof(l->pose));
+  mat4_eye(l->increment);
+  l->have_pose = true;
+  l->first = true;
+  return SUMA_OK;
+}
+
+static int process_scan(suma_localizer* l, const suma_float4* points, const float* labels, const float* probs, uint32_t n,
+                        int32_t fixed_iterations, suma_localizer_result* res, bool on_device) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (!res) return fail(c, SUMA_ERR_INVALID, "suma_localizer_process_scan: NULL result");
+  if (n && !points) return fail(c, SUMA_ERR_INVALID, "suma_localizer_process_scan: NULL points with n > 0");
+  if (!l->have_map) return fail(c, SUMA_ERR_INVALID, "suma_localizer_process_scan: no map (suma_localizer_set_map)");
+  if (!l->have_pose) return fail(c, SUMA_ERR_INVALID, "suma_localizer_process_scan: no start pose (suma_localizer_set_pose)");
+  memset(res, 0, sizeof(*res));
+  /* 1. the predicted pose */
+  double guess[16];
+  if (l->lp.constant_velocity)
+    mat4_mul(l->pose, l->increment, guess);
+  else
+    memcpy(guess, l->pose, sizeof(guess));
+  if (!finite16(guess)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_process_scan: the predicted pose is not finite");
+  float gf[16];
+  mat4_cast_f(guess, gf);
+  /* 2. re-centre the window (updateActiveSubmaps' rule, SurfelMap.cpp:750-790) */
+  {
+    const float e = c->p.submap_extent, factor = 1.1f;
+    const float cx = (float)(2.0 * l->oi * e), cy = (float)(2.0 * l->oj * e);
+    const float changex = gf[12] - cx, changey = gf[13] - cy;
+    int32_t oi = l->oi, oj = l->oj;
+    if (fabsf(changex) > factor * e) oi += (changex < 0) ? -1 : 1;
+    if (fabsf(changey) > factor * e) oj += (changey < 0) ? -1 : 1;
+    if (oi != l->oi || oj != l->oj) {
+      if (oi <= -1048576 || oi >= 1048576 || oj <= -1048576 || oj >= 1048576)
+        return fail(c, SUMA_ERR_INVALID, "suma_localizer_process_scan: the predicted pose leaves the tile grid");
+      int r = gather_window(l, oi, oj);
+      if (r) return r;
+      res->window_rebuilt = 1;
+    }
+  }
+  double T_gn[16];
+  mat4_eye(T_gn);
+  bool minimised = false;
+  suma_icp_stats st;
+  memset(&st, 0, sizeof(st));
+  if (l->n_window) {
+    /* 3. K1-K3 at T_loc */
+    int r = on_device ? suma_preprocess_device(c, points, labels, probs, n, c->timestamp, l->frame)
+                      : suma_preprocess(c, points, labels, probs, n, c->timestamp, l->frame);
+    if (r) return r;
+    /* 4. the model: the window seen from the guess */
+    r = suma_map_render_inactive(c, gf, l->lp.conf_threshold);
+    if (r) return r;
+    /* 5. frame-to-model from identity */
+    double I[16];
+    mat4_eye(I);
+    r = icp_minimize_frames(c, l->frame, c->old_frame, I, fixed_iterations, T_gn, &st);
+    if (r) return r;
+    minimised = finite16(T_gn);
+  }
+  /* 6, 7. */
+  double pose[16], inv[16];
+  if (minimised) {
+    mat4_mul(guess, T_gn, pose);
+    /* kept orthonormal: step 7 inverts the pose by transposition, and what a rotation lacks to be orthonormal would
+     * come back in the next guess twice and once more (pose * pose_prev^T * pose): a factor of 2.4 per scan, from 1e-16
+     * to a lost run within 40 scans */
+    mat4_orthonormalize(pose);
+    if (l->first) {
+      mat4_eye(l->increment);
+    } else {
+      mat4_rigid_inv(l->pose, inv);
+      mat4_mul(inv, pose, l->increment);
+    }
+  } else {
+    /* nothing was minimised (empty window, or a chain that ended on a non-finite pose): pose = guess, and the increment
+     * stays what it is -- rigid_inverse(pose_prev) * (pose_prev * increment) without the rounding */
+    memcpy(pose, guess, sizeof(pose));
+  }
+  memcpy(l->pose, pose, sizeof(pose));
+  l->first = false;
+
+  memcpy(res->guess, guess, sizeof(guess));
+  memcpy(res->pose, pose, sizeof(pose));
+  memcpy(res->increment, l->increment, sizeof(l->increment));
+  res->stats = st;
+  res->valid_ratio = (float)st.valid / (float)(st.valid + st.invalid); /* closure_gate (suma_api.hip) */
+  res->outlier_ratio = (float)st.outlier / (float)(st.outlier + st.inlier);
+  res->tracked = ((double)res->valid_ratio > (double)l->lp.min_valid_ratio &&
+                  (double)res->outlier_ratio < (double)l->lp.max_outlier_ratio) ? 1 : 0;
+  res->origin_ij[0] = l->oi, res->origin_ij[1] = l->oj;
+  res->n_window = l->n_window;
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_process_scan(suma_localizer* l, const suma_float4* points, const float* labels,
+                                           const float* probs, uint32_t n, int32_t fixed_iterations,
+                                           suma_localizer_result* result) {
+  return process_scan(l, points, labels, probs, n, fixed_iterations, result, false);
+}
+
+extern "C" int suma_localizer_process_scan_device(suma_localizer* l, const suma_float4* d_points, const float* d_labels,
+                                                  const float* d_probs, uint32_t n, int32_t fixed_iterations,
+                                                  suma_localizer_result* result) {
+  return process_scan(l, d_points, d_labels, d_probs, n, fixed_iterations, result, true);
+}
+
+extern "C" int suma_localizer_window(suma_localizer* l, int32_t origin_ij[2], uint32_t* n_window, uint32_t* rebuilds) {
+  if (!l) return SUMA_ERR_INVALID;
+  if (origin_ij) origin_ij[0] = l->oi, origin_ij[1] = l->oj;
+  if (n_window) *n_window = l->n_window;
+  if (rebuilds) *rebuilds = l->rebuilds;
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_download_window(suma_localizer* l, suma_surfel* host, uint32_t capacity, uint32_t* n) {
+  if (!l) return SUMA_ERR_INVALID;
+  if (!n || (capacity && !host)) return fail(l->c, SUMA_ERR_INVALID, "suma_localizer_download_window: NULL argument");
+  if (!l->have_pose) { /* nothing has been gathered */
+    *n = 0;
+    return SUMA_OK;
+  }
+  return suma_map_download(l->c, host, capacity, n);
+}

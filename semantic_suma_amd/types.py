@@ -142,6 +142,31 @@ class IcpStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LocalizerParams(C.Structure):
+    """``struct suma_localizer_params``: render threshold, the two gates and the motion model of core.Localizer;
+    ``LocalizerParams.defaults(params)`` = suma_localizer_params_default"""
+    _fields_ = [("conf_threshold", f32), ("min_valid_ratio", f32), ("max_outlier_ratio", f32),
+                ("constant_velocity", i32)]
+
+    @classmethod
+    def defaults(cls, params: "SumaParams" = None, **overrides) -> "LocalizerParams":
+        p = cls(conf_threshold=0.0 if params is None else params.confidence_threshold, min_valid_ratio=0.2,
+                max_outlier_ratio=0.85, constant_velocity=1)
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise KeyError(f"unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+
+class LocalizerResult(C.Structure):
+    """``struct suma_localizer_result``: what one localised scan gave (matrices column-major, as the C-ABI has them;
+    core.Localizer.processScan hands them out row-major)"""
+    _fields_ = [("guess", f64 * 16), ("pose", f64 * 16), ("increment", f64 * 16), ("stats", IcpStats),
+                ("valid_ratio", f32), ("outlier_ratio", f32), ("tracked", i32), ("window_rebuilt", i32),
+                ("origin_ij", i32 * 2), ("n_window", u32)]
+
+
 def default_params(**overrides) -> SumaParams:
     """Values of the reference's config/default.xml (same as suma_params_default in suma_types.h)."""
     p = SumaParams(

@@ -1,0 +1,159 @@
+#!/usr/bin/env python
+"""Localisation in a finished map (core.Localizer, csrc/k_localize.hip): maps a synthetic sequence
+(semantic_suma_amd/synth.py) or a KITTI directory (velodyne/*.bin, optionally labels/*.label) with SurfelMapping,
+exports the map in the world frame (optionally voxel-fused) and localises a range of the same or of later scans in it --
+or takes the map from a PLY written by tools/export_map.py (--map).  The map is never changed.  Prints one line per scan
+(position, the two gate ratios, tracked, window rebuilds; the distance to the mapping pose of the same scan where one
+exists) and a JSON summary.  --timing keeps the scans on the device and reports localisation scans/s beside the mapping
+pipeline's scans/s over the same scans in the same run, and the cost of one window rebuild.  Needs a GPU.
+    python tools/localize.py [--map-scans 80] [--first 10] [--scans 60] [--voxel 0.1] [--width 2048] [--kitti sequences/08]
+    python tools/localize.py --map map.ply --start 12.0 0.5 0.0 3.0 --first 11 --scans 20
+    python tools/localize.py --timing                       # 64 x 2048, the 300-scan map, 60 scans
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from semantic_suma_amd import core, kitti, mapio, synth  # noqa: E402
+from semantic_suma_amd.types import LocalizerParams, params_with_size  # noqa: E402
+
+
+def read_scan(args, k):
+    if args.kitti:
+        bins = sorted(f for f in os.listdir(os.path.join(args.kitti, "velodyne")) if f.endswith(".bin"))
+        pts = kitti.read_velodyne(os.path.join(args.kitti, "velodyne", bins[k]))
+        lp = os.path.join(args.kitti, "labels", bins[k][:-4] + ".label")
+        lab, prob = kitti.read_labels(lp, pts.shape[0]) if os.path.exists(lp) else (None, None)
+        return pts, lab, prob
+    return synth.generate_scan(k, n_azimuth=args.width, height=args.height)[:3]
+
+
+def resident(ctx, scan):
+    pts, lab, prob = (None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in scan)
+    n = pts.reshape(-1, 4).shape[0]
+    return ctx.device_array(pts), 0 if lab is None else ctx.device_array(lab), 0 if prob is None else ctx.device_array(prob), n
+
+
+def pose_from(x, y, z, yaw_deg):
+    a = np.deg2rad(yaw_deg)
+    T = np.eye(4)
+    T[:2, :2] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
+    T[:3, 3] = x, y, z
+    return T
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--map", default=None, help="a PLY of tools/export_map.py / mapio.write_ply instead of a mapping run")
+    ap.add_argument("--map-scans", type=int, default=None, help="scans the mapping run integrates (default 80; --timing: 300)")
+    ap.add_argument("--first", type=int, default=None, help="first scan to localise (default: 20 scans before the end of the map)")
+    ap.add_argument("--scans", type=int, default=60, help="scans to localise")
+    ap.add_argument("--kitti", default=None, help="a sequences/XX directory")
+    ap.add_argument("--width", type=int, default=2048)
+    ap.add_argument("--height", type=int, default=64)
+    ap.add_argument("--voxel", type=float, default=0.0, help="voxel size of the exported map in metres; 0: one record per surfel")
+    ap.add_argument("--extent", type=float, default=None, help="submap_extent")
+    ap.add_argument("--dimension", type=int, default=None, help="submap_dimension")
+    ap.add_argument("--iterations", type=int, default=0, help="fixed Gauss-Newton iterations; 0: until convergence")
+    ap.add_argument("--no-motion-model", action="store_true", help="guess = the last pose (constant_velocity = 0)")
+    ap.add_argument("--start", type=float, nargs=4, metavar=("X", "Y", "Z", "YAW_DEG"), default=None,
+                    help="start pose (default: the mapping pose of scan --first; identity with --map)")
+    ap.add_argument("--save-map", default=None, help="write the exported map as a PLY")
+    ap.add_argument("--timing", action="store_true")
+    args = ap.parse_args()
+    over = {k: v for k, v in (("submap_extent", args.extent), ("submap_dimension", args.dimension)) if v is not None}
+    p = params_with_size(args.width, args.height, **over)
+    n_map = args.map_scans if args.map_scans is not None else (300 if args.timing else 80)
+    first = args.first if args.first is not None else (0 if args.map else max(0, n_map - args.scans - 20))
+    ks = list(range(first, first + args.scans))
+    res = dict(width=args.width, height=args.height, first=first, scans=args.scans, voxel_size=args.voxel,
+               fixed_iterations=args.iterations, constant_velocity=int(not args.no_motion_model))
+
+    map_poses = {}
+    if args.map:
+        records, _ = mapio.read_ply(args.map)
+        res["map"] = args.map
+    else:
+        pipe = core.SurfelMapping(p)
+        mapping_s, timed = 0.0, 0
+        for k in range(n_map):
+            sc = read_scan(args, k)
+            if args.timing and k in ks and k > 0:  # the mapping rate over the scans that are localised below, resident
+                d = resident(pipe.ctx, sc)
+                pipe.ctx.synchronize()
+                t = time.perf_counter()
+                pipe.processScanDevice(*d, fixed_iterations=args.iterations)
+                pipe.ctx.synchronize()
+                mapping_s += time.perf_counter() - t
+                timed += 1
+                for a in d[:3]:
+                    if a:
+                        pipe.ctx.device_free(a)
+            else:
+                pipe.processScan(*sc, fixed_iterations=args.iterations)
+            map_poses[k] = pipe.getCurrentPose()
+        t = time.perf_counter()
+        records, st = pipe.map.export_world(voxel_size=args.voxel, stats=True)
+        res.update(map_scans=n_map, export_ms=round(1e3 * (time.perf_counter() - t), 3), export=st)
+        if timed:
+            res["mapping_scans_per_s"] = round(timed / mapping_s, 2)
+        if args.save_map:
+            mapio.write_ply(args.save_map, records)
+        pipe.close()
+
+    loc = core.Localizer(p, LocalizerParams.defaults(p, constant_velocity=int(not args.no_motion_model)))
+    t = time.perf_counter()
+    dropped = loc.setMap(records)
+    res.update(map_records=int(len(records)), dropped=dropped, set_map_ms=round(1e3 * (time.perf_counter() - t), 3))
+    start = pose_from(*args.start) if args.start else map_poses.get(first, np.eye(4))
+    loc.setPose(start)
+    scans = [read_scan(args, k) for k in ks]
+    if args.timing:
+        scans = [resident(loc.ctx, sc) for sc in scans]
+        loc.ctx.synchronize()
+    out = []
+    t = time.perf_counter()
+    for k, sc in zip(ks, scans):
+        try:
+            out.append(loc.processScanDevice(*sc, fixed_iterations=args.iterations) if args.timing
+                       else loc.processScan(*sc, fixed_iterations=args.iterations))
+        except core.SumaError as e:  # a run that has left the map ends on a pose that is no longer finite
+            res.update(lost_at_scan=k, error=str(e))
+            break
+    loc.ctx.synchronize()
+    wall = time.perf_counter() - t
+    worst = 0.0
+    for k, r in zip(ks, out):
+        T = r["pose"]
+        err = float(np.linalg.norm(T[:3, 3] - map_poses[k][:3, 3])) if k in map_poses else float("nan")
+        worst = max(worst, err) if err == err else worst
+        if "first_beyond_half_a_metre" not in res and err > 0.5:
+            res["first_beyond_half_a_metre"] = k
+        print(f"scan {k:5d}  xyz {T[0, 3]:10.3f} {T[1, 3]:10.3f} {T[2, 3]:8.3f}  valid {r['valid_ratio']:.3f} "
+              f"outlier {r['outlier_ratio']:.3f}  tracked {int(r['tracked'])}  rebuilt {int(r['window_rebuilt'])}  "
+              f"origin {r['origin']}  window {r['n_window']}  to mapping pose {err:.3f} m")
+    origin, n_window, rebuilds = loc.window()
+    res.update(tracked=sum(r["tracked"] for r in out), window_rebuilds=sum(r["window_rebuilt"] for r in out),
+               n_window=n_window, worst_distance_to_mapping_pose_m=round(worst, 4))
+    if args.timing and out:
+        res["localisation_scans_per_s"] = round(len(out) / wall, 2)
+        # one window rebuild: the gather of setPose at the pose the run ended on, behind a synchronisation
+        T, times = (start if "lost_at_scan" in res or "first_beyond_half_a_metre" in res else out[-1]["pose"]), []
+        for _ in range(5):
+            loc.ctx.synchronize()
+            t = time.perf_counter()
+            loc.setPose(T)
+            loc.ctx.synchronize()
+            times.append(time.perf_counter() - t)
+        res["window_rebuild_ms"] = [round(1e3 * x, 3) for x in times]
+    loc.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
