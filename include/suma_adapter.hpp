@@ -574,10 +574,60 @@ class Posegraph {
   suma_posegraph_stats stats_{};
 };
 
+/* Place recognition over the scans of a mapping session (suma_place_*, csrc/k_place.hip): addFrame after a scan
+ * (suma_pipeline_frame(s, 0)), queryFrame / query for the k best places with a yaw, Localizer::relocalize to turn them
+ * into a pose. */
+class PlaceIndex {
+ public:
+  explicit PlaceIndex(const suma_place_params* pp = nullptr, int device = 0, uint32_t capacity = 0) {
+    if (suma_place_index_create(pp, device, capacity, &i_) != SUMA_OK)
+      throw std::runtime_error(std::string("suma_place_index_create: ") + suma_last_error(nullptr));
+  }
+  ~PlaceIndex() { suma_place_index_destroy(i_); }
+  PlaceIndex(const PlaceIndex&) = delete;
+  PlaceIndex& operator=(const PlaceIndex&) = delete;
+
+  uint32_t size() const { return suma_place_index_size(i_); }
+  void clear() { chk(suma_place_index_clear(i_), "PlaceIndex::clear"); }
+  void addFrame(suma_ctx* ctx, const suma_frame* frame, uint32_t id) {
+    chk(suma_place_index_add_frame(i_, ctx, frame, id), "PlaceIndex::addFrame");
+  }
+  /* cells n x sectors x rings (sector-major); the norms are made on the device */
+  void upload(const std::vector<float>& cells, const std::vector<uint32_t>& ids) {
+    chk(suma_place_index_upload(i_, cells.data(), ids.data(), (uint32_t)ids.size()), "PlaceIndex::upload");
+  }
+  void download(uint32_t first, uint32_t n, float* cells, float* norms, uint32_t* ids) {
+    chk(suma_place_index_download(i_, first, n, cells, norms, ids), "PlaceIndex::download");
+  }
+  /* the k best (k <= SUMA_PLACE_MAX_MATCHES), leaving out ids in [exclude_lo, exclude_hi] (lo > hi: none) */
+  std::vector<suma_place_match> queryFrame(suma_ctx* ctx, const suma_frame* frame, uint32_t k, uint32_t exclude_lo = 1,
+                                           uint32_t exclude_hi = 0) {
+    std::vector<suma_place_match> m(SUMA_PLACE_MAX_MATCHES);
+    uint32_t n = 0;
+    chk(suma_place_index_query_frame(i_, ctx, frame, exclude_lo, exclude_hi, k, m.data(), &n), "PlaceIndex::queryFrame");
+    m.resize(n);
+    return m;
+  }
+  std::vector<suma_place_match> query(const float* cells, uint32_t k, uint32_t exclude_lo = 1, uint32_t exclude_hi = 0) {
+    std::vector<suma_place_match> m(SUMA_PLACE_MAX_MATCHES);
+    uint32_t n = 0;
+    chk(suma_place_index_query(i_, cells, exclude_lo, exclude_hi, k, m.data(), &n), "PlaceIndex::query");
+    m.resize(n);
+    return m;
+  }
+  suma_place_index* get() const { return i_; }
+
+ private:
+  void chk(int rc, const char* what) const {
+    if (rc != SUMA_OK) throw std::runtime_error(std::string(what) + ": " + suma_place_index_last_error(i_));
+  }
+  suma_place_index* i_ = nullptr;
+};
+
 /* Localisation in a finished world map, which is left alone (suma_localizer_*, csrc/k_localize.hip): setMap bins the
- * records of SurfelMap::exportWorld / a map file into submap tiles on the device, setPose gives the start pose (there is
- * no global relocalisation) and gathers the tiles around it, processScan renders that window from the predicted pose and
- * minimises the scan against it.  Poses cross as column-major double[16] (Eigen::Matrix4d::data()). */
+ * records of SurfelMap::exportWorld / a map file into submap tiles on the device, setPose gives the start pose and
+ * gathers the tiles around it (relocalize finds one from a PlaceIndex instead), processScan renders that window from the
+ * predicted pose and minimises the scan against it.  Poses cross as column-major double[16] (Eigen::Matrix4d::data()). */
 class Localizer {
  public:
   explicit Localizer(const suma_params& p, const suma_localizer_params* lp = nullptr, int device = 0) {
@@ -605,6 +655,16 @@ class Localizer {
     suma_localizer_result r;
     chk(suma_localizer_process_scan(l_, points, labels, probs, n, fixed_iterations, &r), "Localizer::processScan");
     return r;
+  }
+  /* global relocalisation (suma_localizer_relocalize): no setPose is needed.  poses16: one column-major pose per entry
+   * of the index, by entry index.  The result is large (every candidate's match and scan result): it is returned through
+   * the caller's object.  found = 0 leaves the localiser as it was. */
+  void relocalize(const PlaceIndex& index, const std::vector<double>& poses16, const suma_float4* points,
+                  const float* labels, const float* probs, uint32_t n, uint32_t max_candidates,
+                  suma_relocalize_result* out, int32_t fixed_iterations = 0) {
+    chk(suma_localizer_relocalize(l_, index.get(), poses16.data(), (uint32_t)(poses16.size() / 16), points, labels, probs, n,
+                                  max_candidates, fixed_iterations, out),
+        "Localizer::relocalize");
   }
   /* origin tile, records in the window, gathers since setMap */
   void window(int32_t origin_ij[2], uint32_t* n_window, uint32_t* rebuilds) {

@@ -747,8 +747,9 @@ uint64_t suma_checkpoint_digest(const void* payload, uint64_t bytes);
  *      surfels have creation stamp 0 and row 0 of the ctx's pose table is the identity, so the world frame is their
  *      creation frame; the ctx's timestamp is the constant T_loc = active_timestamps + 10.  Nothing is ever fused: the
  *      map, the pose table and the world records are not written, and a run has no length limit (max_poses is not
- *      consumed).  DESIGN.md 12 has the step order and the two limits: a window smaller than the model image's range
- *      localises on what it has, and there is no global relocalisation -- the start pose is the caller's.
+ *      consumed).  DESIGN.md 12 has the step order and its limit: a window smaller than the model image's range
+ *      localises on what it has.  The start pose is the caller's (suma_localizer_set_pose), or comes from place
+ *      recognition against the mapping session's scans (suma_localizer_relocalize, below).
  *      Calls on one localiser are serialised by the caller.  Errors: the library's codes; the text is
  *      suma_last_error(suma_localizer_ctx(l)), or suma_last_error(NULL) after a failed create.
  *      (Kept here, not in suma_types.h, for the reason given at suma_semantic_params.) */
@@ -807,6 +808,98 @@ int suma_localizer_process_scan_device(suma_localizer* l, const suma_float4* d_p
 int suma_localizer_window(suma_localizer* l, int32_t origin_ij[2], uint32_t* n_window, uint32_t* rebuilds);
 /* the window's surfels as the ctx holds them: *n = their number, min(*n, capacity) are copied */
 int suma_localizer_download_window(suma_localizer* l, suma_surfel* host, uint32_t capacity, uint32_t* n);
+
+/* ---- place recognition and global relocalisation: "the sensor was switched on somewhere inside yesterday's map".  A
+ *      place index holds one descriptor per scan of a mapping session: a polar height map about the sensor (sectors x
+ *      rings, the highest kept point of each cell), made on the device from the vertex map of a frame the pipeline
+ *      already holds (suma_pipeline_frame(s, 0) after a scan).  A query scores every entry under every cyclic shift of
+ *      the sectors (one wave per entry, one lane per shift: hence sectors <= 64) and returns the K best places with the
+ *      yaw the shift stands for.  csrc/k_place.hip states the fp32 specification, tests/place_shim.c restates it;
+ *      DESIGN.md 13 has the decomposition and the limits.  The reference has nothing like it.
+ *      The index is an object beside the pipeline: nothing of it enters a pipeline, a checkpoint image or any other
+ *      entry.  It lives on one device; entries that take a ctx run on that ctx's stream (a ctx on another device is
+ *      SUMA_ERR_INVALID), the others on a stream of the index; the index orders its own work across those streams.
+ *      Calls on one index are serialised by the caller.  Errors: the library's codes; the text is
+ *      suma_place_index_last_error(idx) (and suma_last_error(ctx) where a ctx was passed), or suma_last_error(NULL)
+ *      after a failed create.
+ *      (Kept here, not in suma_types.h, for the reason given at suma_semantic_params.) */
+#define SUMA_PLACE_MAX_DIM 64        /* rings and sectors */
+#define SUMA_PLACE_MAX_MATCHES 32    /* K of a query; candidates of a relocalisation */
+typedef struct suma_place_index suma_place_index;
+typedef struct suma_place_params {
+  uint32_t rings;       /* default 20; 1 .. 64 */
+  uint32_t sectors;     /* default 60; 1 .. 64 */
+  float max_range;      /* default 80.0f; finite, > 0: points at or beyond it are left out */
+  float height_offset;  /* default 2.0f; finite: the sensor's height above the ground, so that heights are positive */
+  uint8_t keep_label[SUMA_DRAW_COLORS]; /* a point counts iff keep_label[label] != 0; default all 1 */
+} suma_place_params;
+typedef struct suma_place_match {
+  uint32_t index;   /* entry index: position in the order of insertion */
+  uint32_t id;      /* the caller's id of that entry */
+  float distance;   /* 0 .. 2: 1 - the mean cosine of the column pairs at the best shift */
+  int32_t shift;    /* 0 .. sectors - 1 */
+  float yaw;        /* radians; the pose hypothesis is T_entry * Rz(yaw) */
+} suma_place_match;
+/* 20, 60, 80.0f, 2.0f, all labels kept */
+void suma_place_params_default(suma_place_params* pp);
+/* params NULL = the defaults; capacity = entries to make room for now (it grows).  SUMA_ERR_INVALID before any device is
+ * touched: rings or sectors outside 1 .. 64, a max_range that is not finite and > 0, a height_offset that is not finite */
+int suma_place_index_create(const suma_place_params* params, int hip_device, uint32_t capacity, suma_place_index** out);
+void suma_place_index_destroy(suma_place_index* idx);
+int suma_place_index_clear(suma_place_index* idx);
+uint32_t suma_place_index_size(const suma_place_index* idx);
+const char* suma_place_index_last_error(const suma_place_index* idx);
+/* appends the descriptor of frame's vertex map (labels from its semantic map) with the caller's id; enqueued on the ctx
+ * stream behind the work that made the frame, not waited for (it blocks only when the storage has to grow) */
+int suma_place_index_add_frame(suma_place_index* idx, suma_ctx* ctx, const suma_frame* frame, uint32_t id);
+/* entries first .. first + n - 1: cells n x sectors x rings floats (sector-major), norms n x sectors, ids n; any output
+ * may be NULL.  Blocking. */
+int suma_place_index_download(suma_place_index* idx, uint32_t first, uint32_t n, float* cells, float* norms, uint32_t* ids);
+/* appends n entries from host cells (every cell 0 or in (0, 1000], else SUMA_ERR_INVALID); the norms are made on the
+ * device.  Blocking. */
+int suma_place_index_upload(suma_place_index* idx, const float* cells, const uint32_t* ids, uint32_t n);
+/* the k best entries (1 <= k <= 32) for frame's descriptor, by (distance ascending, entry index ascending), leaving out
+ * the entries whose id lies in [exclude_lo, exclude_hi] (lo > hi: none); *n_out = min(k, entries left).  Blocking. */
+int suma_place_index_query_frame(suma_place_index* idx, suma_ctx* ctx, const suma_frame* frame, uint32_t exclude_lo,
+                                 uint32_t exclude_hi, uint32_t k, suma_place_match* matches, uint32_t* n_out);
+/* the same search for a descriptor given on the host (sectors x rings cells; its norms are made on the device) */
+int suma_place_index_query(suma_place_index* idx, const float* cells_host, uint32_t exclude_lo, uint32_t exclude_hi,
+                           uint32_t k, suma_place_match* matches, uint32_t* n_out);
+/* unsorted: every entry's least distance and its shift for frame's descriptor (size() floats / int32s).  Blocking. */
+int suma_place_index_query_all(suma_place_index* idx, suma_ctx* ctx, const suma_frame* frame, float* dist, int32_t* shift);
+
+/* global relocalisation of a localiser that has a map: (1) K1-K3 of the scan into the localiser's frame, as
+ * suma_localizer_process_scan does; (2) suma_place_index_query_frame with k = max_candidates (1 .. 32), nothing left
+ * out; (3) for each match in order: suma_localizer_set_pose(poses16[index] * Rz(yaw)) and one localisation scan -- each
+ * result is, to the bit, what suma_localizer_set_pose followed by suma_localizer_process_scan gives; (4) among the
+ * candidates with tracked = 1 the one with the least stats.error / (double)stats.valid wins, the earlier one on a tie,
+ * and the localiser is left in its state (pose, identity increment, window, rendered model): the next
+ * suma_localizer_process_scan continues from there.  If none is tracked, found = 0 and the localiser is as it was
+ * before the call: pose, increment, whether it has a pose, window origin, window contents, gather count.
+ * poses16: one column-major 4x4 pose per ENTRY INDEX (the mapping session's trajectory); n_poses must equal the index's
+ * size.  A candidate whose pose suma_localizer_set_pose refuses (outside the grid, window beyond max_surfels) ends the
+ * call with that error and the localiser restored. */
+typedef struct suma_relocalize_candidate {
+  suma_place_match match;
+  int32_t reserved;
+  suma_localizer_result result;
+} suma_relocalize_candidate;
+typedef struct suma_relocalize_result {
+  int32_t found;
+  uint32_t n_tried;   /* candidates tried = matches returned */
+  int32_t winner;     /* index into candidates, -1 when found = 0 */
+  int32_t reserved;
+  suma_place_match match;        /* the winner's (zero when found = 0) */
+  int32_t reserved2;
+  suma_localizer_result result;  /* the winner's */
+  suma_relocalize_candidate candidates[SUMA_PLACE_MAX_MATCHES];
+} suma_relocalize_result;
+int suma_localizer_relocalize(suma_localizer* l, suma_place_index* idx, const double* poses16, uint32_t n_poses,
+                              const suma_float4* points, const float* labels, const float* probs, uint32_t n,
+                              uint32_t max_candidates, int32_t fixed_iterations, suma_relocalize_result* result);
+int suma_localizer_relocalize_device(suma_localizer* l, suma_place_index* idx, const double* poses16, uint32_t n_poses,
+                                     const suma_float4* d_points, const float* d_labels, const float* d_probs, uint32_t n,
+                                     uint32_t max_candidates, int32_t fixed_iterations, suma_relocalize_result* result);
 
 /* ---- per-kernel timing (rv::Stopwatch / SurfelMapping::Stats, SurfelMapping.cpp:183-207):
  *      on = 1: every kernel group is bracketed by HIP events on the ctx stream; on = 2: only the

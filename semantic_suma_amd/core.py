@@ -9,7 +9,8 @@ stand for (PRBonn/semantic_suma, src/core):
     LieGaussNewton   src/core/LieGaussNewton.h:25-76         minimize(objective, T0), pose(), history()
     SurfelMap        src/core/SurfelMap.h:36-78              update / render* / *MapFrame / updatePoses / size / draw
     SurfelMapping    src/core/SurfelMapping.h:47             processScan(scan)
-    Localizer        (no counterpart)                        setMap / setPose / processScan in a finished map
+    Localizer        (no counterpart)                        setMap / setPose / processScan / relocalize in a finished map
+    PlaceIndex       (no counterpart)                        addFrame / queryFrame: place recognition over a session's scans
     Posegraph        src/core/Posegraph.h:10-78              setInitial / addEdge / optimize / poses
 
 Everything here is plumbing: numpy arrays in, ctypes calls into ``libsuma_hip.so`` (hand-written
@@ -28,7 +29,7 @@ import numpy as np
 from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX_LIGHTS, SURFEL_DTYPE, DrawParams,
                     IcpStats, LoopParams, LoopStatus, PosegraphParams, PosegraphStats, SemanticKnnParams,
                     SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats, CheckpointInfo,
-                    LocalizerParams, LocalizerResult)
+                    LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -277,6 +278,26 @@ def lib():
     L.suma_localizer_process_scan_device.argtypes = [vp, vp, vp, vp, u32, i32, lrp]
     L.suma_localizer_window.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
     L.suma_localizer_download_window.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    ppp, pmp = C.POINTER(PlaceParams), C.POINTER(PlaceMatch)
+    L.suma_place_params_default.argtypes = [ppp]
+    L.suma_place_params_default.restype = None
+    L.suma_place_index_create.argtypes = [ppp, C.c_int, u32, pp]
+    L.suma_place_index_destroy.argtypes = [vp]
+    L.suma_place_index_destroy.restype = None
+    L.suma_place_index_clear.argtypes = [vp]
+    L.suma_place_index_size.argtypes = [vp]
+    L.suma_place_index_size.restype = u32
+    L.suma_place_index_last_error.argtypes = [vp]
+    L.suma_place_index_last_error.restype = C.c_char_p
+    L.suma_place_index_add_frame.argtypes = [vp, vp, vp, u32]
+    L.suma_place_index_download.argtypes = [vp, u32, u32, vp, vp, vp]
+    L.suma_place_index_upload.argtypes = [vp, vp, vp, u32]
+    L.suma_place_index_query_frame.argtypes = [vp, vp, vp, u32, u32, u32, pmp, C.POINTER(u32)]
+    L.suma_place_index_query.argtypes = [vp, vp, u32, u32, u32, pmp, C.POINTER(u32)]
+    L.suma_place_index_query_all.argtypes = [vp, vp, vp, vp, vp]
+    rrp = C.POINTER(RelocalizeResult)
+    L.suma_localizer_relocalize.argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, u32, i32, rrp]
+    L.suma_localizer_relocalize_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, u32, i32, rrp]
     _LIB = L
     return L
 
@@ -1454,8 +1475,8 @@ class SurfelMapping:
 class Localizer:
     """Localisation of scans in a finished world map, which is left alone (suma_localizer_*, csrc/k_localize.hip): the
     map is what SurfelMap.export_world / mapio give.  ``setMap`` bins it into submap tiles on the device, ``setPose``
-    gives the start pose (there is no global relocalisation) and gathers the tiles around it, ``processScan`` renders
-    that window from the predicted pose, minimises the scan against it and returns a dict: guess / pose / increment
+    gives the start pose and gathers the tiles around it (``relocalize`` finds one from a PlaceIndex instead),
+    ``processScan`` renders that window from the predicted pose, minimises the scan against it and returns a dict: guess / pose / increment
     (row-major 4x4), stats, valid_ratio, outlier_ratio, tracked, window_rebuilt, origin, n_window.  Nothing is fused, so a
     run has no length limit."""
 
@@ -1526,6 +1547,47 @@ class Localizer:
                        "suma_localizer_process_scan_device")
         return self._result(res)
 
+    @staticmethod
+    def _poses16(poses) -> np.ndarray:
+        """row-major 4x4 poses -> n x 16 column-major doubles"""
+        P = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        return np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(-1, 16)
+
+    def _relocalized(self, res: RelocalizeResult) -> dict:
+        tried = [dict(match=res.candidates[k].match.as_dict(), result=self._result(res.candidates[k].result))
+                 for k in range(res.n_tried)]
+        found = bool(res.found)
+        return dict(found=found, n_tried=int(res.n_tried), winner=int(res.winner),
+                    match=res.match.as_dict() if found else None, result=self._result(res.result) if found else None,
+                    candidates=tried)
+
+    def relocalize(self, index: "PlaceIndex", poses, points, labels=None, probs=None, max_candidates: int = 8,
+                   fixed_iterations: int = 0) -> dict:
+        """global relocalisation (suma_localizer_relocalize): no setPose is needed.  ``poses``: one 4x4 pose per entry of
+        ``index``, by entry index.  Returns found, n_tried, winner, match, result (as processScan's) and candidates (the
+        match and result of every candidate tried).  found = False leaves the localiser as it was."""
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
+        labels = None if labels is None else np.ascontiguousarray(labels, dtype=np.float32)
+        probs = None if probs is None else np.ascontiguousarray(probs, dtype=np.float32)
+        P = self._poses16(poses)
+        res = RelocalizeResult()
+        self.ctx.check(self.L.suma_localizer_relocalize(self.h, index.h, _ptr(P) if P.shape[0] else None, P.shape[0],
+                                                        _ptr(points), _ptr(labels), _ptr(probs), points.shape[0],
+                                                        max_candidates, fixed_iterations, C.byref(res)),
+                       "suma_localizer_relocalize")
+        return self._relocalized(res)
+
+    def relocalizeDevice(self, index: "PlaceIndex", poses, d_points, d_labels, d_probs, n: int, max_candidates: int = 8,
+                         fixed_iterations: int = 0) -> dict:
+        """the same with the scan already resident in HBM and complete"""
+        P = self._poses16(poses)
+        res = RelocalizeResult()
+        self.ctx.check(self.L.suma_localizer_relocalize_device(self.h, index.h, _ptr(P) if P.shape[0] else None, P.shape[0],
+                                                               _dev(d_points), _dev(d_labels), _dev(d_probs), n,
+                                                               max_candidates, fixed_iterations, C.byref(res)),
+                       "suma_localizer_relocalize_device")
+        return self._relocalized(res)
+
     def window(self):
         """(origin tile (i, j), records in the window, gathers since setMap)"""
         ij = np.zeros(2, dtype=np.int32)
@@ -1558,6 +1620,105 @@ class Localizer:
             self.close()
         except Exception:
             pass
+
+
+class PlaceIndex:
+    """Place recognition over the scans of a mapping session (suma_place_*, csrc/k_place.hip): one descriptor per scan --
+    a polar height map about the sensor -- made on the device from a frame the pipeline already holds, and a brute-force
+    search that returns candidate places with a yaw.  ``addFrame(ctx, frame, id)`` after a scan
+    (``SurfelMapping.frame(0)``), ``queryFrame`` / ``query`` for the k best, ``Localizer.relocalize`` to turn them into a
+    pose.  places.save / places.load keep an index with its poses in one file."""
+
+    def __init__(self, place_params: PlaceParams = None, device: int = 0, capacity: int = 0):
+        self.L = lib()
+        self.params = PlaceParams.defaults() if place_params is None else place_params
+        h = C.c_void_p()
+        rc = self.L.suma_place_index_create(C.byref(self.params), device, capacity, C.byref(h))
+        if rc != 0:
+            raise SumaError(f"suma_place_index_create failed ({rc}): {self.L.suma_last_error(None).decode()}")
+        self.h = h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise SumaError(f"{what} failed ({rc}): {self.L.suma_place_index_last_error(self.h).decode()}")
+
+    def size(self) -> int:
+        return self.L.suma_place_index_size(self.h)
+
+    __len__ = size
+
+    def clear(self):
+        self._check(self.L.suma_place_index_clear(self.h), "suma_place_index_clear")
+
+    def addFrame(self, ctx: Context, frame: Frame, id: int):
+        self._check(self.L.suma_place_index_add_frame(self.h, ctx.h, frame.h, id), "suma_place_index_add_frame")
+
+    def download(self, first: int = 0, n: int = None):
+        """-> (cells n x sectors x rings, norms n x sectors, ids n)"""
+        n = self.size() - first if n is None else n
+        S, R = self.params.sectors, self.params.rings
+        cells, norms = np.zeros((n, S, R), dtype=np.float32), np.zeros((n, S), dtype=np.float32)
+        ids = np.zeros(n, dtype=np.uint32)
+        self._check(self.L.suma_place_index_download(self.h, first, n, _ptr(cells), _ptr(norms), _ptr(ids)),
+                    "suma_place_index_download")
+        return cells, norms, ids
+
+    def upload(self, cells, ids):
+        """appends entries from host cells (n x sectors x rings); their norms are made on the device"""
+        S, R = self.params.sectors, self.params.rings
+        cells = np.ascontiguousarray(cells, dtype=np.float32).reshape(-1, S, R)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if ids.shape[0] != cells.shape[0]:
+            raise ValueError("one id per entry")
+        self._check(self.L.suma_place_index_upload(self.h, _ptr(cells), _ptr(ids), cells.shape[0]),
+                    "suma_place_index_upload")
+
+    @staticmethod
+    def _window(exclude):
+        return (1, 0) if exclude is None else (int(exclude[0]), int(exclude[1]))
+
+    def queryFrame(self, ctx: Context, frame: Frame, k: int = 8, exclude=None) -> list:
+        """the k best entries as dicts (index, id, distance, shift, yaw); ``exclude``: an (lo, hi) window of ids"""
+        m, n = (PlaceMatch * PLACE_MAX_MATCHES)(), C.c_uint32(0)
+        lo, hi = self._window(exclude)
+        self._check(self.L.suma_place_index_query_frame(self.h, ctx.h, frame.h, lo, hi, k, m, C.byref(n)),
+                    "suma_place_index_query_frame")
+        return [m[i].as_dict() for i in range(n.value)]
+
+    def query(self, cells, k: int = 8, exclude=None) -> list:
+        """the same search for a descriptor given on the host (sectors x rings)"""
+        cells = np.ascontiguousarray(cells, dtype=np.float32).reshape(self.params.sectors, self.params.rings)
+        m, n = (PlaceMatch * PLACE_MAX_MATCHES)(), C.c_uint32(0)
+        lo, hi = self._window(exclude)
+        self._check(self.L.suma_place_index_query(self.h, _ptr(cells), lo, hi, k, m, C.byref(n)),
+                    "suma_place_index_query")
+        return [m[i].as_dict() for i in range(n.value)]
+
+    def queryAll(self, ctx: Context, frame: Frame):
+        """unsorted: (every entry's least distance, its shift)"""
+        n = self.size()
+        dist, shift = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int32)
+        self._check(self.L.suma_place_index_query_all(self.h, ctx.h, frame.h, _ptr(dist), _ptr(shift)),
+                    "suma_place_index_query_all")
+        return dist, shift
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.suma_place_index_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def place_yaw_pose(pose, yaw: float) -> np.ndarray:
+    """pose . Rz(yaw): the pose hypothesis of a match (row-major 4x4; numpy's cos / sin, for display and tools)"""
+    Rz = np.eye(4)
+    Rz[:2, :2] = [[np.cos(yaw), -np.sin(yaw)], [np.sin(yaw), np.cos(yaw)]]
+    return np.asarray(pose, dtype=np.float64) @ Rz
 
 
 class Posegraph:

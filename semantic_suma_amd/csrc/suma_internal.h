@@ -558,6 +558,28 @@ int localize_gather(suma_ctx* c, LocMap* m, const std::vector<LocSpan>& spans, u
 /* the cell (i, j) of a position; false: non-finite or outside the grid */
 bool localize_cell(float extent, float x, float y, float z, int32_t* i, int32_t* j);
 
+/* k_place.hip (the specification is there): what kp_describe reads of suma_place_params, with the two quotients made
+ * once on the host and the label mask as bits */
+struct PlaceArgs {
+  uint32_t R, S;
+  float max_range, height_offset;
+  float ring_scale;   /* (float)R / max_range */
+  float sector_scale; /* (float)S / (2.0f * SUMA_PI_F) */
+  uint32_t keep[(SUMA_DRAW_COLORS + 31) / 32];
+};
+/* zeroes the entry (S*R cells + S norms), then cells and norms of frame f into it */
+hipError_t launch_kp_describe(hipStream_t st, const suma_frame* f, const PlaceArgs& a, float* entry);
+hipError_t launch_kp_norms(hipStream_t st, float* entries, uint32_t n_entries, uint32_t S, uint32_t R);
+/* per entry: the least distance over the shifts and the shift */
+hipError_t launch_kp_search(hipStream_t st, const float* db, uint32_t n_entries, const float* q, uint32_t S, uint32_t R,
+                            float* dist, int32_t* shift);
+/* the K best by (dist, index) outside the id window into out (yaw left 0), *n_out = how many */
+hipError_t launch_kp_topk(hipStream_t st, const float* dist, const int32_t* shift, const uint32_t* ids, uint32_t n_entries,
+                          uint32_t lo, uint32_t hi, uint32_t K, suma_place_match* out, uint32_t* n_out);
+/* suma_place.hip: the pose hypothesis of a match, T_entry * Rz(yaw), in mat4_mul's operation order with
+ * sdm_cos_d / sdm_sin_d of (double)yaw */
+void place_hypothesis(const double T_entry[16], float yaw, double out[16]);
+
 /* suma_api.hip: suma_icp_set_data + suma_icp_minimize on the given frames with processScan's fixed-iteration override
  * (fixed_iterations > 0: exactly that many iterations, no stopping test) */
 int icp_minimize_frames(suma_ctx* c, const suma_frame* current, const suma_frame* model, const double T0[16],

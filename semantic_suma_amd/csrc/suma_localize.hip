@@ -165,7 +165,7 @@ extern "C" int suma_localizer_set_pose(suma_localizer* l, const double T[16]) {
 }
 
 static int process_scan(suma_localizer* l, const suma_float4* points, const float* labels, const float* probs, uint32_t n,
-                        int32_t fixed_iterations, suma_localizer_result* res, bool on_device) {
+                        int32_t fixed_iterations, suma_localizer_result* res, bool on_device, bool frame_ready = false) {
   if (!l) return SUMA_ERR_INVALID;
   suma_ctx* c = l->c;
   if (!res) return fail(c, SUMA_ERR_INVALID, "suma_localizer_process_scan: NULL result");
@@ -204,9 +204,10 @@ static int process_scan(suma_localizer* l, const suma_float4* points, const floa
   suma_icp_stats st;
   memset(&st, 0, sizeof(st));
   if (l->n_window) {
-    /* 3. K1-K3 at T_loc */
-    int r = on_device ? suma_preprocess_device(c, points, labels, probs, n, c->timestamp, l->frame)
-                      : suma_preprocess(c, points, labels, probs, n, c->timestamp, l->frame);
+    /* 3. K1-K3 at T_loc (a relocalisation has made them once for all its candidates) */
+    int r = frame_ready ? SUMA_OK
+            : on_device ? suma_preprocess_device(c, points, labels, probs, n, c->timestamp, l->frame)
+                        : suma_preprocess(c, points, labels, probs, n, c->timestamp, l->frame);
     if (r) return r;
     /* 4. the model: the window seen from the guess */
     r = suma_map_render_inactive(c, gf, l->lp.conf_threshold);
@@ -263,6 +264,125 @@ extern "C" int suma_localizer_process_scan_device(suma_localizer* l, const suma_
                                                   const float* d_probs, uint32_t n, int32_t fixed_iterations,
                                                   suma_localizer_result* result) {
   return process_scan(l, d_points, d_labels, d_probs, n, fixed_iterations, result, true);
+}
+
+/* ---- global relocalisation (include/suma_hip.h states the steps) ---- */
+namespace {
+
+/* what a relocalisation that finds nothing has to put back */
+struct LocSaved {
+  double pose[16], increment[16];
+  bool have_pose, first;
+  int32_t oi, oj;
+  uint32_t n_window, rebuilds;
+  std::vector<LocSpan> spans;
+};
+
+void loc_save(const suma_localizer* l, LocSaved* s) {
+  memcpy(s->pose, l->pose, sizeof(s->pose));
+  memcpy(s->increment, l->increment, sizeof(s->increment));
+  s->have_pose = l->have_pose, s->first = l->first;
+  s->oi = l->oi, s->oj = l->oj;
+  s->n_window = l->n_window, s->rebuilds = l->rebuilds;
+  s->spans = l->spans;
+}
+
+/* the window is a function of the map and the origin: gathering it again at the saved origin gives the saved bytes */
+int loc_restore(suma_localizer* l, const LocSaved& s) {
+  int r = SUMA_OK;
+  if (s.have_pose && (l->oi != s.oi || l->oj != s.oj || !l->have_pose)) r = gather_window(l, s.oi, s.oj);
+  memcpy(l->pose, s.pose, sizeof(s.pose));
+  memcpy(l->increment, s.increment, sizeof(s.increment));
+  l->have_pose = s.have_pose, l->first = s.first;
+  l->oi = s.oi, l->oj = s.oj;
+  l->n_window = s.n_window, l->rebuilds = s.rebuilds;
+  l->spans = s.spans;
+  return r;
+}
+
+int relocalize(suma_localizer* l, suma_place_index* idx, const double* poses16, uint32_t n_poses, const suma_float4* points,
+               const float* labels, const float* probs, uint32_t n, uint32_t max_candidates, int32_t fixed_iterations,
+               suma_relocalize_result* res, bool on_device) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (!res) return fail(c, SUMA_ERR_INVALID, "suma_localizer_relocalize: NULL result");
+  if (!idx) return fail(c, SUMA_ERR_INVALID, "suma_localizer_relocalize: NULL place index");
+  if (n && !points) return fail(c, SUMA_ERR_INVALID, "suma_localizer_relocalize: NULL points with n > 0");
+  if (!l->have_map) return fail(c, SUMA_ERR_INVALID, "suma_localizer_relocalize: no map (suma_localizer_set_map)");
+  if (max_candidates < 1 || max_candidates > SUMA_PLACE_MAX_MATCHES)
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_relocalize: max_candidates must be 1 .. 32");
+  if (n_poses != suma_place_index_size(idx) || (n_poses && !poses16))
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_relocalize: one pose per entry of the index is needed (n_poses = " +
+                                     std::to_string(n_poses) + ", entries = " + std::to_string(suma_place_index_size(idx)) + ")");
+  memset(res, 0, sizeof(*res));
+  res->winner = -1;
+  /* 1. K1-K3 at T_loc */
+  int r = on_device ? suma_preprocess_device(c, points, labels, probs, n, c->timestamp, l->frame)
+                    : suma_preprocess(c, points, labels, probs, n, c->timestamp, l->frame);
+  if (r) return r;
+  /* 2. the candidate places */
+  suma_place_match matches[SUMA_PLACE_MAX_MATCHES];
+  uint32_t n_matches = 0;
+  r = suma_place_index_query_frame(idx, c, l->frame, 1u, 0u, max_candidates, matches, &n_matches);
+  if (r) return r;
+  LocSaved saved;
+  loc_save(l, &saved);
+  /* 3. each candidate is a start pose and one scan */
+  int best = -1;
+  double best_score = 0.0;
+  for (uint32_t k = 0; k < n_matches; ++k) {
+    double T[16];
+    place_hypothesis(poses16 + 16 * (size_t)matches[k].index, matches[k].yaw, T);
+    suma_relocalize_candidate* cand = &res->candidates[k];
+    cand->match = matches[k];
+    r = suma_localizer_set_pose(l, T);
+    if (!r) r = process_scan(l, points, labels, probs, n, fixed_iterations, &cand->result, on_device, true);
+    if (r) {
+      const std::string why = c->err;
+      loc_restore(l, saved);
+      return fail(c, r, why);
+    }
+    res->n_tried = k + 1u;
+    if (!cand->result.tracked) continue;
+    const double score = cand->result.stats.error / (double)cand->result.stats.valid;
+    if (best < 0 || score < best_score) best = (int)k, best_score = score;
+  }
+  /* 4. */
+  if (best < 0) return loc_restore(l, saved);
+  const suma_localizer_result& w = res->candidates[best].result;
+  if ((uint32_t)best + 1u != n_matches) { /* a later candidate has left its state: back to the winner's */
+    if (l->oi != w.origin_ij[0] || l->oj != w.origin_ij[1]) {
+      r = gather_window(l, w.origin_ij[0], w.origin_ij[1]);
+      if (r) return r;
+    }
+    memcpy(l->pose, w.pose, sizeof(l->pose));
+    memcpy(l->increment, w.increment, sizeof(l->increment));
+    l->first = false;
+    float gf[16];
+    mat4_cast_f(w.guess, gf);
+    r = suma_map_render_inactive(c, gf, l->lp.conf_threshold); /* the model frame as the winner's scan left it */
+    if (r) return r;
+  }
+  res->found = 1;
+  res->winner = best;
+  res->match = res->candidates[best].match;
+  res->result = w;
+  return SUMA_OK;
+}
+
+}  // namespace
+
+extern "C" int suma_localizer_relocalize(suma_localizer* l, suma_place_index* idx, const double* poses16, uint32_t n_poses,
+                                         const suma_float4* points, const float* labels, const float* probs, uint32_t n,
+                                         uint32_t max_candidates, int32_t fixed_iterations, suma_relocalize_result* result) {
+  return relocalize(l, idx, poses16, n_poses, points, labels, probs, n, max_candidates, fixed_iterations, result, false);
+}
+
+extern "C" int suma_localizer_relocalize_device(suma_localizer* l, suma_place_index* idx, const double* poses16,
+                                                uint32_t n_poses, const suma_float4* d_points, const float* d_labels,
+                                                const float* d_probs, uint32_t n, uint32_t max_candidates,
+                                                int32_t fixed_iterations, suma_relocalize_result* result) {
+  return relocalize(l, idx, poses16, n_poses, d_points, d_labels, d_probs, n, max_candidates, fixed_iterations, result, true);
 }
 
 extern "C" int suma_localizer_window(suma_localizer* l, int32_t origin_ij[2], uint32_t* n_window, uint32_t* rebuilds) {

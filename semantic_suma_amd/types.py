@@ -167,6 +167,57 @@ class LocalizerResult(C.Structure):
                 ("origin_ij", i32 * 2), ("n_window", u32)]
 
 
+PLACE_MAX_DIM = 64       # SUMA_PLACE_MAX_DIM: rings and sectors
+PLACE_MAX_MATCHES = 32   # SUMA_PLACE_MAX_MATCHES
+# is_dynamic_label (csrc/dev_math.h): the moving classes K1 drops at the start of a run
+DYNAMIC_LABELS = (10, 11, 13, 15, 18, 20, 30, 31, 32)
+
+
+class PlaceParams(C.Structure):
+    """``struct suma_place_params``: geometry and label mask of a place descriptor (core.PlaceIndex);
+    ``PlaceParams.defaults()`` = suma_place_params_default"""
+    _fields_ = [("rings", u32), ("sectors", u32), ("max_range", f32), ("height_offset", f32),
+                ("keep_label", C.c_uint8 * DRAW_COLORS)]
+
+    @classmethod
+    def defaults(cls, keep_labels=None, **overrides) -> "PlaceParams":
+        """``keep_labels``: None (all), or the label ids to keep"""
+        p = cls(rings=20, sectors=60, max_range=80.0, height_offset=2.0)
+        keep = set(range(DRAW_COLORS)) if keep_labels is None else {int(l) for l in keep_labels}
+        for l in range(DRAW_COLORS):
+            p.keep_label[l] = 1 if l in keep else 0
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise KeyError(f"unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    @classmethod
+    def static_only(cls, **overrides) -> "PlaceParams":
+        """the defaults without the moving classes (is_dynamic_label)"""
+        return cls.defaults(keep_labels=set(range(DRAW_COLORS)) - set(DYNAMIC_LABELS), **overrides)
+
+
+class PlaceMatch(C.Structure):
+    """``struct suma_place_match``: one candidate place of a query"""
+    _fields_ = [("index", u32), ("id", u32), ("distance", f32), ("shift", i32), ("yaw", f32)]
+
+    def as_dict(self):
+        return dict(index=int(self.index), id=int(self.id), distance=float(self.distance), shift=int(self.shift),
+                    yaw=float(self.yaw))
+
+
+class RelocalizeCandidate(C.Structure):
+    """``struct suma_relocalize_candidate``"""
+    _fields_ = [("match", PlaceMatch), ("reserved", i32), ("result", LocalizerResult)]
+
+
+class RelocalizeResult(C.Structure):
+    """``struct suma_relocalize_result``: what core.Localizer.relocalize found and every candidate it tried"""
+    _fields_ = [("found", i32), ("n_tried", u32), ("winner", i32), ("reserved", i32), ("match", PlaceMatch),
+                ("reserved2", i32), ("result", LocalizerResult), ("candidates", RelocalizeCandidate * PLACE_MAX_MATCHES)]
+
+
 def default_params(**overrides) -> SumaParams:
     """Values of the reference's config/default.xml (same as suma_params_default in suma_types.h)."""
     p = SumaParams(

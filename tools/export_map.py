@@ -4,9 +4,11 @@
 -- active surfels and every parked submap tile -- in the world frame on the GPU (SurfelMap.export_world,
 csrc/k_world.hip) and writes it as a binary PLY (semantic_suma_amd/mapio.py).  Prints the export's stats and the wall
 time of the export alone; --compare also times the host route (getAllSurfels + per-tile downloads + a numpy transform).
-Needs a GPU.
+--places FILE adds every scan's frame to a place index (core.PlaceIndex, csrc/k_place.hip) right behind the scan and
+writes it with the final trajectory -- the pose table, i.e. with loop closing the poses after integration -- for
+tools/localize.py --relocalize (semantic_suma_amd/places.py).  Needs a GPU.
     python tools/export_map.py --out map.ply [--scans 40] [--kitti sequences/08] [--voxel 0.2] [--min-confidence 0]
-                               [--close-loops] [--width 2048] [--compare]
+                               [--close-loops] [--width 2048] [--compare] [--places map.places.npz]
 """
 import argparse
 import json
@@ -17,8 +19,8 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from semantic_suma_amd import core, kitti, mapio, synth  # noqa: E402
-from semantic_suma_amd.types import SURFEL_DTYPE, LoopParams, params_with_size  # noqa: E402
+from semantic_suma_amd import core, kitti, mapio, places, synth  # noqa: E402
+from semantic_suma_amd.types import SURFEL_DTYPE, LoopParams, PlaceParams, params_with_size  # noqa: E402
 
 
 def scans(args):
@@ -63,11 +65,16 @@ def main():
     ap.add_argument("--close-loops", action="store_true")
     ap.add_argument("--repeat", type=int, default=3, help="timed exports (the first one allocates the scratch)")
     ap.add_argument("--compare", action="store_true", help="also time the host route")
+    ap.add_argument("--places", default=None, help="write a place index of every scan with the final trajectory (.npz)")
+    ap.add_argument("--place-range", type=float, default=80.0, help="max_range of the place descriptor in metres")
     args = ap.parse_args()
     p = params_with_size(args.width, 64)
     pipe = core.SurfelMapping(p, loop_params=LoopParams.defaults() if args.close_loops else None)
-    for pts, lab, prob in scans(args):
+    index = core.PlaceIndex(PlaceParams.defaults(max_range=args.place_range), capacity=args.scans) if args.places else None
+    for k, (pts, lab, prob) in enumerate(scans(args)):
         pipe.processScan(pts, lab, prob)
+        if index is not None:
+            index.addFrame(pipe.ctx, pipe.frame(0), k)
     smap = pipe.map
     times = []
     for _ in range(max(1, args.repeat)):
@@ -77,6 +84,9 @@ def main():
     mapio.write_ply(args.out, world)
     res = dict(stats=st, voxel_size=args.voxel, export_wall_ms=[round(1e3 * x, 3) for x in times], out=args.out,
                bytes=os.path.getsize(args.out))
+    if index is not None:
+        places.save(args.places, index, np.asarray(smap.poses(), dtype=np.float64)[:index.size()])
+        res.update(places=args.places, place_entries=index.size())
     if args.compare:
         t = time.perf_counter()
         pts = host_route(smap, p.max_poses)

@@ -5,10 +5,14 @@ exports the map in the world frame (optionally voxel-fused) and localises a rang
 or takes the map from a PLY written by tools/export_map.py (--map).  The map is never changed.  Prints one line per scan
 (position, the two gate ratios, tracked, window rebuilds; the distance to the mapping pose of the same scan where one
 exists) and a JSON summary.  --timing keeps the scans on the device and reports localisation scans/s beside the mapping
-pipeline's scans/s over the same scans in the same run, and the cost of one window rebuild.  Needs a GPU.
+pipeline's scans/s over the same scans in the same run, and the cost of one window rebuild.  --relocalize starts without
+a start pose: the first scan goes through Localizer.relocalize against a place index (core.PlaceIndex) -- the mapping
+run's own scans, or with --map the file tools/export_map.py --places wrote (--places).  Needs a GPU.
     python tools/localize.py [--map-scans 80] [--first 10] [--scans 60] [--voxel 0.1] [--width 2048] [--kitti sequences/08]
     python tools/localize.py --map map.ply --start 12.0 0.5 0.0 3.0 --first 11 --scans 20
     python tools/localize.py --timing                       # 64 x 2048, the 300-scan map, 60 scans
+    python tools/localize.py --relocalize [--candidates 8]  # no setPose: the start comes from place recognition
+    python tools/localize.py --map map.ply --places map.places.npz --relocalize --first 11 --scans 20
 """
 import argparse
 import json
@@ -19,8 +23,8 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from semantic_suma_amd import core, kitti, mapio, synth  # noqa: E402
-from semantic_suma_amd.types import LocalizerParams, params_with_size  # noqa: E402
+from semantic_suma_amd import core, kitti, mapio, places, synth  # noqa: E402
+from semantic_suma_amd.types import LocalizerParams, PlaceParams, params_with_size  # noqa: E402
 
 
 def read_scan(args, k):
@@ -65,6 +69,10 @@ def main():
                     help="start pose (default: the mapping pose of scan --first; identity with --map)")
     ap.add_argument("--save-map", default=None, help="write the exported map as a PLY")
     ap.add_argument("--timing", action="store_true")
+    ap.add_argument("--relocalize", action="store_true", help="no start pose: the first scan is relocalised in a place index")
+    ap.add_argument("--places", default=None, help="with --map: the place index tools/export_map.py --places wrote")
+    ap.add_argument("--candidates", type=int, default=8, help="places a relocalisation tries (1 .. 32)")
+    ap.add_argument("--place-range", type=float, default=80.0, help="max_range of the place descriptor in metres")
     args = ap.parse_args()
     over = {k: v for k, v in (("submap_extent", args.extent), ("submap_dimension", args.dimension)) if v is not None}
     p = params_with_size(args.width, args.height, **over)
@@ -75,11 +83,18 @@ def main():
                fixed_iterations=args.iterations, constant_velocity=int(not args.no_motion_model))
 
     map_poses = {}
+    index, entry_poses = None, None
+    if args.relocalize and args.map and not args.places:
+        ap.error("--relocalize with --map needs --places")
     if args.map:
         records, _ = mapio.read_ply(args.map)
         res["map"] = args.map
+        if args.relocalize:
+            index, entry_poses = places.load(args.places)
     else:
         pipe = core.SurfelMapping(p)
+        if args.relocalize:
+            index = core.PlaceIndex(PlaceParams.defaults(max_range=args.place_range), capacity=n_map)
         mapping_s, timed = 0.0, 0
         for k in range(n_map):
             sc = read_scan(args, k)
@@ -97,6 +112,10 @@ def main():
             else:
                 pipe.processScan(*sc, fixed_iterations=args.iterations)
             map_poses[k] = pipe.getCurrentPose()
+            if index is not None:
+                index.addFrame(pipe.ctx, pipe.frame(0), k)
+        if index is not None:
+            entry_poses = np.stack([map_poses[k] for k in range(n_map)])
         t = time.perf_counter()
         records, st = pipe.map.export_world(voxel_size=args.voxel, stats=True)
         res.update(map_scans=n_map, export_ms=round(1e3 * (time.perf_counter() - t), 3), export=st)
@@ -111,7 +130,8 @@ def main():
     dropped = loc.setMap(records)
     res.update(map_records=int(len(records)), dropped=dropped, set_map_ms=round(1e3 * (time.perf_counter() - t), 3))
     start = pose_from(*args.start) if args.start else map_poses.get(first, np.eye(4))
-    loc.setPose(start)
+    if not args.relocalize:
+        loc.setPose(start)
     scans = [read_scan(args, k) for k in ks]
     if args.timing:
         scans = [resident(loc.ctx, sc) for sc in scans]
@@ -120,6 +140,19 @@ def main():
     t = time.perf_counter()
     for k, sc in zip(ks, scans):
         try:
+            if args.relocalize and not out:  # the first scan: no pose yet
+                t_rel = time.perf_counter()
+                rel = (loc.relocalizeDevice if args.timing else loc.relocalize)(
+                    index, entry_poses, *sc, max_candidates=args.candidates, fixed_iterations=args.iterations)
+                res["relocalisation"] = dict(found=rel["found"], n_tried=rel["n_tried"], winner=rel["winner"],
+                                             match=rel["match"], ms=round(1e3 * (time.perf_counter() - t_rel), 3),
+                                             tried=[dict(c["match"], tracked=c["result"]["tracked"]) for c in rel["candidates"]])
+                if not rel["found"]:
+                    res.update(lost_at_scan=k, error="the relocalisation found no place")
+                    break
+                start = rel["result"]["pose"]
+                out.append(rel["result"])
+                continue
             out.append(loc.processScanDevice(*sc, fixed_iterations=args.iterations) if args.timing
                        else loc.processScan(*sc, fixed_iterations=args.iterations))
         except core.SumaError as e:  # a run that has left the map ends on a pose that is no longer finite
