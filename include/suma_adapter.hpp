@@ -678,6 +678,50 @@ class Localizer {
     out.resize(n < out.size() ? n : out.size());
     return out;
   }
+  /* change evidence (csrc/k_change.hip): from the next setMap on, every record collects hits / misses / occluded /
+   * label_changes from each tracked scan and from every observeFrame; cp NULL = the defaults */
+  void enableEvidence(const suma_change_params* cp = nullptr) {
+    chk(suma_localizer_enable_evidence(l_, cp), "Localizer::enableEvidence");
+  }
+  void disableEvidence() { chk(suma_localizer_disable_evidence(l_), "Localizer::disableEvidence"); }
+  /* one observation of a data-sized frame of ctx() at the sensor pose T (column-major, world frame) */
+  suma_change_counts observeFrame(const suma_frame* frame, const double T[16]) {
+    suma_change_counts c;
+    chk(suma_localizer_observe_frame(l_, frame, T, &c), "Localizer::observeFrame");
+    return c;
+  }
+  /* the totals of the last processScan's observation; *observed (optional): whether it observed */
+  suma_change_counts lastObservation(bool* observed = nullptr) {
+    suma_change_counts c;
+    int32_t o = 0;
+    chk(suma_localizer_last_observation(l_, &c, &o), "Localizer::lastObservation");
+    if (observed) *observed = o != 0;
+    return c;
+  }
+  /* one entry per record setMap was given, in that order */
+  std::vector<suma_change_evidence> evidence() {
+    uint32_t n = 0;
+    chk(suma_localizer_evidence(l_, nullptr, 0, &n), "Localizer::evidence");
+    std::vector<suma_change_evidence> out(n);
+    if (n) chk(suma_localizer_evidence(l_, out.data(), n, &n), "Localizer::evidence");
+    return out;
+  }
+  void clearEvidence() { chk(suma_localizer_clear_evidence(l_), "Localizer::clearEvidence"); }
+  /* the records the rule keeps (suma_change_prune_mask over evidence(); rule NULL = the defaults); *keep (optional): the
+   * mask, one byte per record */
+  std::vector<suma_world_surfel> prunedMap(const std::vector<suma_world_surfel>& records,
+                                           const suma_change_rule* rule = nullptr, std::vector<uint8_t>* keep = nullptr) {
+    const std::vector<suma_change_evidence> ev = evidence();
+    if (ev.size() != records.size()) throw std::runtime_error("Localizer::prunedMap: one evidence entry per record is needed");
+    std::vector<uint8_t> k(ev.size());
+    if (suma_change_prune_mask(ev.data(), (uint32_t)ev.size(), rule, k.data(), nullptr) != SUMA_OK)
+      throw std::runtime_error(std::string("suma_change_prune_mask: ") + suma_last_error(nullptr));
+    std::vector<suma_world_surfel> out;
+    for (size_t i = 0; i < records.size(); ++i)
+      if (k[i]) out.push_back(records[i]);
+    if (keep) keep->swap(k);
+    return out;
+  }
   suma_localizer* get() const { return l_; }
   suma_ctx* ctx() const { return suma_localizer_ctx(l_); }
 

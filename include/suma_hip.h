@@ -809,6 +809,64 @@ int suma_localizer_window(suma_localizer* l, int32_t origin_ij[2], uint32_t* n_w
 /* the window's surfels as the ctx holds them: *n = their number, min(*n, capacity) are copied */
 int suma_localizer_download_window(suma_localizer* l, suma_surfel* host, uint32_t capacity, uint32_t* n);
 
+/* ---- map maintenance, first step: "which records of yesterday's map are still true?"  While a localiser tracks, each
+ *      record of the world map collects evidence from the scans that look at it: confirmed (a return on it: hit), seen
+ *      through (a return well behind it: miss) or hidden (a return well in front of it: occluded).  The map is still not
+ *      written: the evidence is an array of its own, it comes back in the order of the records suma_localizer_set_map was
+ *      given, and suma_change_prune_mask turns it into the records to keep.  csrc/k_change.hip states the fp32
+ *      specification, tests/change_shim.c restates it; DESIGN.md 14 has the scenario it was measured on and what is out
+ *      of scope (adding new surfaces, removing records from the live window, evidence in checkpoints).  Evidence is off
+ *      unless switched on, and with it on every result of the localiser is bit-identical to a run with it off. */
+typedef struct suma_change_params {
+  float free_margin;     /* default 0.5 m: how much farther than the record a return must lie before the record counts
+                            as seen through (and how much nearer before it counts as hidden); finite, > 0 */
+  float min_view_cos;    /* default 0.3: a record seen at a grazing angle collects no miss; finite, in [0, 1) */
+  float max_range;       /* default 50 m: records farther than this collect nothing; finite, > 0 */
+  int32_t tracked_only;  /* default 1: a scan whose tracked == 0 adds nothing */
+} suma_change_params;
+typedef struct suma_change_evidence {
+  uint32_t hits, misses, occluded, label_changes; /* label_changes: hits whose measured label differs from the record's */
+} suma_change_evidence;
+/* what one observation did with the records of the window; unseen + no_return + occluded + misses + grazing + hits +
+ * near = n_window */
+typedef struct suma_change_counts {
+  uint32_t n_window, unseen, no_return, occluded, misses, grazing, hits, near, label_changes;
+} suma_change_counts;
+typedef struct suma_change_rule {
+  uint32_t min_misses;   /* default 3 */
+  float miss_ratio;      /* default 2.0f */
+} suma_change_rule;
+/* 0.5f, 0.3f, 50.0f, 1 */
+void suma_change_params_default(suma_change_params* cp);
+/* 3, 2.0f */
+void suma_change_rule_default(suma_change_rule* rule);
+/* switches evidence on (cp NULL = the defaults).  SUMA_ERR_INVALID with a message for values outside the ranges above.
+ * It takes effect with the next suma_localizer_set_map, which allocates and zeroes the evidence (16 bytes a kept record)
+ * and keeps the sort's source index (4 bytes a kept record); until then the evidence entries below are SUMA_ERR_INVALID.
+ * Enabling again only replaces the parameters. */
+int suma_localizer_enable_evidence(suma_localizer* l, const suma_change_params* cp);
+/* switches it off and gives the evidence and the source index back */
+int suma_localizer_disable_evidence(suma_localizer* l);
+/* the primitive: one observation of a frame of the localiser's ctx (data image size) at the sensor pose T (column-major,
+ * world frame, finite) over the current window, on the ctx stream behind the work that made the frame; *counts
+ * (optional) = its totals.  It is what a host with poses from elsewhere calls.  An empty window observes nothing. */
+int suma_localizer_observe_frame(suma_localizer* l, const suma_frame* frame, const double T[16], suma_change_counts* counts);
+/* With evidence on, suma_localizer_process_scan(_device) ends with one observation of the scan's own frame at the final
+ * pose, unless the window is empty or tracked_only && !tracked; suma_localizer_relocalize observes nothing (its
+ * candidates are hypotheses).  This returns the last scan's totals and whether it observed (both optional). */
+int suma_localizer_last_observation(suma_localizer* l, suma_change_counts* counts, int32_t* observed);
+/* the evidence in the order of suma_localizer_set_map's records: *n = that call's n (dropped records included, which
+ * stay zero), min(*n, capacity) are copied (suma_map_download's convention).  Blocking. */
+int suma_localizer_evidence(suma_localizer* l, suma_change_evidence* host, uint32_t capacity, uint32_t* n);
+int suma_localizer_evidence_device(suma_localizer* l, suma_change_evidence* d_out, uint32_t capacity, uint32_t* n);
+/* back to zero; a new suma_localizer_set_map clears too */
+int suma_localizer_clear_evidence(suma_localizer* l);
+/* host only, no device -- the rule's one home for C, C++ and Python hosts: keep[k] = 0 iff misses >= min_misses &&
+ * (float)misses > miss_ratio * (float)hits (rule NULL = the defaults; a NaN ratio removes nothing); *n_removed
+ * (optional) = the zeros.  SUMA_ERR_INVALID for NULL arrays with n > 0; the text is suma_last_error(NULL). */
+int suma_change_prune_mask(const suma_change_evidence* evidence, uint32_t n, const suma_change_rule* rule, uint8_t* keep,
+                           uint32_t* n_removed);
+
 /* ---- place recognition and global relocalisation: "the sensor was switched on somewhere inside yesterday's map".  A
  *      place index holds one descriptor per scan of a mapping session: a polar height map about the sensor (sectors x
  *      rings, the highest kept point of each cell), made on the device from the vertex map of a frame the pipeline

@@ -9,7 +9,8 @@ stand for (PRBonn/semantic_suma, src/core):
     LieGaussNewton   src/core/LieGaussNewton.h:25-76         minimize(objective, T0), pose(), history()
     SurfelMap        src/core/SurfelMap.h:36-78              update / render* / *MapFrame / updatePoses / size / draw
     SurfelMapping    src/core/SurfelMapping.h:47             processScan(scan)
-    Localizer        (no counterpart)                        setMap / setPose / processScan / relocalize in a finished map
+    Localizer        (no counterpart)                        setMap / setPose / processScan / relocalize in a finished map;
+                                                             enableEvidence / evidence / prunedMap: which records still hold
     PlaceIndex       (no counterpart)                        addFrame / queryFrame: place recognition over a session's scans
     Posegraph        src/core/Posegraph.h:10-78              setInitial / addEdge / optimize / poses
 
@@ -29,7 +30,7 @@ import numpy as np
 from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX_LIGHTS, SURFEL_DTYPE, DrawParams,
                     IcpStats, LoopParams, LoopStatus, PosegraphParams, PosegraphStats, SemanticKnnParams,
                     SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats, CheckpointInfo,
-                    LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
+                    ChangeCounts, ChangeParams, ChangeRule, EVIDENCE_DTYPE, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -278,6 +279,19 @@ def lib():
     L.suma_localizer_process_scan_device.argtypes = [vp, vp, vp, vp, u32, i32, lrp]
     L.suma_localizer_window.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
     L.suma_localizer_download_window.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    cpp, ccp, crp = C.POINTER(ChangeParams), C.POINTER(ChangeCounts), C.POINTER(ChangeRule)
+    L.suma_change_params_default.argtypes = [cpp]
+    L.suma_change_params_default.restype = None
+    L.suma_change_rule_default.argtypes = [crp]
+    L.suma_change_rule_default.restype = None
+    L.suma_localizer_enable_evidence.argtypes = [vp, cpp]
+    L.suma_localizer_disable_evidence.argtypes = [vp]
+    L.suma_localizer_observe_frame.argtypes = [vp, vp, vp, ccp]
+    L.suma_localizer_last_observation.argtypes = [vp, ccp, C.POINTER(i32)]
+    L.suma_localizer_evidence.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_localizer_evidence_device.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_localizer_clear_evidence.argtypes = [vp]
+    L.suma_change_prune_mask.argtypes = [vp, u32, crp, vp, C.POINTER(u32)]
     ppp, pmp = C.POINTER(PlaceParams), C.POINTER(PlaceMatch)
     L.suma_place_params_default.argtypes = [ppp]
     L.suma_place_params_default.restype = None
@@ -1472,6 +1486,26 @@ class SurfelMapping:
             pass
 
 
+def prune_mask(evidence: np.ndarray, rule: ChangeRule = None) -> np.ndarray:
+    """suma_change_prune_mask: bool per record, False = removed by the rule (None: the defaults).  Host only."""
+    ev = np.ascontiguousarray(evidence, dtype=EVIDENCE_DTYPE).reshape(-1)
+    keep = np.ones(ev.shape[0], dtype=np.uint8)
+    rc = lib().suma_change_prune_mask(_ptr(ev) if ev.shape[0] else None, ev.shape[0],
+                                      None if rule is None else C.byref(rule), _ptr(keep) if ev.shape[0] else None, None)
+    if rc != 0:
+        raise SumaError(f"suma_change_prune_mask failed ({rc}): {lib().suma_last_error(None).decode()}")
+    return keep.astype(bool)
+
+
+def pruned_map(records: np.ndarray, evidence: np.ndarray, rule: ChangeRule = None):
+    """(records[keep], keep)"""
+    records = np.asarray(records).reshape(-1)
+    if records.shape[0] != np.asarray(evidence).reshape(-1).shape[0]:
+        raise ValueError("one evidence entry per record is needed")
+    keep = prune_mask(evidence, rule)
+    return records[keep], keep
+
+
 class Localizer:
     """Localisation of scans in a finished world map, which is left alone (suma_localizer_*, csrc/k_localize.hip): the
     map is what SurfelMap.export_world / mapio give.  ``setMap`` bins it into submap tiles on the device, ``setPose``
@@ -1603,6 +1637,55 @@ class Localizer:
         self.ctx.check(self.L.suma_localizer_download_window(self.h, _ptr(out) if n else None, n, C.byref(got)),
                        "suma_localizer_download_window")
         return out[:min(n, got.value)]
+
+    # -- change evidence (csrc/k_change.hip)
+    def enableEvidence(self, params: ChangeParams = None):
+        """from the next setMap on, every record of the map collects evidence (hits, misses, occluded, label_changes)
+        from each scan processScan tracks, and from every observeFrame"""
+        self.ctx.check(self.L.suma_localizer_enable_evidence(self.h, None if params is None else C.byref(params)),
+                       "suma_localizer_enable_evidence")
+
+    def disableEvidence(self):
+        self.ctx.check(self.L.suma_localizer_disable_evidence(self.h), "suma_localizer_disable_evidence")
+
+    def observeFrame(self, frame: Frame, pose) -> dict:
+        """one observation of a data-sized frame of this localiser's ctx at a sensor pose (row-major 4x4, world frame)
+        over the current window; returns its totals"""
+        T = _cm(pose, np.float64)
+        cnt = ChangeCounts()
+        self.ctx.check(self.L.suma_localizer_observe_frame(self.h, frame.h, _ptr(T), C.byref(cnt)),
+                       "suma_localizer_observe_frame")
+        return cnt.as_dict()
+
+    def lastObservation(self):
+        """(the totals of the last processScan's observation, whether it observed)"""
+        cnt, obs = ChangeCounts(), C.c_int32(0)
+        self.ctx.check(self.L.suma_localizer_last_observation(self.h, C.byref(cnt), C.byref(obs)),
+                       "suma_localizer_last_observation")
+        return cnt.as_dict(), bool(obs.value)
+
+    def evidence(self) -> np.ndarray:
+        """EVIDENCE_DTYPE, one per record setMap was given, in that order (dropped records stay zero)"""
+        n = C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_evidence(self.h, None, 0, C.byref(n)), "suma_localizer_evidence")
+        out = np.zeros(n.value, dtype=EVIDENCE_DTYPE)
+        if n.value:
+            self.ctx.check(self.L.suma_localizer_evidence(self.h, _ptr(out), n.value, C.byref(n)), "suma_localizer_evidence")
+        return out
+
+    def evidenceDevice(self, d_out, capacity: int) -> int:
+        """the same into a device buffer of ``capacity`` entries (an address or a torch tensor); returns the map's n"""
+        n = C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_evidence_device(self.h, _dev(d_out), capacity, C.byref(n)),
+                       "suma_localizer_evidence_device")
+        return n.value
+
+    def clearEvidence(self):
+        self.ctx.check(self.L.suma_localizer_clear_evidence(self.h), "suma_localizer_clear_evidence")
+
+    def prunedMap(self, records: np.ndarray, rule: ChangeRule = None):
+        """(records[keep], keep) by suma_change_prune_mask over evidence(); ``records``: what setMap was given"""
+        return pruned_map(records, self.evidence(), rule)
 
     def modelFrame(self) -> Frame:
         """the window as the last scan's render saw it (the ctx's oldMapFrame)"""

@@ -106,6 +106,13 @@ SDEV bool is_dynamic_label(float l) {
          l == 31.0f || l == 32.0f;
 }
 
+/* the label a semantic texel / surfel stands for (k_world.hip states the rule, step 1 of the world export): the red
+ * channel holds label / 255; anything outside 0 .. 259, NaN included, is label 0 */
+SDEV uint32_t world_label(float r) {
+  const float t = r * 255.0f + 0.5f;
+  return (t >= 0.0f && t < 260.0f) ? (uint32_t)t : 0u;
+}
+
 /* 24-bit unorm depth (GL_DEPTH24_STENCIL8 renderbuffers of the reference) */
 /* nearest-even of the fp32 product (v_rndne_f32): the rule of a real GL implementation (Mesa llvmpipe, pinned in
  * round 4: DESIGN.md section 2); rounds 1-3 used (uint32_t)(zw * 16777215.0f + 0.5f), whose fp32 add rounds twice */

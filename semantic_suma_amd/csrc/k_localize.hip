@@ -154,8 +154,10 @@ __global__ void __launch_bounds__(LOC_THREADS)
 }
 
 /* ---- host side ---- */
-int localize_bin(suma_ctx* c, const suma_world_surfel* d_records, uint32_t n, LocMap* m) {
+int localize_bin(suma_ctx* c, const suma_world_surfel* d_records, uint32_t n, LocMap* m, bool keep_evidence) {
   LocMap nm;
+  nm.has_evidence = keep_evidence;
+  nm.n_total = n;
   if (n == 0) {
     nm.spans = std::move(m->spans);
     *m = std::move(nm);
@@ -214,6 +216,12 @@ int localize_bin(suma_ctx* c, const suma_world_surfel* d_records, uint32_t n, Lo
     kl_counts<<<(n_tiles + LOC_THREADS - 1) / LOC_THREADS, LOC_THREADS, 0, st>>>(d_dir, n_tiles, nm.n_kept);
     kl_permute<<<(nm.n_kept + LOC_THREADS - 1) / LOC_THREADS, LOC_THREADS, 0, st>>>(rec, idx.current(), nm.n_kept, nm.sorted);
     HIP_TRY(c, hipGetLastError());
+    if (keep_evidence) { /* the sort's source index outlives the scratch, and the evidence starts at zero */
+      HIP_TRY(c, nm.src_idx.alloc(nm.n_kept));
+      HIP_TRY(c, nm.evidence.alloc(nm.n_kept));
+      HIP_TRY(c, hipMemcpyAsync(nm.src_idx, idx.current(), (size_t)nm.n_kept * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(c, hipMemsetAsync(nm.evidence, 0, (size_t)nm.n_kept * sizeof(suma_change_evidence), st));
+    }
     HIP_TRY(c, hipMemcpyAsync(nm.dir.data(), d_dir, n_tiles * sizeof(LocTile), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     /* what the window look-up relies on, checked once: ascending keys, runs that tile [0, n_kept) */

@@ -76,10 +76,7 @@ SDEV const float4* world_source(const WorldArgs& a, uint32_t s) {
   const WorldSpan sp = a.spans[lo];
   return reinterpret_cast<const float4*>(sp.base + (s - sp.start));
 }
-SDEV uint32_t world_label(float r) {
-  const float t = r * 255.0f + 0.5f;
-  return (t >= 0.0f && t < 260.0f) ? (uint32_t)t : 0u;
-}
+/* world_label (step 1's rule) is in dev_math.h: k_change.hip reads labels by it too */
 SDEV uint32_t world_weight(float w) {
   const float c = (w > 0.0f) ? ((w < 1.0f) ? w : 1.0f) : 0.0f; /* NaN: 0 */
   return (uint32_t)__builtin_rintf(c * 65535.0f);

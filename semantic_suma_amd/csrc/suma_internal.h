@@ -547,9 +547,15 @@ struct LocMap {
   std::vector<LocTile> dir; /* the host's copy of the directory */
   uint32_t n_kept = 0, n_dropped = 0;
   DevBuf<LocSpan> spans;    /* the span table of the last gather */
+  /* change evidence (k_change.hip), only in a map binned with keep_evidence: one zeroed word per sorted record, and the
+   * sort's source index (4 bytes a record), which a map without evidence gives back */
+  bool has_evidence = false;
+  uint32_t n_total = 0;     /* records of the caller's array, dropped ones included */
+  DevBuf<suma_change_evidence> evidence;
+  DevBuf<uint32_t> src_idx;
 };
 /* bins n device records (only read) into *m on the ctx stream; blocking.  A failure leaves *m as it was */
-int localize_bin(suma_ctx* c, const suma_world_surfel* d_records, uint32_t n, LocMap* m);
+int localize_bin(suma_ctx* c, const suma_world_surfel* d_records, uint32_t n, LocMap* m, bool keep_evidence = false);
 /* the window's tiles looked up in the directory: spans ascending by (i, then j), *total = records */
 void localize_window_spans(const LocMap& m, int32_t oi, int32_t oj, int32_t dim, std::vector<LocSpan>* spans,
                            uint64_t* total);
@@ -557,6 +563,13 @@ void localize_window_spans(const LocMap& m, int32_t oi, int32_t oj, int32_t dim,
 int localize_gather(suma_ctx* c, LocMap* m, const std::vector<LocSpan>& spans, uint32_t total);
 /* the cell (i, j) of a position; false: non-finite or outside the grid */
 bool localize_cell(float extent, float x, float y, float z, int32_t* i, int32_t* j);
+
+/* k_change.hip (the specification is there): one observation of frame f at pose T over the first `total` window records
+ * of the span table in m.spans, totals added to the 9 words at d_totals; and m's evidence into source order, into a zeroed
+ * block of m.n_total words */
+hipError_t launch_kc_observe(suma_ctx* c, const LocMap& m, uint32_t n_spans, uint32_t total, const suma_frame* f,
+                             const double T[16], const suma_change_params& cp, uint32_t* d_totals);
+hipError_t launch_kc_scatter(suma_ctx* c, const LocMap& m, suma_change_evidence* d_out);
 
 /* k_place.hip (the specification is there): what kp_describe reads of suma_place_params, with the two quotients made
  * once on the host and the label mask as bits */

@@ -27,6 +27,14 @@ struct suma_localizer {
   int32_t oi = 0, oj = 0;
   uint32_t n_window = 0, rebuilds = 0;
   std::vector<LocSpan> spans;
+  /* change evidence (k_change.hip): wanted from the next set_map on; the map says whether it has it */
+  bool ev_wanted = false;
+  suma_change_params cp;
+  DevBuf<uint32_t> ev_totals;             /* the nine totals of one observation */
+  PinnedBuf<uint32_t> ev_totals_h;
+  DevBuf<suma_change_evidence> ev_source; /* the evidence in source order, made by every download */
+  suma_change_counts last_counts;
+  int32_t last_observed = 0;
 };
 
 namespace {
@@ -55,6 +63,39 @@ int gather_window(suma_localizer* l, int32_t oi, int32_t oj) {
   l->n_window = (uint32_t)total;
   l->rebuilds += 1;
   return SUMA_OK;
+}
+
+/* one observation over the current window; counts may be NULL.  The caller has checked that the map has evidence */
+int observe(suma_localizer* l, const suma_frame* f, const double T[16], suma_change_counts* counts) {
+  suma_ctx* c = l->c;
+  suma_change_counts out;
+  memset(&out, 0, sizeof(out));
+  if (l->n_window) {
+    int r = grow(c, l->ev_totals, 9, {c->stream});
+    if (r < 0) return r;
+    r = grow(c, l->ev_totals_h, 9, {c->stream});
+    if (r < 0) return r;
+    if (c->gate_pending) HIP_TRY(c, flush_gate(c));
+    const_cast<suma_frame*>(f)->last_access = ++c->enq_seq;
+    HIP_TRY(c, hipMemsetAsync(l->ev_totals, 0, 9 * sizeof(uint32_t), c->stream));
+    {
+      ProfScope ps(c, "change_observe", 64.0 * l->n_window + 48.0 * f->width * f->height);
+      HIP_TRY(c, launch_kc_observe(c, l->map, (uint32_t)l->spans.size(), l->n_window, f, T, l->cp, l->ev_totals));
+    }
+    HIP_TRY(c, hipMemcpyAsync(l->ev_totals_h, l->ev_totals, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    memcpy(&out, l->ev_totals_h.p, sizeof(out));
+  }
+  if (counts) *counts = out;
+  return SUMA_OK;
+}
+
+int change_params_check(const suma_change_params& q, std::string* why) {
+  if (!(std::isfinite(q.free_margin) && q.free_margin > 0.0f)) *why = "free_margin must be finite and > 0";
+  else if (!(std::isfinite(q.min_view_cos) && q.min_view_cos >= 0.0f && q.min_view_cos < 1.0f)) *why = "min_view_cos must lie in [0, 1)";
+  else if (!(std::isfinite(q.max_range) && q.max_range > 0.0f)) *why = "max_range must be finite and > 0";
+  else return SUMA_OK;
+  return SUMA_ERR_INVALID;
 }
 
 }  // namespace
@@ -98,6 +139,8 @@ extern "C" int suma_localizer_create(const suma_params* params, const suma_local
     return r;
   }
   l->lp = q;
+  suma_change_params_default(&l->cp);
+  memset(&l->last_counts, 0, sizeof(l->last_counts));
   l->c->timestamp = (uint32_t)params->active_timestamps + 10u; /* T_loc (k_localize.hip) */
   mat4_eye(l->pose);
   mat4_eye(l->increment);
@@ -109,6 +152,7 @@ extern "C" void suma_localizer_destroy(suma_localizer* l) {
   if (!l) return;
   if (l->c && l->c->stream) hipStreamSynchronize(l->c->stream);
   l->map = LocMap(); /* device blocks go before the ctx */
+  l->ev_totals.reset(), l->ev_totals_h.reset(), l->ev_source.reset();
   suma_frame_destroy(l->frame);
   suma_ctx_destroy(l->c);
   delete l;
@@ -122,8 +166,10 @@ extern "C" int suma_localizer_set_map_device(suma_localizer* l, const suma_world
   suma_ctx* c = l->c;
   if (n && !d_records) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_map: NULL records with n > 0");
   if (n && ((uintptr_t)d_records & 15u)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_map: records must be 16-byte aligned");
-  int r = localize_bin(c, d_records, n, &l->map);
+  int r = localize_bin(c, d_records, n, &l->map, l->ev_wanted);
   if (r) return r;
+  memset(&l->last_counts, 0, sizeof(l->last_counts));
+  l->last_observed = 0;
   l->have_map = true;
   l->have_pose = false;
   l->n_window = 0, l->rebuilds = 0;
@@ -164,6 +210,7 @@ extern "C" int suma_localizer_set_pose(suma_localizer* l, const double T[16]) {
   return SUMA_OK;
 }
 
+/* frame_ready: a candidate of a relocalisation -- K1-K3 are made, and a hypothesis observes nothing */
 static int process_scan(suma_localizer* l, const suma_float4* points, const float* labels, const float* probs, uint32_t n,
                         int32_t fixed_iterations, suma_localizer_result* res, bool on_device, bool frame_ready = false) {
   if (!l) return SUMA_ERR_INVALID;
@@ -251,6 +298,16 @@ static int process_scan(suma_localizer* l, const suma_float4* points, const floa
                   (double)res->outlier_ratio < (double)l->lp.max_outlier_ratio) ? 1 : 0;
   res->origin_ij[0] = l->oi, res->origin_ij[1] = l->oj;
   res->n_window = l->n_window;
+  /* 8. with evidence on: one observation of the scan's own frame at the final pose (k_change.hip) */
+  if (l->map.has_evidence && !frame_ready) {
+    memset(&l->last_counts, 0, sizeof(l->last_counts));
+    l->last_observed = 0;
+    if (l->n_window && (res->tracked || !l->cp.tracked_only) && finite16(pose)) {
+      int r = observe(l, l->frame, pose, &l->last_counts);
+      if (r) return r;
+      l->last_observed = 1;
+    }
+  }
   return SUMA_OK;
 }
 
@@ -401,4 +458,145 @@ extern "C" int suma_localizer_download_window(suma_localizer* l, suma_surfel* ho
     return SUMA_OK;
   }
   return suma_map_download(l->c, host, capacity, n);
+}
+
+/* ---- change evidence (include/suma_hip.h states the entries, k_change.hip the specification) ---- */
+extern "C" void suma_change_params_default(suma_change_params* cp) {
+  if (!cp) return;
+  cp->free_margin = 0.5f;
+  cp->min_view_cos = 0.3f;
+  cp->max_range = 50.0f;
+  cp->tracked_only = 1;
+}
+
+extern "C" void suma_change_rule_default(suma_change_rule* rule) {
+  if (!rule) return;
+  rule->min_misses = 3u;
+  rule->miss_ratio = 2.0f;
+}
+
+extern "C" int suma_localizer_enable_evidence(suma_localizer* l, const suma_change_params* cp) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_change_params q;
+  suma_change_params_default(&q);
+  if (cp) q = *cp;
+  std::string why;
+  if (change_params_check(q, &why)) return fail(l->c, SUMA_ERR_INVALID, "suma_localizer_enable_evidence: " + why);
+  l->cp = q;
+  l->ev_wanted = true;
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_disable_evidence(suma_localizer* l) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  l->ev_wanted = false;
+  if (l->map.has_evidence) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* an observation may still read them */
+    l->map.has_evidence = false;
+    l->map.evidence.reset();
+    l->map.src_idx.reset();
+    l->ev_source.reset();
+  }
+  l->last_observed = 0;
+  memset(&l->last_counts, 0, sizeof(l->last_counts));
+  return SUMA_OK;
+}
+
+static int evidence_ready(suma_localizer* l, const char* who) {
+  if (!l->have_map || !l->map.has_evidence)
+    return fail(l->c, SUMA_ERR_INVALID, std::string(who) + ": no evidence (suma_localizer_enable_evidence, then "
+                                        "suma_localizer_set_map)");
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_observe_frame(suma_localizer* l, const suma_frame* frame, const double T[16],
+                                            suma_change_counts* counts) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = evidence_ready(l, "suma_localizer_observe_frame");
+  if (r) return r;
+  if (!frame || !T) return fail(c, SUMA_ERR_INVALID, "suma_localizer_observe_frame: NULL argument");
+  if (frame->ctx != c) return fail(c, SUMA_ERR_INVALID, "suma_localizer_observe_frame: the frame belongs to another ctx");
+  if (frame->width != c->p.data_width || frame->height != c->p.data_height)
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_observe_frame: the frame must have the data image's size");
+  if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_observe_frame: non-finite pose");
+  return observe(l, frame, T, counts);
+}
+
+extern "C" int suma_localizer_last_observation(suma_localizer* l, suma_change_counts* counts, int32_t* observed) {
+  if (!l) return SUMA_ERR_INVALID;
+  int r = evidence_ready(l, "suma_localizer_last_observation");
+  if (r) return r;
+  if (counts) *counts = l->last_counts;
+  if (observed) *observed = l->last_observed;
+  return SUMA_OK;
+}
+
+/* the evidence in source order into l->ev_source (n_total words), enqueued */
+static int evidence_to_source_order(suma_localizer* l) {
+  suma_ctx* c = l->c;
+  const uint32_t n = l->map.n_total;
+  if (!n) return SUMA_OK;
+  int r = grow(c, l->ev_source, n, {c->stream});
+  if (r < 0) return r;
+  HIP_TRY(c, hipMemsetAsync(l->ev_source, 0, (size_t)n * sizeof(suma_change_evidence), c->stream));
+  ProfScope ps(c, "change_scatter", 36.0 * l->map.n_kept + 16.0 * n);
+  HIP_TRY(c, launch_kc_scatter(c, l->map, l->ev_source));
+  return SUMA_OK;
+}
+
+static int evidence_download(suma_localizer* l, suma_change_evidence* out, uint32_t capacity, uint32_t* n, bool to_device,
+                             const char* who) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = evidence_ready(l, who);
+  if (r) return r;
+  if (!n || (capacity && !out)) return fail(c, SUMA_ERR_INVALID, std::string(who) + ": NULL argument");
+  *n = l->map.n_total;
+  const uint32_t m = *n < capacity ? *n : capacity;
+  if (!m) return SUMA_OK;
+  r = evidence_to_source_order(l);
+  if (r) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, l->ev_source, (size_t)m * sizeof(suma_change_evidence),
+                            to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_evidence(suma_localizer* l, suma_change_evidence* host, uint32_t capacity, uint32_t* n) {
+  return evidence_download(l, host, capacity, n, false, "suma_localizer_evidence");
+}
+
+extern "C" int suma_localizer_evidence_device(suma_localizer* l, suma_change_evidence* d_out, uint32_t capacity, uint32_t* n) {
+  return evidence_download(l, d_out, capacity, n, true, "suma_localizer_evidence_device");
+}
+
+extern "C" int suma_localizer_clear_evidence(suma_localizer* l) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = evidence_ready(l, "suma_localizer_clear_evidence");
+  if (r) return r;
+  if (l->map.n_kept)
+    HIP_TRY(c, hipMemsetAsync(l->map.evidence, 0, (size_t)l->map.n_kept * sizeof(suma_change_evidence), c->stream));
+  memset(&l->last_counts, 0, sizeof(l->last_counts));
+  l->last_observed = 0;
+  return SUMA_OK;
+}
+
+extern "C" int suma_change_prune_mask(const suma_change_evidence* evidence, uint32_t n, const suma_change_rule* rule,
+                                      uint8_t* keep, uint32_t* n_removed) {
+  if (n && (!evidence || !keep)) return fail_without_ctx(SUMA_ERR_INVALID, "suma_change_prune_mask: NULL array with n > 0");
+  suma_change_rule q;
+  suma_change_rule_default(&q);
+  if (rule) q = *rule;
+  uint32_t removed = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    const suma_change_evidence& e = evidence[k];
+    const bool gone = e.misses >= q.min_misses && (float)e.misses > q.miss_ratio * (float)e.hits;
+    keep[k] = gone ? 0 : 1;
+    removed += gone ? 1u : 0u;
+  }
+  if (n_removed) *n_removed = removed;
+  return SUMA_OK;
 }

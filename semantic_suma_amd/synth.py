@@ -103,8 +103,11 @@ def _boxes(k: int):
 
 
 def generate_scan(k: int, n_azimuth: int = 2000, height: int = 64, noise: float = 0.02, seed: int = 1337,
-                  semantics: bool = True, max_range: float = 100.0, pose: np.ndarray | None = None):
-    """Ray-cast scan ``k``.  Returns (points[N,4] f32, labels[N] f32, probs[N] f32, pose[4,4] f64)."""
+                  semantics: bool = True, max_range: float = 100.0, pose: np.ndarray | None = None, without=()):
+    """Ray-cast scan ``k``.  Returns (points[N,4] f32, labels[N] f32, probs[N] f32, pose[4,4] f64).
+    ``without``: indices into the box list of ``_boxes(k)`` (the 23 cubes, then the buildings) that the ray caster skips
+    -- the same world with those objects taken away (the boxes draw no random numbers, so the default changes nothing)."""
+    without = frozenset(int(b) for b in without)
     T = trajectory_pose(k) if pose is None else np.asarray(pose, dtype=np.float64)
     rng = np.random.default_rng(seed + 7919 * k)
     el = beam_elevations(height)
@@ -135,6 +138,8 @@ def generate_scan(k: int, n_azimuth: int = 2000, height: int = 64, noise: float 
             label = np.where(hit, LABEL_BUILDING, label)
         cz, half, yaw, blabel = _boxes(k)
         for b in range(cz.shape[0]):                                 # slab test in the box frame
+            if b in without:
+                continue
             rel = Tinv[:3, :3] @ (cz[b] - o)                          # box centre in the sensor frame
             dist = math.hypot(rel[0], rel[1])
             rad = float(np.linalg.norm(half[b, :2]))

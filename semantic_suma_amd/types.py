@@ -167,6 +167,45 @@ class LocalizerResult(C.Structure):
                 ("origin_ij", i32 * 2), ("n_window", u32)]
 
 
+class ChangeParams(C.Structure):
+    """``struct suma_change_params``: what counts as seen through, grazing and too far for the change evidence of
+    core.Localizer (csrc/k_change.hip); ``ChangeParams.defaults()`` = suma_change_params_default"""
+    _fields_ = [("free_margin", f32), ("min_view_cos", f32), ("max_range", f32), ("tracked_only", i32)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "ChangeParams":
+        p = cls(free_margin=0.5, min_view_cos=0.3, max_range=50.0, tracked_only=1)
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise KeyError(f"unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+
+class ChangeCounts(C.Structure):
+    """``struct suma_change_counts``: what one observation did with the records of the window"""
+    _fields_ = [("n_window", u32), ("unseen", u32), ("no_return", u32), ("occluded", u32), ("misses", u32),
+                ("grazing", u32), ("hits", u32), ("near", u32), ("label_changes", u32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class ChangeRule(C.Structure):
+    """``struct suma_change_rule``: a record is removed iff misses >= min_misses and misses > miss_ratio * hits (fp32);
+    ``ChangeRule.defaults()`` = suma_change_rule_default"""
+    _fields_ = [("min_misses", u32), ("miss_ratio", f32)]
+
+    @classmethod
+    def defaults(cls, min_misses: int = 3, miss_ratio: float = 2.0) -> "ChangeRule":
+        return cls(min_misses=min_misses, miss_ratio=miss_ratio)
+
+
+# numpy view of ``struct suma_change_evidence``: one per record of the map, in the map's record order
+EVIDENCE_DTYPE = np.dtype([("hits", "<u4"), ("misses", "<u4"), ("occluded", "<u4"), ("label_changes", "<u4")])
+assert EVIDENCE_DTYPE.itemsize == 16
+
+
 PLACE_MAX_DIM = 64       # SUMA_PLACE_MAX_DIM: rings and sectors
 PLACE_MAX_MATCHES = 32   # SUMA_PLACE_MAX_MATCHES
 # is_dynamic_label (csrc/dev_math.h): the moving classes K1 drops at the start of a run

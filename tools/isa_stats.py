@@ -3,7 +3,7 @@
 VALU instructions, of v_readlane / v_writelane (SGPR spill traffic when the register report says "SGPRs Spill"), hazard
 nops, IEEE division sequences (v_div_fixup), scalar and vector memory instructions, and the register report of the
 compiler.  This is what found K9's spilled arguments.
-    python tools/isa_stats.py [file.hip ...] [-D...]        (default: the four kernel files)
+    python tools/isa_stats.py [file.hip ...] [-D...]        (default: the five kernel files below)
 """
 import os
 import re
@@ -46,7 +46,7 @@ def largest_loop(lines):
 
 def main():
     defs = [a for a in sys.argv[1:] if a.startswith("-")]
-    files = [a for a in sys.argv[1:] if not a.startswith("-")] or ["k_icp.hip", "k_render.hip", "k_update.hip", "k_preprocess.hip"]
+    files = [a for a in sys.argv[1:] if not a.startswith("-")] or ["k_icp.hip", "k_render.hip", "k_update.hip", "k_preprocess.hip", "k_change.hip"]
     print(f"{'kernel':44s} {'VGPR':>4s} {'SGPRspill':>9s} | {'VALU':>5s} {'rdlane':>6s} {'wrlane':>6s} {'s_nop':>5s} {'div':>4s} "
           f"{'smem':>4s} {'vmem':>4s} {'lds':>4s} | largest loop: {'VALU':>5s} {'rdlane':>6s} {'s_nop':>5s} {'div':>4s} {'smem':>4s}")
     for f in files:

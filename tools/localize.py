@@ -6,15 +6,19 @@ or takes the map from a PLY written by tools/export_map.py (--map).  The map is 
 (position, the two gate ratios, tracked, window rebuilds; the distance to the mapping pose of the same scan where one
 exists) and a JSON summary.  --timing keeps the scans on the device and reports localisation scans/s beside the mapping
 pipeline's scans/s over the same scans in the same run, and the cost of one window rebuild.  --relocalize starts without
-a start pose: the first scan goes through Localizer.relocalize against a place index (core.PlaceIndex) -- the mapping
+a start pose; --evidence collects change evidence per map record while the scans are localised (csrc/k_change.hip), prints
+every scan's totals and, with --prune-out, writes the map without the records the default rule removes (--without takes
+objects out of the synthetic world the localised scans see).  With --relocalize the first scan goes through Localizer.relocalize against a place index (core.PlaceIndex) -- the mapping
 run's own scans, or with --map the file tools/export_map.py --places wrote (--places).  Needs a GPU.
     python tools/localize.py [--map-scans 80] [--first 10] [--scans 60] [--voxel 0.1] [--width 2048] [--kitti sequences/08]
     python tools/localize.py --map map.ply --start 12.0 0.5 0.0 3.0 --first 11 --scans 20
     python tools/localize.py --timing                       # 64 x 2048, the 300-scan map, 60 scans
     python tools/localize.py --relocalize [--candidates 8]  # no setPose: the start comes from place recognition
     python tools/localize.py --map map.ply --places map.places.npz --relocalize --first 11 --scans 20
+    python tools/localize.py --evidence --without 2 41 --prune-out pruned.ply   # cube 2 and a building are gone
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -27,20 +31,64 @@ from semantic_suma_amd import core, kitti, mapio, places, synth  # noqa: E402
 from semantic_suma_amd.types import LocalizerParams, PlaceParams, params_with_size  # noqa: E402
 
 
-def read_scan(args, k):
+def read_scan(args, k, without=()):
     if args.kitti:
         bins = sorted(f for f in os.listdir(os.path.join(args.kitti, "velodyne")) if f.endswith(".bin"))
         pts = kitti.read_velodyne(os.path.join(args.kitti, "velodyne", bins[k]))
         lp = os.path.join(args.kitti, "labels", bins[k][:-4] + ".label")
         lab, prob = kitti.read_labels(lp, pts.shape[0]) if os.path.exists(lp) else (None, None)
         return pts, lab, prob
-    return synth.generate_scan(k, n_azimuth=args.width, height=args.height)[:3]
+    return synth.generate_scan(k, n_azimuth=args.width, height=args.height, without=without)[:3]
 
 
 def resident(ctx, scan):
     pts, lab, prob = (None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in scan)
     n = pts.reshape(-1, 4).shape[0]
     return ctx.device_array(pts), 0 if lab is None else ctx.device_array(lab), 0 if prob is None else ctx.device_array(prob), n
+
+
+def event_ms(ctx, enqueue, repeats=10, warmup=3):
+    """event times of `enqueue()` on the ctx stream, in ms"""
+    import torch
+    st = torch.cuda.ExternalStream(ctx.stream) if ctx.stream else torch.cuda.current_stream()
+    out = []
+    with torch.cuda.stream(st):
+        for k in range(warmup + repeats):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(st)
+            enqueue()
+            b.record(st)
+            b.synchronize()
+            if k >= warmup:
+                out.append(a.elapsed_time(b))
+    return out
+
+
+def observe_timing(loc, scan, pose, n_window):
+    """kc_observe's event time (suma_profile, one observation at a time) against an event-timed device-to-device copy of
+    the bytes it touches: 64 a window record (48 of the record, 16 of its evidence) and the frame's three maps"""
+    ctx, p = loc.ctx, loc.params
+    frame = core.Frame(ctx, p.data_width, p.data_height)
+    core.Preprocessing(ctx).process(scan[0], frame, scan[1], scan[2], p.active_timestamps + 10)
+    ctx.profile(1)
+    kernel = []
+    for k in range(13):
+        ctx.profile_reset()
+        loc.observeFrame(frame, pose)
+        ms = {r["name"]: r["total_ms"] for r in ctx.profile_get()}["change_observe"]
+        if k >= 3:
+            kernel.append(ms)
+    ctx.profile(0)
+    nbytes = 64 * n_window + 48 * p.data_width * p.data_height
+    src, dst = ctx.device_array(np.zeros(nbytes, dtype=np.uint8)), ctx.device_array(np.zeros(nbytes, dtype=np.uint8))
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    copy = event_ms(ctx, lambda: hip.hipMemcpyAsync(dst, src, nbytes, 3, C.c_void_p(ctx.stream)))
+    ctx.device_free(src)
+    ctx.device_free(dst)
+    k, c = float(np.median(kernel)), float(np.median(copy))
+    return dict(bytes=nbytes, kc_observe_us_median10=round(1e3 * k, 2), d2d_copy_us_median10=round(1e3 * c, 2),
+                observe_over_copy=round(k / c, 3), samples=dict(kc_observe_ms=kernel, d2d_copy_ms=copy))
 
 
 def pose_from(x, y, z, yaw_deg):
@@ -73,7 +121,13 @@ def main():
     ap.add_argument("--places", default=None, help="with --map: the place index tools/export_map.py --places wrote")
     ap.add_argument("--candidates", type=int, default=8, help="places a relocalisation tries (1 .. 32)")
     ap.add_argument("--place-range", type=float, default=80.0, help="max_range of the place descriptor in metres")
+    ap.add_argument("--evidence", action="store_true", help="collect change evidence per map record and print every scan's totals")
+    ap.add_argument("--prune-out", default=None, metavar="FILE.ply", help="with --evidence: write the map the default rule keeps")
+    ap.add_argument("--without", type=int, nargs="*", default=[], metavar="BOX",
+                    help="synthetic scans: boxes of synth._boxes the localised scans do not see (0-22 cubes, 23.. buildings)")
     args = ap.parse_args()
+    if args.prune_out and not args.evidence:
+        ap.error("--prune-out needs --evidence")
     over = {k: v for k, v in (("submap_extent", args.extent), ("submap_dimension", args.dimension)) if v is not None}
     p = params_with_size(args.width, args.height, **over)
     n_map = args.map_scans if args.map_scans is not None else (300 if args.timing else 80)
@@ -126,13 +180,17 @@ def main():
         pipe.close()
 
     loc = core.Localizer(p, LocalizerParams.defaults(p, constant_velocity=int(not args.no_motion_model)))
+    if args.evidence:
+        loc.enableEvidence()
     t = time.perf_counter()
     dropped = loc.setMap(records)
     res.update(map_records=int(len(records)), dropped=dropped, set_map_ms=round(1e3 * (time.perf_counter() - t), 3))
     start = pose_from(*args.start) if args.start else map_poses.get(first, np.eye(4))
     if not args.relocalize:
         loc.setPose(start)
-    scans = [read_scan(args, k) for k in ks]
+    scans = [read_scan(args, k, tuple(args.without)) for k in ks]
+    host_scans = scans
+    observations = []
     if args.timing:
         scans = [resident(loc.ctx, sc) for sc in scans]
         loc.ctx.synchronize()
@@ -155,6 +213,8 @@ def main():
                 continue
             out.append(loc.processScanDevice(*sc, fixed_iterations=args.iterations) if args.timing
                        else loc.processScan(*sc, fixed_iterations=args.iterations))
+            if args.evidence:
+                observations.append(loc.lastObservation())
         except core.SumaError as e:  # a run that has left the map ends on a pose that is no longer finite
             res.update(lost_at_scan=k, error=str(e))
             break
@@ -170,6 +230,16 @@ def main():
         print(f"scan {k:5d}  xyz {T[0, 3]:10.3f} {T[1, 3]:10.3f} {T[2, 3]:8.3f}  valid {r['valid_ratio']:.3f} "
               f"outlier {r['outlier_ratio']:.3f}  tracked {int(r['tracked'])}  rebuilt {int(r['window_rebuilt'])}  "
               f"origin {r['origin']}  window {r['n_window']}  to mapping pose {err:.3f} m")
+    if args.evidence:
+        for k, (cnt, observed) in zip(ks[len(ks) - len(observations):] if args.relocalize else ks, observations):
+            print(f"scan {k:5d}  observed {int(observed)}  " + "  ".join(f"{n} {v}" for n, v in cnt.items()))
+        ev = loc.evidence()
+        kept, keep = core.pruned_map(records, ev)
+        res["evidence"] = dict({f: int(ev[f].sum()) for f in ev.dtype.names}, observed_scans=sum(o for _, o in observations),
+                               records_with_misses=int((ev["misses"] > 0).sum()), pruned=int((~keep).sum()), kept=int(len(kept)))
+        if args.prune_out:
+            mapio.write_ply(args.prune_out, kept)
+            res["pruned_map"] = args.prune_out
     origin, n_window, rebuilds = loc.window()
     res.update(tracked=sum(r["tracked"] for r in out), window_rebuilds=sum(r["window_rebuilt"] for r in out),
                n_window=n_window, worst_distance_to_mapping_pose_m=round(worst, 4))
@@ -184,6 +254,8 @@ def main():
             loc.ctx.synchronize()
             times.append(time.perf_counter() - t)
         res["window_rebuild_ms"] = [round(1e3 * x, 3) for x in times]
+        if args.evidence and "lost_at_scan" not in res:
+            res["observe"] = observe_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], loc.window()[1])
     loc.close()
     print(json.dumps(res))
 
