@@ -722,6 +722,60 @@ class Localizer {
     if (keep) keep->swap(k);
     return out;
   }
+  /* newly seen surfaces (csrc/k_novel.hip): from now on every tracked scan ends with one collection of the texels no
+   * record of the window explains; np NULL = the defaults (201 MB of candidates are allocated) */
+  void enableNovelty(const suma_novel_params* np = nullptr) {
+    chk(suma_localizer_enable_novelty(l_, np), "Localizer::enableNovelty");
+  }
+  void disableNovelty() { chk(suma_localizer_disable_novelty(l_), "Localizer::disableNovelty"); }
+  /* one collection of a data-sized frame of ctx() at the sensor pose T (column-major, world frame) */
+  suma_novel_counts collectFrame(const suma_frame* frame, const double T[16], uint32_t scan_id) {
+    suma_novel_counts c;
+    chk(suma_localizer_collect_frame(l_, frame, T, scan_id, &c), "Localizer::collectFrame");
+    return c;
+  }
+  /* the counts of the last processScan's collection; *collected (optional): whether it collected */
+  suma_novel_counts lastCollection(bool* collected = nullptr) {
+    suma_novel_counts c;
+    int32_t o = 0;
+    chk(suma_localizer_last_collection(l_, &c, &o), "Localizer::lastCollection");
+    if (collected) *collected = o != 0;
+    return c;
+  }
+  /* the candidates in creation order */
+  std::vector<suma_world_surfel> novelCandidates() {
+    uint32_t n = 0;
+    chk(suma_localizer_novel_candidates(l_, nullptr, 0, &n), "Localizer::novelCandidates");
+    std::vector<suma_world_surfel> out(n);
+    if (n) chk(suma_localizer_novel_candidates(l_, out.data(), n, &n), "Localizer::novelCandidates");
+    return out;
+  }
+  /* the candidates fused per voxel, kept where min_views scans agree (fp NULL = the defaults); *views (optional): how
+   * many scans each record was seen by; *stats (optional) */
+  std::vector<suma_world_surfel> novel(const suma_novel_fuse_params* fp = nullptr, std::vector<uint32_t>* views = nullptr,
+                                       suma_novel_stats* stats = nullptr) {
+    suma_novel_stats st;
+    chk(suma_localizer_novel(l_, fp, nullptr, nullptr, 0, &st), "Localizer::novel");
+    std::vector<suma_world_surfel> out(st.n_out);
+    std::vector<uint32_t> v(st.n_out);
+    if (st.n_out) chk(suma_localizer_novel(l_, fp, out.data(), v.data(), st.n_out, &st), "Localizer::novel");
+    if (views) views->swap(v);
+    if (stats) *stats = st;
+    return out;
+  }
+  void clearNovelty() { chk(suma_localizer_clear_novelty(l_), "Localizer::clearNovelty"); }
+  /* the records prunedMap keeps (all of them while the map has no evidence) followed by novel()'s: what goes into the
+   * next setMap */
+  std::vector<suma_world_surfel> updatedMap(const std::vector<suma_world_surfel>& records,
+                                            const suma_change_rule* rule = nullptr,
+                                            const suma_novel_fuse_params* fp = nullptr) {
+    uint32_t n = 0;
+    std::vector<suma_world_surfel> out =
+        suma_localizer_evidence(l_, nullptr, 0, &n) == SUMA_OK ? prunedMap(records, rule) : records;
+    const std::vector<suma_world_surfel> fresh = novel(fp);
+    out.insert(out.end(), fresh.begin(), fresh.end());
+    return out;
+  }
   suma_localizer* get() const { return l_; }
   suma_ctx* ctx() const { return suma_localizer_ctx(l_); }
 

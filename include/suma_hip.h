@@ -815,7 +815,7 @@ int suma_localizer_download_window(suma_localizer* l, suma_surfel* host, uint32_
  *      written: the evidence is an array of its own, it comes back in the order of the records suma_localizer_set_map was
  *      given, and suma_change_prune_mask turns it into the records to keep.  csrc/k_change.hip states the fp32
  *      specification, tests/change_shim.c restates it; DESIGN.md 14 has the scenario it was measured on and what is out
- *      of scope (adding new surfaces, removing records from the live window, evidence in checkpoints).  Evidence is off
+ *      of scope (removing records from the live window, evidence in checkpoints).  Evidence is off
  *      unless switched on, and with it on every result of the localiser is bit-identical to a run with it off. */
 typedef struct suma_change_params {
   float free_margin;     /* default 0.5 m: how much farther than the record a return must lie before the record counts
@@ -866,6 +866,81 @@ int suma_localizer_clear_evidence(suma_localizer* l);
  * (optional) = the zeros.  SUMA_ERR_INVALID for NULL arrays with n > 0; the text is suma_last_error(NULL). */
 int suma_change_prune_mask(const suma_change_evidence* evidence, uint32_t n, const suma_change_rule* rule, uint8_t* keep,
                            uint32_t* n_removed);
+
+/* ---- map maintenance, second step: "what is there today that yesterday's map does not have?"  While a localiser
+ *      tracks, the texels of each scan that no record of the window explains are collected on the device as world-frame
+ *      candidate surfels; on request they are fused per voxel and kept where several scans agree.  The fused records
+ *      concatenate with the records the prune rule keeps into the updated map, which goes into the next
+ *      suma_localizer_set_map, a file or a picture.  The map is still not written.  csrc/k_novel.hip states the fp32
+ *      specification, tests/novel_shim.c restates it; DESIGN.md 15 has the scenario and what is out of scope (candidates
+ *      in checkpoints, inserting into the live window, free-space checks of old candidates).  Novelty is off unless
+ *      switched on, and with it on every other output of the localiser is bit-identical to a run with it off. */
+typedef struct suma_novel_params {
+  float agree_margin;      /* default 0.5 m: a record explains a texel whose range differs by no more; finite, > 0 */
+  float max_range;         /* default 50 m: texels with range + agree_margin >= this collect nothing; finite, > 0 */
+  int32_t tracked_only;    /* default 1: a scan whose tracked == 0 collects nothing */
+  uint32_t max_candidates; /* default 4 194 304 (48 bytes each, 201 MB, allocated by the enable); 1 .. 2^30 */
+} suma_novel_params;
+typedef struct suma_novel_fuse_params {
+  float voxel_size;        /* default 0.2 m; finite, > 0 */
+  uint32_t min_views;      /* default 2: distinct scans (timestamps) that must have put a candidate into the voxel; >= 1 */
+  float confidence;        /* default confidence_threshold + 1.0f: the localiser renders only records with confidence >
+                              conf_threshold, so a new record at the mapping prior (log_prior, what a candidate carries)
+                              would never be matched against; not NaN */
+} suma_novel_fuse_params;
+/* what one collection did with the texels of the frame; no_return + out_of_range + grazing + explained + novel =
+ * n_texels; stored = the novel ones that fitted into the buffer */
+typedef struct suma_novel_counts {
+  uint32_t n_texels, no_return, out_of_range, grazing, explained, novel, stored;
+} suma_novel_counts;
+typedef struct suma_novel_stats {
+  uint32_t n_candidates;   /* held now */
+  uint32_t n_overflow;     /* novel texels that did not fit since the last clear */
+  uint32_t n_dropped;      /* candidates outside the voxel grid */
+  uint32_t n_voxels;       /* distinct voxels */
+  uint32_t n_out;          /* voxels with views >= min_views: the size of the result */
+} suma_novel_stats;
+/* 0.5f, 50.0f, 1, 4194304 */
+void suma_novel_params_default(suma_novel_params* np);
+/* 0.2f, 2, params->confidence_threshold + 1.0f (params NULL: 1.0f) */
+void suma_novel_fuse_params_default(const suma_params* params, suma_novel_fuse_params* fp);
+/* switches novelty on (np NULL = the defaults) and allocates the candidate buffer, the mark image and the flags.
+ * SUMA_ERR_INVALID with a message for values outside the ranges above, and nothing launched.  Enabling again replaces
+ * the parameters; a different max_candidates clears the candidates. */
+int suma_localizer_enable_novelty(suma_localizer* l, const suma_novel_params* np);
+/* switches it off and gives the buffers back */
+int suma_localizer_disable_novelty(suma_localizer* l);
+/* the primitive: one collection of a frame of the localiser's ctx (data image size) at the sensor pose T (column-major,
+ * world frame, finite) over the current window, enqueued on the ctx stream; the candidates carry scan_id as their
+ * timestamp.  *counts (optional) = its totals, which makes the call blocking.  An empty window collects nothing. */
+int suma_localizer_collect_frame(suma_localizer* l, const suma_frame* frame, const double T[16], uint32_t scan_id,
+                                 suma_novel_counts* counts);
+/* With novelty on, suma_localizer_process_scan(_device) ends with one collection of the scan's own frame at the final
+ * pose (behind the observation, when evidence is on too), unless the window is empty, tracked_only && !tracked, or the
+ * pose is not finite; its scan_id is the number of process_scan(_device) calls since the last suma_localizer_set_map,
+ * counted from 0 whether or not they collected.  The scan path does not wait for it.  suma_localizer_relocalize collects
+ * nothing and does not count.  This returns the totals of the last collection -- a scan's or
+ * suma_localizer_collect_frame's -- and whether it collected (both optional).  Blocking. */
+int suma_localizer_last_collection(suma_localizer* l, suma_novel_counts* counts, int32_t* collected);
+/* the candidates in creation order: *n = their number, min(*n, capacity) are copied.  Blocking. */
+int suma_localizer_novel_candidates(suma_localizer* l, suma_world_surfel* host, uint32_t capacity, uint32_t* n);
+int suma_localizer_novel_candidates_device(suma_localizer* l, suma_world_surfel* d_out, uint32_t capacity, uint32_t* n);
+/* replaces the candidates by n records of the caller's (a session's candidates saved by suma_localizer_novel_candidates and
+ * taken up again: checkpoints do not hold them).  SUMA_ERR_CAPACITY, nothing changed, when n > max_candidates. */
+int suma_localizer_set_novel_candidates(suma_localizer* l, const suma_world_surfel* host, uint32_t n);
+/* the fused records in ascending voxel order and their views (fp NULL = the defaults of the localiser's suma_params):
+ * stats->n_out = their number, min(n_out, capacity) are written (suma_map_export_world's convention); host / views may
+ * be NULL with capacity 0.  Blocking; the candidates stay.  Two calls give the same bytes. */
+int suma_localizer_novel(suma_localizer* l, const suma_novel_fuse_params* fp, suma_world_surfel* host, uint32_t* views,
+                         uint32_t capacity, suma_novel_stats* stats);
+int suma_localizer_novel_device(suma_localizer* l, const suma_novel_fuse_params* fp, suma_world_surfel* d_out,
+                                uint32_t* d_views, uint32_t capacity, suma_novel_stats* stats);
+/* the mark image of the last collection (one byte a texel of the data image): *n = its size, min(*n, capacity) are copied */
+int suma_localizer_novel_marks(suma_localizer* l, uint8_t* host, uint32_t capacity, uint32_t* n);
+/* no candidates, n_overflow = 0; a new suma_localizer_set_map clears too and restarts the scan count.
+ * _last_collection, _novel_candidates(_device) and _novel(_device) return SUMA_ERR_CAPACITY after filling their outputs
+ * when n_overflow > 0 (the downloads' convention). */
+int suma_localizer_clear_novelty(suma_localizer* l);
 
 /* ---- place recognition and global relocalisation: "the sensor was switched on somewhere inside yesterday's map".  A
  *      place index holds one descriptor per scan of a mapping session: a polar height map about the sensor (sectors x

@@ -10,7 +10,8 @@ stand for (PRBonn/semantic_suma, src/core):
     SurfelMap        src/core/SurfelMap.h:36-78              update / render* / *MapFrame / updatePoses / size / draw
     SurfelMapping    src/core/SurfelMapping.h:47             processScan(scan)
     Localizer        (no counterpart)                        setMap / setPose / processScan / relocalize in a finished map;
-                                                             enableEvidence / evidence / prunedMap: which records still hold
+                                                             enableEvidence / evidence / prunedMap: which records still hold;
+                                                             enableNovelty / novel / updatedMap: what is new
     PlaceIndex       (no counterpart)                        addFrame / queryFrame: place recognition over a session's scans
     Posegraph        src/core/Posegraph.h:10-78              setInitial / addEdge / optimize / poses
 
@@ -30,7 +31,7 @@ import numpy as np
 from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX_LIGHTS, SURFEL_DTYPE, DrawParams,
                     IcpStats, LoopParams, LoopStatus, PosegraphParams, PosegraphStats, SemanticKnnParams,
                     SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats, CheckpointInfo,
-                    ChangeCounts, ChangeParams, ChangeRule, EVIDENCE_DTYPE, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
+                    ChangeCounts, ChangeParams, ChangeRule, EVIDENCE_DTYPE, NovelCounts, NovelFuseParams, NovelParams, NovelStats, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -292,6 +293,22 @@ def lib():
     L.suma_localizer_evidence_device.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.suma_localizer_clear_evidence.argtypes = [vp]
     L.suma_change_prune_mask.argtypes = [vp, u32, crp, vp, C.POINTER(u32)]
+    npp, nfp, ncp, nsp = C.POINTER(NovelParams), C.POINTER(NovelFuseParams), C.POINTER(NovelCounts), C.POINTER(NovelStats)
+    L.suma_novel_params_default.argtypes = [npp]
+    L.suma_novel_params_default.restype = None
+    L.suma_novel_fuse_params_default.argtypes = [C.POINTER(SumaParams), nfp]
+    L.suma_novel_fuse_params_default.restype = None
+    L.suma_localizer_enable_novelty.argtypes = [vp, npp]
+    L.suma_localizer_disable_novelty.argtypes = [vp]
+    L.suma_localizer_collect_frame.argtypes = [vp, vp, vp, u32, ncp]
+    L.suma_localizer_last_collection.argtypes = [vp, ncp, C.POINTER(i32)]
+    L.suma_localizer_novel_candidates.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_localizer_novel_candidates_device.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_localizer_set_novel_candidates.argtypes = [vp, vp, u32]
+    L.suma_localizer_novel.argtypes = [vp, nfp, vp, vp, u32, nsp]
+    L.suma_localizer_novel_device.argtypes = [vp, nfp, vp, vp, u32, nsp]
+    L.suma_localizer_novel_marks.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_localizer_clear_novelty.argtypes = [vp]
     ppp, pmp = C.POINTER(PlaceParams), C.POINTER(PlaceMatch)
     L.suma_place_params_default.argtypes = [ppp]
     L.suma_place_params_default.restype = None
@@ -1686,6 +1703,93 @@ class Localizer:
     def prunedMap(self, records: np.ndarray, rule: ChangeRule = None):
         """(records[keep], keep) by suma_change_prune_mask over evidence(); ``records``: what setMap was given"""
         return pruned_map(records, self.evidence(), rule)
+
+    # -- newly seen surfaces (csrc/k_novel.hip)
+    def _novel_check(self, rc: int, what: str, allow_overflow: bool):
+        """the downloads fill their outputs and then report an overflow of max_candidates (-3); ``allow_overflow``
+        takes the outputs all the same"""
+        if not (allow_overflow and rc == -3):
+            self.ctx.check(rc, what)
+
+    def enableNovelty(self, params: NovelParams = None):
+        """from now on every scan processScan tracks ends with one collection: the texels no record of the window
+        explains become world-frame candidates on the device (48 bytes each, max_candidates of them are allocated)"""
+        self.ctx.check(self.L.suma_localizer_enable_novelty(self.h, None if params is None else C.byref(params)),
+                       "suma_localizer_enable_novelty")
+
+    def disableNovelty(self):
+        self.ctx.check(self.L.suma_localizer_disable_novelty(self.h), "suma_localizer_disable_novelty")
+
+    def collectFrame(self, frame: Frame, pose, scan_id: int) -> dict:
+        """one collection of a data-sized frame of this localiser's ctx at a sensor pose (row-major 4x4, world frame)
+        over the current window; returns its counts"""
+        T = _cm(pose, np.float64)
+        cnt = NovelCounts()
+        self.ctx.check(self.L.suma_localizer_collect_frame(self.h, frame.h, _ptr(T), scan_id, C.byref(cnt)),
+                       "suma_localizer_collect_frame")
+        return cnt.as_dict()
+
+    def lastCollection(self, allow_overflow: bool = False):
+        """(the counts of the last processScan's collection, whether it collected)"""
+        cnt, col = NovelCounts(), C.c_int32(0)
+        self._novel_check(self.L.suma_localizer_last_collection(self.h, C.byref(cnt), C.byref(col)),
+                          "suma_localizer_last_collection", allow_overflow)
+        return cnt.as_dict(), bool(col.value)
+
+    def novelCandidates(self, allow_overflow: bool = False) -> np.ndarray:
+        """WORLD_SURFEL_DTYPE: the candidates in creation order (timestamp = the scan's number, support = 1)"""
+        n = C.c_uint32(0)
+        self._novel_check(self.L.suma_localizer_novel_candidates(self.h, None, 0, C.byref(n)),
+                          "suma_localizer_novel_candidates", True)
+        out = np.zeros(n.value, dtype=WORLD_SURFEL_DTYPE)
+        self._novel_check(self.L.suma_localizer_novel_candidates(self.h, _ptr(out) if n.value else None, n.value, C.byref(n)),
+                          "suma_localizer_novel_candidates", allow_overflow)
+        return out[:n.value]
+
+    def setNovelCandidates(self, records: np.ndarray):
+        """replaces the candidates (what novelCandidates of an earlier session gave)"""
+        ws = np.ascontiguousarray(records, dtype=WORLD_SURFEL_DTYPE).reshape(-1)
+        self.ctx.check(self.L.suma_localizer_set_novel_candidates(self.h, _ptr(ws) if ws.shape[0] else None, ws.shape[0]),
+                       "suma_localizer_set_novel_candidates")
+
+    def novel(self, fuse_params: NovelFuseParams = None, allow_overflow: bool = False, stats: bool = False):
+        """(records, views): the candidates fused per voxel, kept where at least min_views scans agree, in ascending
+        voxel order; with ``stats`` the suma_novel_stats dict comes third"""
+        fp = None if fuse_params is None else C.byref(fuse_params)
+        st = NovelStats()
+        self._novel_check(self.L.suma_localizer_novel(self.h, fp, None, None, 0, C.byref(st)), "suma_localizer_novel", True)
+        n = st.n_out
+        rec, views = np.zeros(n, dtype=WORLD_SURFEL_DTYPE), np.zeros(n, dtype=np.uint32)
+        if n:
+            self._novel_check(self.L.suma_localizer_novel(self.h, fp, _ptr(rec), _ptr(views), n, C.byref(st)),
+                              "suma_localizer_novel", allow_overflow)
+        elif not allow_overflow and st.n_overflow:
+            self.ctx.check(self.L.suma_localizer_novel(self.h, fp, None, None, 0, C.byref(st)), "suma_localizer_novel")
+        return (rec, views, st.as_dict()) if stats else (rec, views)
+
+    def novelMarks(self) -> np.ndarray:
+        """the mark image of the last collection, H x W uint8: 1 where a record of the window agrees with the texel"""
+        p = self.params
+        out = np.zeros((p.data_height, p.data_width), dtype=np.uint8)
+        n = C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_novel_marks(self.h, _ptr(out), out.size, C.byref(n)), "suma_localizer_novel_marks")
+        return out
+
+    def clearNovelty(self):
+        self.ctx.check(self.L.suma_localizer_clear_novelty(self.h), "suma_localizer_clear_novelty")
+
+    def updatedMap(self, records: np.ndarray, rule: ChangeRule = None, fuse_params: NovelFuseParams = None) -> np.ndarray:
+        """the records prunedMap keeps (all of them when evidence is off) followed by the fused novel records: what goes
+        into the next setMap, mapio.write_ply or draw.  ``records``: what setMap was given"""
+        records = np.ascontiguousarray(records, dtype=WORLD_SURFEL_DTYPE).reshape(-1)
+        try:
+            ev = self.evidence()
+        except SumaError as e:
+            if "no evidence" not in str(e):
+                raise
+            ev = None
+        kept = records if ev is None else pruned_map(records, ev, rule)[0]
+        return np.concatenate([kept, self.novel(fuse_params)[0]])
 
     def modelFrame(self) -> Frame:
         """the window as the last scan's render saw it (the ctx's oldMapFrame)"""

@@ -571,6 +571,34 @@ hipError_t launch_kc_observe(suma_ctx* c, const LocMap& m, uint32_t n_spans, uin
                              const double T[16], const suma_change_params& cp, uint32_t* d_totals);
 hipError_t launch_kc_scatter(suma_ctx* c, const LocMap& m, suma_change_evidence* d_out);
 
+/* k_novel.hip (the specification is there): the candidates a localiser collects beside its map */
+struct NovelState {      /* device resident: no collection needs a host round trip */
+  uint32_t count;        /* candidates held */
+  uint32_t n_overflow;   /* novel texels that did not fit */
+  uint32_t done;         /* blocks of kn_emit that have finished; back to 0 when the launch ends */
+  uint32_t pad;
+  uint32_t counts[8];    /* suma_novel_counts of the last collection */
+};
+struct Novel {
+  bool on = false;
+  suma_novel_params np;
+  DevBuf<float4> cand;           /* 3 float4 a candidate, np.max_candidates of them */
+  DevBuf<uint8_t> mark, flag;    /* one byte a texel of the data image */
+  DevBuf<uint32_t> block_counts; /* kn_collect's counts, 8 words a block of 256 texels */
+  DevBuf<NovelState> state;
+  PinnedBuf<uint32_t> stage_h;   /* 16 words: the state, or the fusion's counters, on their way to the host */
+  DevBuf<char> scratch, tmp;     /* the fusion's arrays and rocPRIM's temporary storage */
+  DevBuf<float4> fused;          /* the fusion's output on its way to the host */
+  DevBuf<uint32_t> fused_views;
+};
+/* one collection of frame f at pose T over the first `total` window records of the span table in m.spans, enqueued */
+int novel_collect(suma_ctx* c, Novel& nv, const LocMap& m, uint32_t n_spans, uint32_t total, const suma_frame* f,
+                  const double T[16], uint32_t scan_id);
+/* candidates 0 .. n - 1 fused into d_out / d_views (device, capacity records); blocking.  counters_out: n_dropped,
+ * n_voxels, n_out */
+int novel_fuse(suma_ctx* c, Novel& nv, uint32_t n, const suma_novel_fuse_params& fp, suma_world_surfel* d_out,
+               uint32_t* d_views, uint32_t capacity, uint32_t counters_out[3]);
+
 /* k_place.hip (the specification is there): what kp_describe reads of suma_place_params, with the two quotients made
  * once on the host and the label mask as bits */
 struct PlaceArgs {

@@ -35,6 +35,10 @@ struct suma_localizer {
   DevBuf<suma_change_evidence> ev_source; /* the evidence in source order, made by every download */
   suma_change_counts last_counts;
   int32_t last_observed = 0;
+  /* novelty (k_novel.hip): the candidates beside the map */
+  Novel nv;
+  uint32_t scan_count = 0;     /* process_scan calls since the last set_map */
+  int32_t last_collected = 0;
 };
 
 namespace {
@@ -88,6 +92,15 @@ int observe(suma_localizer* l, const suma_frame* f, const double T[16], suma_cha
   }
   if (counts) *counts = out;
   return SUMA_OK;
+}
+
+/* one collection over the current window, enqueued on the ctx stream */
+int collect(suma_localizer* l, const suma_frame* f, const double T[16], uint32_t scan_id) {
+  suma_ctx* c = l->c;
+  if (!l->n_window) return SUMA_OK;
+  if (c->gate_pending) HIP_TRY(c, flush_gate(c));
+  const_cast<suma_frame*>(f)->last_access = ++c->enq_seq;
+  return novel_collect(c, l->nv, l->map, (uint32_t)l->spans.size(), l->n_window, f, T, scan_id);
 }
 
 int change_params_check(const suma_change_params& q, std::string* why) {
@@ -153,6 +166,7 @@ extern "C" void suma_localizer_destroy(suma_localizer* l) {
   if (l->c && l->c->stream) hipStreamSynchronize(l->c->stream);
   l->map = LocMap(); /* device blocks go before the ctx */
   l->ev_totals.reset(), l->ev_totals_h.reset(), l->ev_source.reset();
+  l->nv = Novel();
   suma_frame_destroy(l->frame);
   suma_ctx_destroy(l->c);
   delete l;
@@ -168,6 +182,9 @@ extern "C" int suma_localizer_set_map_device(suma_localizer* l, const suma_world
   if (n && ((uintptr_t)d_records & 15u)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_map: records must be 16-byte aligned");
   int r = localize_bin(c, d_records, n, &l->map, l->ev_wanted);
   if (r) return r;
+  if (l->nv.on) HIP_TRY(c, hipMemsetAsync(l->nv.state, 0, sizeof(NovelState), c->stream));
+  l->scan_count = 0;
+  l->last_collected = 0;
   memset(&l->last_counts, 0, sizeof(l->last_counts));
   l->last_observed = 0;
   l->have_map = true;
@@ -306,6 +323,18 @@ static int process_scan(suma_localizer* l, const suma_float4* points, const floa
       int r = observe(l, l->frame, pose, &l->last_counts);
       if (r) return r;
       l->last_observed = 1;
+    }
+  }
+  /* 9. with novelty on: one collection of the scan's own frame at the final pose (k_novel.hip), enqueued only */
+  if (!frame_ready) {
+    const uint32_t scan_id = l->scan_count++;
+    if (l->nv.on) {
+      l->last_collected = 0;
+      if (l->n_window && (res->tracked || !l->nv.np.tracked_only) && finite16(pose)) {
+        int r = collect(l, l->frame, pose, scan_id);
+        if (r) return r;
+        l->last_collected = 1;
+      }
     }
   }
   return SUMA_OK;
@@ -598,5 +627,260 @@ extern "C" int suma_change_prune_mask(const suma_change_evidence* evidence, uint
     removed += gone ? 1u : 0u;
   }
   if (n_removed) *n_removed = removed;
+  return SUMA_OK;
+}
+
+/* ---- novelty (include/suma_hip.h states the entries, k_novel.hip the specification) ---- */
+extern "C" void suma_novel_params_default(suma_novel_params* np) {
+  if (!np) return;
+  np->agree_margin = 0.5f;
+  np->max_range = 50.0f;
+  np->tracked_only = 1;
+  np->max_candidates = 4194304u;
+}
+
+extern "C" void suma_novel_fuse_params_default(const suma_params* params, suma_novel_fuse_params* fp) {
+  if (!fp) return;
+  fp->voxel_size = 0.2f;
+  fp->min_views = 2u;
+  fp->confidence = (params ? params->confidence_threshold : 0.0f) + 1.0f;
+}
+
+static int novelty_ready(suma_localizer* l, const char* who) {
+  if (!l->nv.on) return fail(l->c, SUMA_ERR_INVALID, std::string(who) + ": novelty is off (suma_localizer_enable_novelty)");
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_enable_novelty(suma_localizer* l, const suma_novel_params* np) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  suma_novel_params q;
+  suma_novel_params_default(&q);
+  if (np) q = *np;
+  const char* why = nullptr;
+  if (!(std::isfinite(q.agree_margin) && q.agree_margin > 0.0f)) why = "agree_margin must be finite and > 0";
+  else if (!(std::isfinite(q.max_range) && q.max_range > 0.0f)) why = "max_range must be finite and > 0";
+  else if (q.max_candidates < 1u || q.max_candidates > (1u << 30)) why = "max_candidates must be 1 .. 2^30";
+  if (why) return fail(c, SUMA_ERR_INVALID, std::string("suma_localizer_enable_novelty: ") + why);
+  Novel& nv = l->nv;
+  const size_t P = (size_t)c->p.data_width * (size_t)c->p.data_height;
+  const size_t blocks = (P + 255) / 256;
+  const bool fresh = !nv.on || nv.np.max_candidates != q.max_candidates;
+  if (fresh) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    Novel nw;
+    hipError_t e = nw.cand.alloc(3 * (size_t)q.max_candidates);
+    if (e == hipSuccess) e = nw.mark.alloc(P);
+    if (e == hipSuccess) e = nw.flag.alloc(P);
+    if (e == hipSuccess) e = nw.block_counts.alloc(8 * blocks);
+    if (e == hipSuccess) e = nw.state.alloc(1);
+    if (e == hipSuccess) e = nw.stage_h.alloc(16);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(c, SUMA_ERR_NOMEM, "suma_localizer_enable_novelty: no device memory for " +
+                                     std::to_string(q.max_candidates) + " candidates");
+    }
+    HIP_TRY(c, hipMemsetAsync(nw.state, 0, sizeof(NovelState), c->stream));
+    HIP_TRY(c, hipMemsetAsync(nw.mark, 0, P, c->stream));
+    nv = std::move(nw);
+    l->last_collected = 0;
+  }
+  nv.np = q;
+  nv.on = true;
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_disable_novelty(suma_localizer* l) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (l->nv.on) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a collection may still write them */
+    l->nv = Novel();
+  }
+  l->last_collected = 0;
+  return SUMA_OK;
+}
+
+/* the device state into host words (blocking): count, n_overflow, done, pad, counts[8] */
+static int novel_state(suma_localizer* l, NovelState* out) {
+  suma_ctx* c = l->c;
+  HIP_TRY(c, hipMemcpyAsync(l->nv.stage_h, l->nv.state, sizeof(NovelState), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(out, l->nv.stage_h.p, sizeof(NovelState));
+  return SUMA_OK;
+}
+
+static int novel_overflow(suma_localizer* l, const NovelState& s, const char* who) {
+  if (!s.n_overflow) return SUMA_OK;
+  return fail(l->c, SUMA_ERR_CAPACITY, std::string(who) + ": " + std::to_string(s.n_overflow) +
+                                       " novel texels did not fit into max_candidates = " +
+                                       std::to_string(l->nv.np.max_candidates));
+}
+
+extern "C" int suma_localizer_collect_frame(suma_localizer* l, const suma_frame* frame, const double T[16], uint32_t scan_id,
+                                            suma_novel_counts* counts) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = novelty_ready(l, "suma_localizer_collect_frame");
+  if (r) return r;
+  if (!frame || !T) return fail(c, SUMA_ERR_INVALID, "suma_localizer_collect_frame: NULL argument");
+  if (frame->ctx != c) return fail(c, SUMA_ERR_INVALID, "suma_localizer_collect_frame: the frame belongs to another ctx");
+  if (frame->width != c->p.data_width || frame->height != c->p.data_height)
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_collect_frame: the frame must have the data image's size");
+  if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_collect_frame: non-finite pose");
+  if (counts) memset(counts, 0, sizeof(*counts));
+  l->last_collected = 0;
+  if (!l->have_map || !l->n_window) return SUMA_OK;
+  r = collect(l, frame, T, scan_id);
+  if (r) return r;
+  l->last_collected = 1;
+  if (counts) {
+    NovelState s;
+    r = novel_state(l, &s);
+    if (r) return r;
+    memcpy(counts, s.counts, sizeof(*counts));
+  }
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_last_collection(suma_localizer* l, suma_novel_counts* counts, int32_t* collected) {
+  if (!l) return SUMA_ERR_INVALID;
+  int r = novelty_ready(l, "suma_localizer_last_collection");
+  if (r) return r;
+  NovelState s;
+  r = novel_state(l, &s);
+  if (r) return r;
+  if (counts) {
+    memset(counts, 0, sizeof(*counts));
+    if (l->last_collected) memcpy(counts, s.counts, sizeof(*counts));
+  }
+  if (collected) *collected = l->last_collected;
+  return novel_overflow(l, s, "suma_localizer_last_collection");
+}
+
+static int candidates_download(suma_localizer* l, suma_world_surfel* out, uint32_t capacity, uint32_t* n, bool to_device,
+                               const char* who) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = novelty_ready(l, who);
+  if (r) return r;
+  if (!n || (capacity && !out)) return fail(c, SUMA_ERR_INVALID, std::string(who) + ": NULL argument");
+  NovelState s;
+  r = novel_state(l, &s);
+  if (r) return r;
+  *n = s.count;
+  const uint32_t m = s.count < capacity ? s.count : capacity;
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(out, l->nv.cand, (size_t)m * sizeof(suma_world_surfel),
+                              to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return novel_overflow(l, s, who);
+}
+
+extern "C" int suma_localizer_novel_candidates(suma_localizer* l, suma_world_surfel* host, uint32_t capacity, uint32_t* n) {
+  return candidates_download(l, host, capacity, n, false, "suma_localizer_novel_candidates");
+}
+
+extern "C" int suma_localizer_novel_candidates_device(suma_localizer* l, suma_world_surfel* d_out, uint32_t capacity,
+                                                      uint32_t* n) {
+  return candidates_download(l, d_out, capacity, n, true, "suma_localizer_novel_candidates_device");
+}
+
+extern "C" int suma_localizer_set_novel_candidates(suma_localizer* l, const suma_world_surfel* host, uint32_t n) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = novelty_ready(l, "suma_localizer_set_novel_candidates");
+  if (r) return r;
+  if (n && !host) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_novel_candidates: NULL records with n > 0");
+  if (n > l->nv.np.max_candidates)
+    return fail(c, SUMA_ERR_CAPACITY, "suma_localizer_set_novel_candidates: " + std::to_string(n) + " records, max_candidates = " +
+                                      std::to_string(l->nv.np.max_candidates));
+  HIP_TRY(c, hipMemsetAsync(l->nv.state, 0, sizeof(NovelState), c->stream));
+  if (n) {
+    HIP_TRY(c, hipMemcpyAsync(l->nv.cand, host, (size_t)n * sizeof(suma_world_surfel), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&l->nv.state->count, &n, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream)); /* pageable sources: the copies have left them */
+  l->last_collected = 0;
+  return SUMA_OK;
+}
+
+static int novel_fused(suma_localizer* l, const suma_novel_fuse_params* fp, suma_world_surfel* out, uint32_t* views,
+                       uint32_t capacity, suma_novel_stats* stats, bool to_device, const char* who) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = novelty_ready(l, who);
+  if (r) return r;
+  if (!stats || (capacity && (!out || !views))) return fail(c, SUMA_ERR_INVALID, std::string(who) + ": NULL argument");
+  suma_novel_fuse_params q;
+  suma_novel_fuse_params_default(&c->p, &q);
+  if (fp) q = *fp;
+  if (!(std::isfinite(q.voxel_size) && q.voxel_size > 0.0f))
+    return fail(c, SUMA_ERR_INVALID, std::string(who) + ": voxel_size must be finite and > 0");
+  if (q.min_views < 1u) return fail(c, SUMA_ERR_INVALID, std::string(who) + ": min_views must be at least 1");
+  if (std::isnan(q.confidence)) return fail(c, SUMA_ERR_INVALID, std::string(who) + ": confidence is NaN");
+  memset(stats, 0, sizeof(*stats));
+  NovelState s;
+  r = novel_state(l, &s);
+  if (r) return r;
+  stats->n_candidates = s.count;
+  stats->n_overflow = s.n_overflow;
+  suma_world_surfel* d_out = out;
+  uint32_t* d_views = views;
+  const uint32_t cap = capacity < s.count ? capacity : s.count; /* no more voxels than candidates */
+  if (!to_device && cap) {
+    if ((r = grow(c, l->nv.fused, 3 * (size_t)cap, {c->stream})) < 0) return r;
+    if ((r = grow(c, l->nv.fused_views, cap, {c->stream})) < 0) return r;
+    d_out = reinterpret_cast<suma_world_surfel*>(l->nv.fused.p);
+    d_views = l->nv.fused_views;
+  }
+  uint32_t cnt[3];
+  r = novel_fuse(c, l->nv, s.count, q, d_out, d_views, cap, cnt);
+  if (r) return r;
+  stats->n_dropped = cnt[0];
+  stats->n_voxels = cnt[1];
+  stats->n_out = cnt[2];
+  const uint32_t m = cnt[2] < cap ? cnt[2] : cap;
+  if (!to_device && m) {
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)m * sizeof(suma_world_surfel), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(views, d_views, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return novel_overflow(l, s, who);
+}
+
+extern "C" int suma_localizer_novel(suma_localizer* l, const suma_novel_fuse_params* fp, suma_world_surfel* host,
+                                    uint32_t* views, uint32_t capacity, suma_novel_stats* stats) {
+  return novel_fused(l, fp, host, views, capacity, stats, false, "suma_localizer_novel");
+}
+
+extern "C" int suma_localizer_novel_device(suma_localizer* l, const suma_novel_fuse_params* fp, suma_world_surfel* d_out,
+                                           uint32_t* d_views, uint32_t capacity, suma_novel_stats* stats) {
+  return novel_fused(l, fp, d_out, d_views, capacity, stats, true, "suma_localizer_novel_device");
+}
+
+extern "C" int suma_localizer_novel_marks(suma_localizer* l, uint8_t* host, uint32_t capacity, uint32_t* n) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = novelty_ready(l, "suma_localizer_novel_marks");
+  if (r) return r;
+  if (!n || (capacity && !host)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_novel_marks: NULL argument");
+  *n = (uint32_t)c->p.data_width * (uint32_t)c->p.data_height;
+  const uint32_t m = *n < capacity ? *n : capacity;
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(host, l->nv.mark, m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_clear_novelty(suma_localizer* l) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = novelty_ready(l, "suma_localizer_clear_novelty");
+  if (r) return r;
+  HIP_TRY(c, hipMemsetAsync(l->nv.state, 0, sizeof(NovelState), c->stream));
+  l->last_collected = 0;
   return SUMA_OK;
 }

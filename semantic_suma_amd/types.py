@@ -206,6 +206,57 @@ EVIDENCE_DTYPE = np.dtype([("hits", "<u4"), ("misses", "<u4"), ("occluded", "<u4
 assert EVIDENCE_DTYPE.itemsize == 16
 
 
+class NovelParams(C.Structure):
+    """``struct suma_novel_params``: what the collection of newly seen surfaces of core.Localizer (csrc/k_novel.hip) takes
+    for explained and too far, and how many candidates it holds; ``NovelParams.defaults()`` = suma_novel_params_default"""
+    _fields_ = [("agree_margin", f32), ("max_range", f32), ("tracked_only", i32), ("max_candidates", u32)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "NovelParams":
+        p = cls(agree_margin=0.5, max_range=50.0, tracked_only=1, max_candidates=4194304)
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        return p
+
+
+class NovelFuseParams(C.Structure):
+    """``struct suma_novel_fuse_params``; ``NovelFuseParams.defaults(params)`` = suma_novel_fuse_params_default: the
+    confidence new records get is confidence_threshold + 1, so that the localiser renders them"""
+    _fields_ = [("voxel_size", f32), ("min_views", u32), ("confidence", f32)]
+
+    @classmethod
+    def defaults(cls, params=None, **overrides) -> "NovelFuseParams":
+        conf = C.c_float((params.confidence_threshold if params is not None else 0.0)).value
+        p = cls(voxel_size=0.2, min_views=2, confidence=float(np.float32(conf) + np.float32(1.0)))
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        return p
+
+
+class NovelCounts(C.Structure):
+    """``struct suma_novel_counts``: what one collection did with the texels of the frame"""
+    _fields_ = [("n_texels", u32), ("no_return", u32), ("out_of_range", u32), ("grazing", u32), ("explained", u32),
+                ("novel", u32), ("stored", u32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+NOVEL_COUNTS = tuple(k for k, _ in NovelCounts._fields_)
+
+
+class NovelStats(C.Structure):
+    """``struct suma_novel_stats``"""
+    _fields_ = [("n_candidates", u32), ("n_overflow", u32), ("n_dropped", u32), ("n_voxels", u32), ("n_out", u32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 PLACE_MAX_DIM = 64       # SUMA_PLACE_MAX_DIM: rings and sectors
 PLACE_MAX_MATCHES = 32   # SUMA_PLACE_MAX_MATCHES
 # is_dynamic_label (csrc/dev_math.h): the moving classes K1 drops at the start of a run

@@ -8,7 +8,10 @@ exists) and a JSON summary.  --timing keeps the scans on the device and reports 
 pipeline's scans/s over the same scans in the same run, and the cost of one window rebuild.  --relocalize starts without
 a start pose; --evidence collects change evidence per map record while the scans are localised (csrc/k_change.hip), prints
 every scan's totals and, with --prune-out, writes the map without the records the default rule removes (--without takes
-objects out of the synthetic world the localised scans see).  With --relocalize the first scan goes through Localizer.relocalize against a place index (core.PlaceIndex) -- the mapping
+objects out of the synthetic world the localised scans see).  --novel collects the surfaces no record of the map explains
+(csrc/k_novel.hip), prints every scan's counts and, with --update-out, writes the updated map: the records the rule keeps
+(all of them without --evidence) followed by the fused new ones (--map-without takes objects out of the world the mapping
+run sees).  With --relocalize the first scan goes through Localizer.relocalize against a place index (core.PlaceIndex) -- the mapping
 run's own scans, or with --map the file tools/export_map.py --places wrote (--places).  Needs a GPU.
     python tools/localize.py [--map-scans 80] [--first 10] [--scans 60] [--voxel 0.1] [--width 2048] [--kitti sequences/08]
     python tools/localize.py --map map.ply --start 12.0 0.5 0.0 3.0 --first 11 --scans 20
@@ -16,6 +19,7 @@ run's own scans, or with --map the file tools/export_map.py --places wrote (--pl
     python tools/localize.py --relocalize [--candidates 8]  # no setPose: the start comes from place recognition
     python tools/localize.py --map map.ply --places map.places.npz --relocalize --first 11 --scans 20
     python tools/localize.py --evidence --without 2 41 --prune-out pruned.ply   # cube 2 and a building are gone
+    python tools/localize.py --map-without 2 41 --novel --update-out new.ply    # cube 2 and a building have arrived
 """
 import argparse
 import ctypes as C
@@ -91,6 +95,39 @@ def observe_timing(loc, scan, pose, n_window):
                 observe_over_copy=round(k / c, 3), samples=dict(kc_observe_ms=kernel, d2d_copy_ms=copy))
 
 
+def collect_timing(loc, scan, pose, n_window):
+    """kn_mark's and kn_collect + kn_emit's event times (suma_profile, one collection at a time) against event-timed
+    device-to-device copies of the bytes they touch: 32 a window record (16 of its position, 16 of the vertex texel) for
+    the marks; the frame's three maps, nine mark bytes and a flag byte a texel for the collection"""
+    ctx, p = loc.ctx, loc.params
+    frame = core.Frame(ctx, p.data_width, p.data_height)
+    core.Preprocessing(ctx).process(scan[0], frame, scan[1], scan[2], p.active_timestamps + 10)
+    held = loc.novelCandidates(allow_overflow=True)
+    ctx.profile(1)
+    mark, collect = [], []
+    for k in range(13):
+        ctx.profile_reset()
+        loc.collectFrame(frame, pose, 0)
+        ms = {r["name"]: r["total_ms"] for r in ctx.profile_get()}
+        if k >= 3:
+            mark.append(ms["novel_mark"])
+            collect.append(ms["novel_collect"])
+    ctx.profile(0)
+    loc.setNovelCandidates(held)
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    out = {}
+    for name, nbytes, kernel in (("kn_mark", 32 * n_window, mark), ("kn_collect", 58 * p.data_width * p.data_height, collect)):
+        src, dst = ctx.device_array(np.zeros(nbytes, dtype=np.uint8)), ctx.device_array(np.zeros(nbytes, dtype=np.uint8))
+        copy = event_ms(ctx, lambda: hip.hipMemcpyAsync(dst, src, nbytes, 3, C.c_void_p(ctx.stream)))
+        ctx.device_free(src)
+        ctx.device_free(dst)
+        k, c = float(np.median(kernel)), float(np.median(copy))
+        out[name] = dict(bytes=nbytes, kernel_us_median10=round(1e3 * k, 2), d2d_copy_us_median10=round(1e3 * c, 2),
+                         kernel_over_copy=round(k / c, 3), samples=dict(kernel_ms=kernel, d2d_copy_ms=copy))
+    return out
+
+
 def pose_from(x, y, z, yaw_deg):
     a = np.deg2rad(yaw_deg)
     T = np.eye(4)
@@ -125,9 +162,16 @@ def main():
     ap.add_argument("--prune-out", default=None, metavar="FILE.ply", help="with --evidence: write the map the default rule keeps")
     ap.add_argument("--without", type=int, nargs="*", default=[], metavar="BOX",
                     help="synthetic scans: boxes of synth._boxes the localised scans do not see (0-22 cubes, 23.. buildings)")
+    ap.add_argument("--novel", action="store_true", help="collect the surfaces no map record explains and print every scan's counts")
+    ap.add_argument("--update-out", default=None, metavar="FILE.ply",
+                    help="with --novel: write the updated map (what the rule keeps, then the fused new records)")
+    ap.add_argument("--map-without", type=int, nargs="*", default=[], metavar="BOX",
+                    help="synthetic scans: boxes of synth._boxes the mapping run does not see")
     args = ap.parse_args()
     if args.prune_out and not args.evidence:
         ap.error("--prune-out needs --evidence")
+    if args.update_out and not args.novel:
+        ap.error("--update-out needs --novel")
     over = {k: v for k, v in (("submap_extent", args.extent), ("submap_dimension", args.dimension)) if v is not None}
     p = params_with_size(args.width, args.height, **over)
     n_map = args.map_scans if args.map_scans is not None else (300 if args.timing else 80)
@@ -151,7 +195,7 @@ def main():
             index = core.PlaceIndex(PlaceParams.defaults(max_range=args.place_range), capacity=n_map)
         mapping_s, timed = 0.0, 0
         for k in range(n_map):
-            sc = read_scan(args, k)
+            sc = read_scan(args, k, tuple(args.map_without))
             if args.timing and k in ks and k > 0:  # the mapping rate over the scans that are localised below, resident
                 d = resident(pipe.ctx, sc)
                 pipe.ctx.synchronize()
@@ -182,6 +226,8 @@ def main():
     loc = core.Localizer(p, LocalizerParams.defaults(p, constant_velocity=int(not args.no_motion_model)))
     if args.evidence:
         loc.enableEvidence()
+    if args.novel:
+        loc.enableNovelty()
     t = time.perf_counter()
     dropped = loc.setMap(records)
     res.update(map_records=int(len(records)), dropped=dropped, set_map_ms=round(1e3 * (time.perf_counter() - t), 3))
@@ -190,7 +236,7 @@ def main():
         loc.setPose(start)
     scans = [read_scan(args, k, tuple(args.without)) for k in ks]
     host_scans = scans
-    observations = []
+    observations, collections = [], []
     if args.timing:
         scans = [resident(loc.ctx, sc) for sc in scans]
         loc.ctx.synchronize()
@@ -215,6 +261,8 @@ def main():
                        else loc.processScan(*sc, fixed_iterations=args.iterations))
             if args.evidence:
                 observations.append(loc.lastObservation())
+            if args.novel and not args.timing:  # the counts wait for the device: a timed run asks once, at the end
+                collections.append(loc.lastCollection(allow_overflow=True))
         except core.SumaError as e:  # a run that has left the map ends on a pose that is no longer finite
             res.update(lost_at_scan=k, error=str(e))
             break
@@ -240,6 +288,18 @@ def main():
         if args.prune_out:
             mapio.write_ply(args.prune_out, kept)
             res["pruned_map"] = args.prune_out
+    if args.novel:
+        for k, (cnt, collected) in zip(ks[len(ks) - len(collections):] if args.relocalize else ks, collections):
+            print(f"scan {k:5d}  collected {int(collected)}  " + "  ".join(f"{n} {v}" for n, v in cnt.items()))
+        fused, views, st = loc.novel(allow_overflow=True, stats=True)
+        res["novel"] = dict(st, candidates_per_scan=round(st["n_candidates"] / max(1, len(out)), 1),
+                            candidate_bytes=48 * st["n_candidates"],
+                            per_scan=[c["stored"] for c, _ in collections] if collections else None,
+                            max_views=int(views.max()) if len(views) else 0)
+        if args.update_out:
+            upd = np.concatenate([core.pruned_map(records, loc.evidence())[0] if args.evidence else records, fused])
+            mapio.write_ply(args.update_out, upd)
+            res.update(updated_map=args.update_out, updated_records=int(len(upd)))
     origin, n_window, rebuilds = loc.window()
     res.update(tracked=sum(r["tracked"] for r in out), window_rebuilds=sum(r["window_rebuilt"] for r in out),
                n_window=n_window, worst_distance_to_mapping_pose_m=round(worst, 4))
@@ -256,6 +316,8 @@ def main():
         res["window_rebuild_ms"] = [round(1e3 * x, 3) for x in times]
         if args.evidence and "lost_at_scan" not in res:
             res["observe"] = observe_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], loc.window()[1])
+        if args.novel and "lost_at_scan" not in res:
+            res["collect"] = collect_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], loc.window()[1])
     loc.close()
     print(json.dumps(res))
 
