@@ -112,7 +112,18 @@ typedef struct suma_icp_objective {
 int suma_icp_set_objective(suma_ctx* ctx, const suma_icp_objective* objective);
 /* ---- Frame2Model::jacobianProducts (Frame2Model.h:50, Frame2Model.cpp:136-261): K6 at the given
  *      pose.  JtJ 6x6 column-major, Jtr 6; acc (optional) = the raw 2^-28 fixed-point sums,
- *      SUMA_ACC_WORDS int64.  Returns F in stats->error. */
+ *      SUMA_ACC_WORDS int64.  Returns F in stats->error.
+ *      Domain of the sums (the same for every entry point that runs K6: suma_icp_minimize, _minimize_batch, the scan
+ *      pipeline, loop-closure verification, the localiser):
+ *        - every fp32 term that enters a fixed-point word -- (w J_i) J_j, (w r) J_i, (w r) r -- must satisfy
+ *          |term| < 2^23: below that bound the device's conversion is round(term * 2^28) to nearest even, exactly as
+ *          the oracle's llrint.  With lidar ranges <= 120 m the largest term is about 1.5e4 (|v x n|^2).  A term at or
+ *          beyond the bound leaves ONLY the word it belongs to unspecified; every other word and the three counters
+ *          are still exact.  Nothing saturates.
+ *        - every texel of a frame handed to K6, valid or not, must hold finite values (no NaN, no inf).
+ *        - a pixel that does not contribute -- no pair, or an outlier -- never changes JtJ, Jtr or the inlier sum
+ *          (words 0..26 and 28), whatever finite values it holds, including ones whose products overflow.  Word 27
+ *          (F over ALL pairs) takes an outlier's w r^2 as the reference does, under the bound above. */
 int suma_icp_jacobian_products(suma_ctx* ctx, const double pose[16], uint32_t iteration, double JtJ[36], double Jtr[6],
                                int64_t* acc, suma_icp_stats* stats);
 /* ---- LieGaussNewton::minimize (LieGaussNewton.h:32, LieGaussNewton.cpp:13-79) with

@@ -802,20 +802,24 @@ __device__ __forceinline__ void icp_iter_body(const IterArgs& g, const uint32_t 
       wr2 = (weight * residual) * residual;
       wr = weight * residual;
       is_inlier = inlier;
-      J[0] = n_m.x;
-      J[1] = n_m.y;
-      J[2] = n_m.z;
-      J[3] = cp.x;
-      J[4] = cp.y;
-      J[5] = cp.z;
+      /* J of an inlier only: an outlier's J stays zero.  Its cp can be +-inf although both texels are finite (two
+       * coordinates near FLT_MAX: cross3 overflows), and 0 * inf below would be a NaN in every word of the pixel. */
+      J[0] = inlier ? n_m.x : 0.0f;
+      J[1] = inlier ? n_m.y : 0.0f;
+      J[2] = inlier ? n_m.z : 0.0f;
+      J[3] = inlier ? cp.x : 0.0f;
+      J[4] = inlier ? cp.y : 0.0f;
+      J[5] = inlier ? cp.z : 0.0f;
       wgt = weight;
     }
     /* Round 6: a term that does not contribute is formed from a ZERO WEIGHT instead of being selected away behind its
      * conversion -- fix_bits(0) is the magic number itself, so every lane-trip adds exactly one magic number to each of
      * the 29 fixed-point words and the consume step removes lane_trips(P) of them (round 5: 29 64-bit selects per pixel
      * and a bias of n_inlier / n_valid magic numbers).  The sums are the same integers; ~55 VALU instructions per
-     * pixel fewer in a phase that is issue bound at two waves per SIMD.  J is finite for every pair (both texels valid),
-     * so 0 * J is a zero. */
+     * pixel fewer in a phase that is issue bound at two waves per SIMD.  0 * J is a zero only for a finite J, and
+     * finite texels do not make J finite (see above), so a pixel that does not contribute has J = 0 as well: its 28
+     * gated terms are exact zeros whatever it holds.  Word 27 (F over ALL pairs) takes the outliers' w r^2 ungated, as
+     * the reference sums it; a non-finite or out-of-range (>= 2^23) term there leaves that one word unspecified. */
     const bool in = pair && is_inlier;
     const float wgt_in = in ? wgt : 0.0f, wr_in = in ? wr : 0.0f, wr2_in = in ? wr2 : 0.0f;
     /* words 0..15: the first 16 entries of the upper triangle of J^T W J (row-major: (0,0)..(0,5), (1,1)..(1,5),
