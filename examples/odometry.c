@@ -4,12 +4,18 @@
  * (KITTI devkit format: the upper 3x4 of the sensor pose, row-major).
  *
  *   cc -O2 -Iinclude examples/odometry.c -Lsemantic_suma_amd -lsuma_hip -Wl,-rpath,$PWD/semantic_suma_amd -o odometry
- *   ./odometry [--close-loops] [--checkpoint FILE --checkpoint-every N] [--resume FILE]
- *              /data/kitti/sequences/00/velodyne 4541 [labels_dir]
+ *   ./odometry [--close-loops] [--deskew [--clockwise] [--t-ref X]] [--checkpoint FILE --checkpoint-every N]
+ *              [--resume FILE] /data/kitti/sequences/00/velodyne 4541 [labels_dir]
  *
  * --close-loops: the reference's close-loops = true (config/default.xml:71).  The pipeline keeps a pose graph, verifies
  * loop closures and integrates the optimised trajectory while it runs; the poses are then printed once, at the end, from
  * the pose graph (SurfelMapping::getOptimizedPoses) instead of scan by scan from the odometry.
+ *
+ * --deskew: the scans are RAW sweeps of a moving sensor (KITTI's odometry scans are compensated already and need none of
+ * this): every scan is motion compensated in front of the preprocessing, with the previous scan's increment as the motion
+ * over one sweep (suma_pipeline_enable_deskew).  The point's azimuth gives its time; --clockwise for a sensor that turns
+ * clockwise seen from above (Velodyne), --t-ref X for the instant of the sweep the pose refers to (default 0.5).  A
+ * checkpoint holds none of this: give the options again with --resume.
  *
  * --checkpoint FILE --checkpoint-every N: after every N-th scan the whole session (suma_pipeline_checkpoint_save) is
  * written to FILE.tmp and renamed to FILE, so FILE is always a complete image.
@@ -79,11 +85,16 @@ static void* read_file(const char* file, uint64_t* bytes) {
 }
 
 int main(int argc, char** argv) {
-  int close_loops = 0, checkpoint_every = 0;
+  int close_loops = 0, checkpoint_every = 0, deskew = 0;
+  suma_deskew_params dp;
+  suma_deskew_params_default(&dp);
   const char *prog = argv[0], *checkpoint_file = NULL, *resume_file = NULL;
   while (argc > 1 && strncmp(argv[1], "--", 2) == 0) {
     int used = 1;
     if (strcmp(argv[1], "--close-loops") == 0) close_loops = 1;
+    else if (strcmp(argv[1], "--deskew") == 0) deskew = 1;
+    else if (strcmp(argv[1], "--clockwise") == 0) dp.clockwise = 1;
+    else if (strcmp(argv[1], "--t-ref") == 0 && argc > 2) dp.t_ref = (float)atof(argv[2]), used = 2;
     else if (strcmp(argv[1], "--checkpoint") == 0 && argc > 2) checkpoint_file = argv[2], used = 2;
     else if (strcmp(argv[1], "--checkpoint-every") == 0 && argc > 2) checkpoint_every = atoi(argv[2]), used = 2;
     else if (strcmp(argv[1], "--resume") == 0 && argc > 2) resume_file = argv[2], used = 2;
@@ -91,7 +102,7 @@ int main(int argc, char** argv) {
     argc -= used, argv += used;
   }
   if (argc < 3 || (argc > 1 && strncmp(argv[1], "--", 2) == 0) || (checkpoint_file != NULL) != (checkpoint_every > 0)) {
-    fprintf(stderr, "usage: %s [--close-loops] [--checkpoint FILE --checkpoint-every N] [--resume FILE] <velodyne_dir> "
+    fprintf(stderr, "usage: %s [--close-loops] [--deskew [--clockwise] [--t-ref X]] [--checkpoint FILE --checkpoint-every N] [--resume FILE] <velodyne_dir> "
                     "<n_scans> [labels_dir]\n", prog);
     return 2;
   }
@@ -146,6 +157,13 @@ int main(int argc, char** argv) {
       suma_pipeline_destroy(pipe);
       return 1;
     }
+  }
+
+  if (deskew && suma_pipeline_enable_deskew(pipe, &dp) != SUMA_OK) { /* after a load: the image holds no deskew state */
+    fprintf(stderr, "suma_pipeline_enable_deskew: %s\n", suma_last_error(suma_pipeline_ctx(pipe)));
+    suma_pipeline_destroy(pipe);
+    free(image);
+    return 1;
   }
 
   suma_float4* pts = NULL;

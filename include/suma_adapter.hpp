@@ -471,6 +471,20 @@ class SurfelMapping {
     if (!ok) throw std::runtime_error("SurfelMapping::loadCheckpoint: cannot read " + path);
     chk(suma_pipeline_checkpoint_load(s_, image.data(), image.size()), "SurfelMapping::loadCheckpoint");
   }
+  /* ---- motion compensation of raw sweeps (suma_pipeline_*deskew*, csrc/k_deskew.hip): nothing in the reference to
+   *      mirror, its KITTI scans are compensated already.  While enabled, processScan corrects the points in front of
+   *      the preprocessing with the last increment as the motion over one sweep; setDeskewMotion overrides it once
+   *      (column-major double[16]: an IMU, wheel odometry, the first scans).  A checkpoint holds none of this: enable it
+   *      again after loadCheckpoint. ---- */
+  void enableDeskew(const suma_deskew_params* dp = nullptr) { chk(suma_pipeline_enable_deskew(s_, dp), "SurfelMapping::enableDeskew"); }
+  void disableDeskew() { chk(suma_pipeline_disable_deskew(s_), "SurfelMapping::disableDeskew"); }
+  void setDeskewMotion(const double* motion16) { chk(suma_pipeline_set_deskew_motion(s_, motion16), "SurfelMapping::setDeskewMotion"); }
+  /* what the last corrected scan used; returns its source (SUMA_DESKEW_MOTION_*) */
+  int32_t deskewMotion(double* motion16) const {
+    int32_t source = SUMA_DESKEW_MOTION_NONE;
+    chk(suma_pipeline_deskew_motion(s_, motion16, &source), "SurfelMapping::deskewMotion");
+    return source;
+  }
   /* ---- device parts of checkLoopClosure ---- */
   /* :546-574, a tracked closure verified again; on success the caller sets currentPose_old_ = out.pose_old (:581) */
   suma_loop_track trackLoopClosure(double min_valid = 0.2, double max_outlier = 0.85, double max_diff = 0.1) {
@@ -728,6 +742,16 @@ class Localizer {
     chk(suma_localizer_enable_novelty(l_, np), "Localizer::enableNovelty");
   }
   void disableNovelty() { chk(suma_localizer_disable_novelty(l_), "Localizer::disableNovelty"); }
+  /* ---- motion compensation of raw sweeps: as SurfelMapping's, with the localiser's increment as the motion (the
+   *      identity after setPose); relocalize does not correct ---- */
+  void enableDeskew(const suma_deskew_params* dp = nullptr) { chk(suma_localizer_enable_deskew(l_, dp), "Localizer::enableDeskew"); }
+  void disableDeskew() { chk(suma_localizer_disable_deskew(l_), "Localizer::disableDeskew"); }
+  void setDeskewMotion(const double* motion16) { chk(suma_localizer_set_deskew_motion(l_, motion16), "Localizer::setDeskewMotion"); }
+  int32_t deskewMotion(double* motion16) {
+    int32_t source = SUMA_DESKEW_MOTION_NONE;
+    chk(suma_localizer_deskew_motion(l_, motion16, &source), "Localizer::deskewMotion");
+    return source;
+  }
   /* one collection of a data-sized frame of ctx() at the sensor pose T (column-major, world frame) */
   suma_novel_counts collectFrame(const suma_frame* frame, const double T[16], uint32_t scan_id) {
     suma_novel_counts c;

@@ -1045,6 +1045,66 @@ int suma_localizer_relocalize_device(suma_localizer* l, suma_place_index* idx, c
                                      const suma_float4* d_points, const float* d_labels, const float* d_probs, uint32_t n,
                                      uint32_t max_candidates, int32_t fixed_iterations, suma_relocalize_result* result);
 
+/* ---- motion compensation (deskewing) of raw sweeps (csrc/k_deskew.hip states the operation).
+ *      A point measured at sweep fraction s in [0, 1], in the sensor frame of that instant, is moved into the sensor
+ *      frame at fraction t_ref:  p' = Exp((s - t_ref) * scale * Log(motion)) * p,  motion = pose_prev^-1 * pose, the
+ *      sensor's rigid motion over one sweep period (column-major double[16]).  The fourth component is copied bit for
+ *      bit; a point with a non-finite coordinate or time keeps all its bits.  s comes from the point's azimuth
+ *      (suma_deskew_params, below) or from the caller's times[n].
+ *   suma_deskew_points(_device): n points (host / device), out may equal the input; the device entry enqueues on the ctx
+ *      stream and returns.  dp NULL = the defaults (azimuth time, counter-clockwise, start_azimuth 0, t_ref 0.5, scale 1).
+ *      A motion that is bitwise the identity launches nothing and leaves every bit alone.  n = 0 is SUMA_OK.
+ *      SUMA_ERR_INVALID with a message: t_ref outside [0, 1], a non-finite field, start_azimuth outside [-2 pi, 2 pi], an
+ *      unknown time source, the `times` source without times, a NULL or non-finite motion, device points that are not
+ *      16-byte aligned.
+ *   Pipeline: while enabled, suma_pipeline_process_scan(_device) and suma_pipeline_begin_scan(_device) correct the scan
+ *      in front of K1 with the motion suma_pipeline_last_increment returns at that moment (the identity before the first
+ *      pose update, so the first scan keeps its bits), on the stream K1 reads the points from and without any new
+ *      synchronisation.  The caller's points are never written: the corrected scan lives in a block the pipeline owns.
+ *      The scan entries carry no times, so only the azimuth source can be enabled.
+ *      suma_pipeline_set_deskew_motion: a one-shot override for the next scan (an IMU, wheel odometry, the first scans);
+ *      it is dropped by _disable_deskew and suma_pipeline_reset.  suma_pipeline_deskew_motion: what the last corrected
+ *      scan used and where it came from (SUMA_DESKEW_MOTION_*; NONE and the identity before any).
+ *      While enabled, the entries that hand a scan over before the previous pose exists return SUMA_ERR_INVALID and
+ *      change nothing: suma_pipeline_prefetch_scan, _process_prefetched, _begin_prefetched, _process_scan_async, the four
+ *      *_scan_scores* entries and suma_pipeline_run_scans.  enable is refused between begin_scan and update_map and
+ *      while prefetched scans are pending.  With the correction never enabled nothing of it runs.
+ *   Checkpoints hold no deskew state: the image is unchanged, a host enables the correction again after a load, and
+ *      since last_increment is in the image the resumed run continues bit for bit.  A pending one-shot override is NOT
+ *      saved.
+ *   Localiser: the same switch on suma_localizer_process_scan(_device), with the `increment` of its step 7 as the motion
+ *      (kept with constant_velocity = 0 too; the identity after suma_localizer_set_pose).  suma_localizer_relocalize
+ *      does not correct.  Evidence and novelty read the frame the localiser holds, hence the corrected one. */
+/* The parameters (they live here and not in suma_types.h, which belongs to the CPU oracle as well).
+ * 20 bytes: int32 time_source @0, int32 clockwise @4, float start_azimuth @8, t_ref @12, scale @16. */
+enum { SUMA_DESKEW_TIME_AZIMUTH = 0, SUMA_DESKEW_TIME_TIMES = 1 };
+/* where the motion of the last corrected scan came from */
+enum { SUMA_DESKEW_MOTION_NONE = 0, SUMA_DESKEW_MOTION_INCREMENT = 1, SUMA_DESKEW_MOTION_OVERRIDE = 2 };
+typedef struct suma_deskew_params {
+  int32_t time_source;  /* SUMA_DESKEW_TIME_AZIMUTH: the sweep fraction of a point is its azimuth's share of the turn;
+                           SUMA_DESKEW_TIME_TIMES: the caller's times[n] */
+  int32_t clockwise;    /* azimuth time only: 0 = the beam turns counter-clockwise seen from +z (atan2(y, x) grows) */
+  float start_azimuth;  /* azimuth time only: atan2(y, x) of the sweep's first column, radians, in [-2 pi, 2 pi] */
+  float t_ref;          /* the sweep fraction whose sensor frame the points are moved into, in [0, 1] */
+  float scale;          /* the sweep period as a fraction of the interval `motion` spans (1: one sweep per scan) */
+} suma_deskew_params;
+void suma_deskew_params_default(suma_deskew_params* dp);
+/* host only, no device needed: SUMA_OK, or the SUMA_ERR_INVALID suma_deskew_points(_device) would return for these
+ * parameters, this motion and (for the `times` source) times present or not; the text is suma_last_error(NULL) */
+int suma_deskew_check(const suma_deskew_params* dp, int have_times, const double motion[16]);
+int suma_deskew_points(suma_ctx* ctx, const suma_deskew_params* dp, const suma_float4* points, const float* times_or_null,
+                       uint32_t n, const double motion[16], suma_float4* out);
+int suma_deskew_points_device(suma_ctx* ctx, const suma_deskew_params* dp, const suma_float4* d_points,
+                              const float* d_times_or_null, uint32_t n, const double motion[16], suma_float4* d_out);
+int suma_pipeline_enable_deskew(suma_pipeline* s, const suma_deskew_params* dp);
+int suma_pipeline_disable_deskew(suma_pipeline* s);
+int suma_pipeline_set_deskew_motion(suma_pipeline* s, const double motion[16]);
+int suma_pipeline_deskew_motion(const suma_pipeline* s, double motion[16], int32_t* source);
+int suma_localizer_enable_deskew(suma_localizer* l, const suma_deskew_params* dp);
+int suma_localizer_disable_deskew(suma_localizer* l);
+int suma_localizer_set_deskew_motion(suma_localizer* l, const double motion[16]);
+int suma_localizer_deskew_motion(const suma_localizer* l, double motion[16], int32_t* source);
+
 /* ---- per-kernel timing (rv::Stopwatch / SurfelMapping::Stats, SurfelMapping.cpp:183-207):
  *      on = 1: every kernel group is bracketed by HIP events on the ctx stream; on = 2: only the
  *      Gauss-Newton chain (the kernel with the largest share of GPU time), which costs two event

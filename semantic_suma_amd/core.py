@@ -8,7 +8,8 @@ stand for (PRBonn/semantic_suma, src/core):
     Frame2Model      src/core/Frame2Model.h:28-73 / Objective.h:14-82
     LieGaussNewton   src/core/LieGaussNewton.h:25-76         minimize(objective, T0), pose(), history()
     SurfelMap        src/core/SurfelMap.h:36-78              update / render* / *MapFrame / updatePoses / size / draw
-    SurfelMapping    src/core/SurfelMapping.h:47             processScan(scan)
+    SurfelMapping    src/core/SurfelMapping.h:47             processScan(scan); enableDeskew: raw sweeps are motion
+                                                             compensated in front of the preprocessing (no counterpart)
     Localizer        (no counterpart)                        setMap / setPose / processScan / relocalize in a finished map;
                                                              enableEvidence / evidence / prunedMap: which records still hold;
                                                              enableNovelty / novel / updatedMap: what is new
@@ -31,7 +32,7 @@ import numpy as np
 from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX_LIGHTS, SURFEL_DTYPE, DrawParams,
                     IcpStats, LoopParams, LoopStatus, PosegraphParams, PosegraphStats, SemanticKnnParams,
                     SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats, CheckpointInfo,
-                    ChangeCounts, ChangeParams, ChangeRule, EVIDENCE_DTYPE, NovelCounts, NovelFuseParams, NovelParams, NovelStats, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
+                    ChangeCounts, ChangeParams, ChangeRule, DeskewParams, EVIDENCE_DTYPE, NovelCounts, NovelFuseParams, NovelParams, NovelStats, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -309,6 +310,17 @@ def lib():
     L.suma_localizer_novel_device.argtypes = [vp, nfp, vp, vp, u32, nsp]
     L.suma_localizer_novel_marks.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.suma_localizer_clear_novelty.argtypes = [vp]
+    dkp = C.POINTER(DeskewParams)
+    L.suma_deskew_params_default.argtypes = [dkp]
+    L.suma_deskew_params_default.restype = None
+    L.suma_deskew_check.argtypes = [dkp, C.c_int, vp]
+    L.suma_deskew_points.argtypes = [vp, dkp, vp, vp, u32, vp, vp]
+    L.suma_deskew_points_device.argtypes = [vp, dkp, vp, vp, u32, vp, vp]
+    for who in ("pipeline", "localizer"):
+        getattr(L, f"suma_{who}_enable_deskew").argtypes = [vp, dkp]
+        getattr(L, f"suma_{who}_disable_deskew").argtypes = [vp]
+        getattr(L, f"suma_{who}_set_deskew_motion").argtypes = [vp, vp]
+        getattr(L, f"suma_{who}_deskew_motion").argtypes = [vp, vp, C.POINTER(i32)]
     ppp, pmp = C.POINTER(PlaceParams), C.POINTER(PlaceMatch)
     L.suma_place_params_default.argtypes = [ppp]
     L.suma_place_params_default.restype = None
@@ -1134,13 +1146,68 @@ def checkpoint_digest(payload) -> int:
     return lib().suma_checkpoint_digest(payload, len(payload))
 
 
-class SurfelMapping:
+class _DeskewSwitch:
+    """the motion-compensation switch SurfelMapping and Localizer share (suma_pipeline_*deskew* / suma_localizer_*deskew*,
+    csrc/k_deskew.hip): while enabled, processScan* / beginScan* correct the raw sweep in front of K1 with the last
+    increment as the motion over one sweep"""
+    _deskew_prefix = ""
+
+    def _dk(self, name):
+        return getattr(self.L, f"suma_{self._deskew_prefix}_{name}")
+
+    def enableDeskew(self, params: DeskewParams = None):
+        """None = the defaults: azimuth time, counter-clockwise, start_azimuth 0, t_ref 0.5, scale 1"""
+        self.ctx.check(self._dk("enable_deskew")(self.h, None if params is None else C.byref(params)),
+                       f"suma_{self._deskew_prefix}_enable_deskew")
+
+    def disableDeskew(self):
+        self.ctx.check(self._dk("disable_deskew")(self.h), f"suma_{self._deskew_prefix}_disable_deskew")
+
+    def setDeskewMotion(self, motion):
+        """one-shot override of the motion over one sweep for the next scan (an IMU, wheel odometry, the first scans)"""
+        T = _cm(motion, np.float64)
+        self.ctx.check(self._dk("set_deskew_motion")(self.h, _ptr(T)), f"suma_{self._deskew_prefix}_set_deskew_motion")
+
+    def deskewMotion(self):
+        """(motion the last corrected scan used, row-major 4x4; its source: types.DESKEW_MOTION_*)"""
+        T, src = np.zeros((4, 4), dtype=np.float64), C.c_int32(0)
+        self.ctx.check(self._dk("deskew_motion")(self.h, _ptr(T), C.byref(src)), f"suma_{self._deskew_prefix}_deskew_motion")
+        return T.T.copy(), int(src.value)
+
+
+def deskew_points(ctx: "Context", points, motion, params: DeskewParams = None, times=None) -> np.ndarray:
+    """suma_deskew_points: N x 4 points of one raw sweep moved into the sensor frame at ``params.t_ref``; ``motion`` is
+    the sensor's motion over one sweep (row-major 4x4), ``times`` the per-point sweep fractions for the times source"""
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
+    tm = None if times is None else np.ascontiguousarray(times, dtype=np.float32).reshape(-1)
+    if tm is not None and tm.shape[0] != pts.shape[0]:
+        raise ValueError("one time per point is needed")
+    out = np.empty_like(pts)
+    T = _cm(motion, np.float64)
+    ctx.check(ctx.L.suma_deskew_points(ctx.h, None if params is None else C.byref(params), _ptr(pts) if pts.shape[0] else None,
+                                       _ptr(tm), pts.shape[0], _ptr(T), _ptr(out) if pts.shape[0] else None),
+              "suma_deskew_points")
+    return out
+
+
+def deskew_points_device(ctx: "Context", d_points, motion, n: int, d_out=None, params: DeskewParams = None, d_times=None):
+    """suma_deskew_points_device: the same on device addresses or torch tensors, enqueued on the ctx stream; ``d_out``
+    None corrects in place"""
+    T = _cm(motion, np.float64)
+    ctx.check(ctx.L.suma_deskew_points_device(ctx.h, None if params is None else C.byref(params), _dev(d_points),
+                                              _dev(d_times), n, _ptr(T), _dev(d_points if d_out is None else d_out)),
+              "suma_deskew_points_device")
+
+
+class SurfelMapping(_DeskewSwitch):
     """SurfelMapping::processScan (SurfelMapping.cpp:175-210).  processScan* run a scan in one call; beginScan /
     updatePose / updateMap are its phases.  With ``loop_params`` (types.LoopParams) the pipeline closes loops itself, as
     the reference does with close-loops = true: it keeps the pose graph (``posegraph``), every beginScan* first
     integrates a finished optimisation, processScan* run checkLoopClosure between updatePose and updateMap, and hosts
     on the phase calls place ``checkLoopClosure()`` there.  Without it, a host may still script closures by hand
-    (verifyLoopClosure, trackLoopClosure, setPoseOld, integrateLoopClosures)."""
+    (verifyLoopClosure, trackLoopClosure, setPoseOld, integrateLoopClosures).  enableDeskew: the scans are raw sweeps;
+    while it is on, the prefetch / async / scores entries and runScans refuse."""
+    _deskew_prefix = "pipeline"
 
     def __init__(self, params: SumaParams, device: int = 0, loop_params: LoopParams = None):
         self.L = lib()
@@ -1523,13 +1590,14 @@ def pruned_map(records: np.ndarray, evidence: np.ndarray, rule: ChangeRule = Non
     return records[keep], keep
 
 
-class Localizer:
+class Localizer(_DeskewSwitch):
     """Localisation of scans in a finished world map, which is left alone (suma_localizer_*, csrc/k_localize.hip): the
     map is what SurfelMap.export_world / mapio give.  ``setMap`` bins it into submap tiles on the device, ``setPose``
     gives the start pose and gathers the tiles around it (``relocalize`` finds one from a PlaceIndex instead),
     ``processScan`` renders that window from the predicted pose, minimises the scan against it and returns a dict: guess / pose / increment
     (row-major 4x4), stats, valid_ratio, outlier_ratio, tracked, window_rebuilt, origin, n_window.  Nothing is fused, so a
-    run has no length limit."""
+    run has no length limit.  enableDeskew: processScan* take raw sweeps; relocalize does not correct."""
+    _deskew_prefix = "localizer"
 
     def __init__(self, params: SumaParams, loc_params: LocalizerParams = None, device: int = 0):
         self.L = lib()

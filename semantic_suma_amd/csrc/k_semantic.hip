@@ -222,6 +222,7 @@ extern "C" int suma_semantic_unproject(suma_ctx* c, const suma_semantic_params* 
 
 int semantic_scan_input(suma_pipeline* s, uint32_t n, void* producer_event, hipStream_t* st) {
   suma_ctx* c = s->c;
+  SUMA_REFUSE_WHILE_DESKEW(s, "suma_pipeline_*_scan_scores*");
   if (s->phase != 0)
     return fail(c, SUMA_ERR_INVALID, "suma_pipeline_begin_scan: the previous scan has not been closed with suma_pipeline_update_map");
   *st = pipeline_input_stream(s);

@@ -1691,6 +1691,7 @@ extern "C" void suma_pipeline_destroy(suma_pipeline* s) {
   suma_frame_destroy(s->current_frame);
   suma_frame_destroy(s->current_model);
   suma_frame_destroy(s->last_model);
+  deskew_destroy(s); /* its device block goes before the ctx; both streams have drained */
   suma_ctx_destroy(s->c);
   delete s;
 }
@@ -1917,8 +1918,10 @@ int pipeline_begin_scan_impl(suma_pipeline* s, const suma_float4* d_points, cons
    * previous scan's minimisation result is behind it in stream order), K1 has its own z-buffer.  The ctx stream
    * continues behind a gate that waits for the side stream's signal (k_sync.hip). */
   int r;
+  const bool deskew = s->deskew && s->deskew->on; /* raw sweeps: corrected in front of K1, on K1's stream (k_deskew.hip) */
   if (c->side_stream) {
     if (upload_done) HIP_TRY(c, hipStreamWaitEvent(c->side_stream, upload_done, 0));
+    if (deskew && (r = deskew_scan(c, *s->deskew, s->last_increment, c->side_stream, d_points, n, &d_points)) != SUMA_OK) return r;
     c->ls = c->side_stream;
     r = suma_preprocess_device(c, d_points, d_labels, d_probs, n, s->timestamp, s->current_frame);
     c->ls = c->stream;
@@ -1927,6 +1930,7 @@ int pipeline_begin_scan_impl(suma_pipeline* s, const suma_float4* d_points, cons
     if (r) return r;
   } else {
     if (upload_done) HIP_TRY(c, hipStreamWaitEvent(c->stream, upload_done, 0));
+    if (deskew && (r = deskew_scan(c, *s->deskew, s->last_increment, c->stream, d_points, n, &d_points)) != SUMA_OK) return r;
     r = suma_preprocess_device(c, d_points, d_labels, d_probs, n, s->timestamp, s->current_frame);
     if (r) return r;
   }
@@ -2015,6 +2019,7 @@ extern "C" int suma_pipeline_reset(suma_pipeline* s) {
   mat4_eye(s->pose_new);
   mat4_eye(s->last_increment);
   mat4_eye(s->last_pose_old);
+  if (s->deskew) s->deskew->have_override = false; /* the switch stays; a motion meant for a scan of the old run does not */
   c->obj_set = false;
   c->k8_fused_frame = nullptr;
   return suma_synchronize(c);

@@ -352,6 +352,7 @@ uint32_t ingest_pending(suma_ctx* c) {
 extern "C" int suma_pipeline_prefetch_scan(suma_pipeline* s, const suma_float4* points, const float* labels,
                                            const float* probs, uint32_t n) {
   if (!s || (n > 0 && !points)) return SUMA_ERR_INVALID;
+  SUMA_REFUSE_WHILE_DESKEW(s, "suma_pipeline_prefetch_scan");
   Ingest* g = nullptr;
   int r = ingest_get(s->c, &g);
   if (r) return r;
@@ -373,6 +374,7 @@ extern "C" int suma_pipeline_prefetch_scan(suma_pipeline* s, const suma_float4* 
 
 /* the oldest staged scan: begin (phases_only) or the whole scan */
 static int run_prefetched(suma_pipeline* s, int32_t fixed_iterations, bool begin_only) {
+  SUMA_REFUSE_WHILE_DESKEW(s, "suma_pipeline_process_prefetched");
   if (!s || !s->c->ingest) return SUMA_ERR_INVALID;
   Ingest* g = s->c->ingest;
   suma_ctx* c = s->c;
@@ -422,6 +424,7 @@ extern "C" int suma_pipeline_begin_prefetched(suma_pipeline* s) { return run_pre
 extern "C" int suma_pipeline_process_scan_async(suma_pipeline* s, const suma_float4* points, const float* labels,
                                                 const float* probs, uint32_t n, int32_t fixed_iterations) {
   if (!s || (n > 0 && !points)) return SUMA_ERR_INVALID;
+  SUMA_REFUSE_WHILE_DESKEW(s, "suma_pipeline_process_scan_async");
   bool staged = false;
   if (s->c->ingest) {
     Ingest* g = s->c->ingest;

@@ -374,6 +374,7 @@ struct suma_pipeline {
   uint32_t stats_slot;
   suma_icp_stats stats_mst;
   struct LoopState* loop; /* suma_pipeline_enable_loop_closing; NULL: off, and nothing of the loop closing runs */
+  struct Deskew* deskew;  /* suma_pipeline_enable_deskew (suma_deskew.hip); NULL until first enabled, and nothing of it runs while off */
 };
 
 int pipeline_process_scan_impl(suma_pipeline* s, const suma_float4* d_points, const float* d_labels, const float* d_probs,
@@ -598,6 +599,45 @@ int novel_collect(suma_ctx* c, Novel& nv, const LocMap& m, uint32_t n_spans, uin
  * n_voxels, n_out */
 int novel_fuse(suma_ctx* c, Novel& nv, uint32_t n, const suma_novel_fuse_params& fp, suma_world_surfel* d_out,
                uint32_t* d_views, uint32_t capacity, uint32_t counters_out[3]);
+
+/* k_deskew.hip (the specification is there): what kd_deskew receives by value -- the twist of one sweep, made once on the
+ * host in fp64 (deskew_twist) and rounded to fp32 */
+#define SUMA_DESKEW_SMALL_THETA 1e-6
+struct DeskewArgs {
+  float v[3], a[3], b[3], c[3]; /* scale * v0, the unit axis, a x v, a x (a x v) */
+  float theta, inv_theta;       /* both 0 for a pure translation */
+  float t_ref, start_azimuth;
+  int32_t clockwise, use_times;
+};
+bool deskew_is_identity(const double motion[16]);
+void deskew_twist(const suma_deskew_params& dp, const double motion[16], DeskewArgs* out);
+hipError_t launch_kd_deskew(hipStream_t st, const float4* in, const float* times, uint32_t n, const DeskewArgs& a,
+                            float4* out);
+/* suma_deskew.hip: the correction a pipeline or a localiser applies to its scans */
+struct Deskew {
+  bool on = false;
+  suma_deskew_params dp;
+  bool have_override = false; /* suma_*_set_deskew_motion: one shot, for the next scan */
+  double override_motion[16];
+  double last_motion[16];     /* what the last scan used */
+  int32_t last_source = 0;    /* SUMA_DESKEW_MOTION_* */
+  DevBuf<float4> points;      /* the corrected scan: the caller's buffer is never written */
+};
+/* sets c->err; for_scans: the entries that take no times (pipeline, localiser) refuse the times source */
+int deskew_params_check(suma_ctx* c, const suma_deskew_params* dp, bool for_scans, const char* who);
+/* the motion of the next scan (the override once, else `increment`), noted in dk as the last one used; then n points at
+ * d_in corrected into dk.points on stream st, *d_out = the points K1 reads: d_in itself for the identity motion (nothing is
+ * launched).  Growing dk.points waits for both streams of c -- only when a larger scan than any before arrives */
+int deskew_scan(suma_ctx* c, Deskew& dk, const double increment[16], hipStream_t st, const suma_float4* d_in, uint32_t n,
+                const suma_float4** d_out);
+void deskew_destroy(suma_pipeline* s);
+/* the entries that hand a scan over before the previous pose exists have no motion to use */
+#define SUMA_REFUSE_WHILE_DESKEW(s, who)                                                                        \
+  do {                                                                                                           \
+    if ((s) && (s)->deskew && (s)->deskew->on)                                                                   \
+      return fail((s)->c, SUMA_ERR_INVALID, who ": not while motion compensation is enabled (the scan is handed " \
+                                                 "over before the previous pose exists; suma_pipeline_disable_deskew)"); \
+  } while (0)
 
 /* k_place.hip (the specification is there): what kp_describe reads of suma_place_params, with the two quotients made
  * once on the host and the label mask as bits */

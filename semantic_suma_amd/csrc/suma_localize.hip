@@ -39,6 +39,11 @@ struct suma_localizer {
   Novel nv;
   uint32_t scan_count = 0;     /* process_scan calls since the last set_map */
   int32_t last_collected = 0;
+  /* motion compensation (k_deskew.hip): the correction of process_scan's points, and the staging of a host scan that is
+   * corrected (an uncorrected one goes through suma_preprocess's own staging) */
+  Deskew dk;
+  DevBuf<float4> dk_points;
+  DevBuf<float> dk_labels, dk_probs;
 };
 
 namespace {
@@ -167,6 +172,7 @@ extern "C" void suma_localizer_destroy(suma_localizer* l) {
   l->map = LocMap(); /* device blocks go before the ctx */
   l->ev_totals.reset(), l->ev_totals_h.reset(), l->ev_source.reset();
   l->nv = Novel();
+  l->dk.points.reset(), l->dk_points.reset(), l->dk_labels.reset(), l->dk_probs.reset();
   suma_frame_destroy(l->frame);
   suma_ctx_destroy(l->c);
   delete l;
@@ -227,6 +233,29 @@ extern "C" int suma_localizer_set_pose(suma_localizer* l, const double T[16]) {
   return SUMA_OK;
 }
 
+/* step 3 with motion compensation on: the points are corrected with the increment of the previous scan's step 7 (or the
+ * one-shot override) in front of K1, all on the ctx stream; a host scan is staged in the localiser's own blocks first */
+static int preprocess_deskewed(suma_localizer* l, const suma_float4* points, const float* labels, const float* probs,
+                               uint32_t n, bool on_device) {
+  suma_ctx* c = l->c;
+  if (!on_device && n) {
+    const size_t cap = (size_t)n + n / 4 + 1024;
+    if (grow(c, l->dk_points, n, {c->stream}, cap) < 0 || (labels && grow(c, l->dk_labels, n, {c->stream}, cap) < 0) ||
+        (probs && grow(c, l->dk_probs, n, {c->stream}, cap) < 0))
+      return SUMA_ERR_HIP;
+    HIP_TRY(c, hipMemcpyAsync(l->dk_points, points, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    if (labels) HIP_TRY(c, hipMemcpyAsync(l->dk_labels, labels, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (probs) HIP_TRY(c, hipMemcpyAsync(l->dk_probs, probs, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    points = (const suma_float4*)l->dk_points.p;
+    if (labels) labels = l->dk_labels;
+    if (probs) probs = l->dk_probs;
+  }
+  if (c->gate_pending) HIP_TRY(c, flush_gate(c)); /* an earlier suma_preprocess on the side stream comes first */
+  int r = deskew_scan(c, l->dk, l->increment, c->stream, points, n, &points);
+  if (r) return r;
+  return suma_preprocess_device(c, points, labels, probs, n, c->timestamp, l->frame);
+}
+
 /* frame_ready: a candidate of a relocalisation -- K1-K3 are made, and a hypothesis observes nothing */
 static int process_scan(suma_localizer* l, const suma_float4* points, const float* labels, const float* probs, uint32_t n,
                         int32_t fixed_iterations, suma_localizer_result* res, bool on_device, bool frame_ready = false) {
@@ -269,9 +298,10 @@ static int process_scan(suma_localizer* l, const suma_float4* points, const floa
   memset(&st, 0, sizeof(st));
   if (l->n_window) {
     /* 3. K1-K3 at T_loc (a relocalisation has made them once for all its candidates) */
-    int r = frame_ready ? SUMA_OK
-            : on_device ? suma_preprocess_device(c, points, labels, probs, n, c->timestamp, l->frame)
-                        : suma_preprocess(c, points, labels, probs, n, c->timestamp, l->frame);
+    int r = frame_ready  ? SUMA_OK
+            : l->dk.on   ? preprocess_deskewed(l, points, labels, probs, n, on_device)
+            : on_device  ? suma_preprocess_device(c, points, labels, probs, n, c->timestamp, l->frame)
+                         : suma_preprocess(c, points, labels, probs, n, c->timestamp, l->frame);
     if (r) return r;
     /* 4. the model: the window seen from the guess */
     r = suma_map_render_inactive(c, gf, l->lp.conf_threshold);
@@ -350,6 +380,41 @@ extern "C" int suma_localizer_process_scan_device(suma_localizer* l, const suma_
                                                   const float* d_probs, uint32_t n, int32_t fixed_iterations,
                                                   suma_localizer_result* result) {
   return process_scan(l, d_points, d_labels, d_probs, n, fixed_iterations, result, true);
+}
+
+/* ---- motion compensation (k_deskew.hip; the pipeline's entries are in suma_deskew.hip) ---- */
+extern "C" int suma_localizer_enable_deskew(suma_localizer* l, const suma_deskew_params* dp) {
+  if (!l) return SUMA_ERR_INVALID;
+  int r = deskew_params_check(l->c, dp, true, "suma_localizer_enable_deskew");
+  if (r) return r;
+  suma_deskew_params_default(&l->dk.dp);
+  if (dp) l->dk.dp = *dp;
+  if (!l->dk.on) mat4_eye(l->dk.last_motion), l->dk.last_source = SUMA_DESKEW_MOTION_NONE;
+  l->dk.on = true;
+  return SUMA_OK;
+}
+extern "C" int suma_localizer_disable_deskew(suma_localizer* l) {
+  if (!l) return SUMA_ERR_INVALID;
+  l->dk.on = false;
+  l->dk.have_override = false;
+  return SUMA_OK;
+}
+extern "C" int suma_localizer_set_deskew_motion(suma_localizer* l, const double motion[16]) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (!l->dk.on) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_deskew_motion: motion compensation is not enabled");
+  if (!motion) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_deskew_motion: NULL motion");
+  if (!finite16(motion)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_deskew_motion: non-finite motion");
+  memcpy(l->dk.override_motion, motion, 16 * sizeof(double));
+  l->dk.have_override = true;
+  return SUMA_OK;
+}
+extern "C" int suma_localizer_deskew_motion(const suma_localizer* l, double motion[16], int32_t* source) {
+  if (!l || !motion) return SUMA_ERR_INVALID;
+  if (l->dk.last_source == SUMA_DESKEW_MOTION_NONE) mat4_eye(motion);
+  else memcpy(motion, l->dk.last_motion, 16 * sizeof(double));
+  if (source) *source = l->dk.last_source;
+  return SUMA_OK;
 }
 
 /* ---- global relocalisation (include/suma_hip.h states the steps) ---- */

@@ -63,6 +63,7 @@ static void run_one_sequence(suma_pipeline* s, const suma_sequence_job& job, int
 extern "C" int suma_pipeline_run_scans(suma_pipeline* s, const suma_sequence_job* job, int32_t fixed_iterations,
                                        uint32_t* scans_done, double* seconds_per_call) {
   if (!s || !job || (!job->scans && job->n_scans)) return SUMA_ERR_INVALID;
+  SUMA_REFUSE_WHILE_DESKEW(s, "suma_pipeline_run_scans");
   int r = SUMA_OK;
   uint32_t k = 0;
   double t_prev = seconds_per_call ? now_s() : 0.0;

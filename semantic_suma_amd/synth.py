@@ -103,12 +103,21 @@ def _boxes(k: int):
 
 
 def generate_scan(k: int, n_azimuth: int = 2000, height: int = 64, noise: float = 0.02, seed: int = 1337,
-                  semantics: bool = True, max_range: float = 100.0, pose: np.ndarray | None = None, without=()):
+                  semantics: bool = True, max_range: float = 100.0, pose: np.ndarray | None = None, without=(),
+                  column_poses: np.ndarray | None = None):
     """Ray-cast scan ``k``.  Returns (points[N,4] f32, labels[N] f32, probs[N] f32, pose[4,4] f64).
     ``without``: indices into the box list of ``_boxes(k)`` (the 23 cubes, then the buildings) that the ray caster skips
-    -- the same world with those objects taken away (the boxes draw no random numbers, so the default changes nothing)."""
+    -- the same world with those objects taken away (the boxes draw no random numbers, so the default changes nothing).
+    ``column_poses`` [n_azimuth, 4, 4]: a RAW sweep of a moving sensor -- azimuth column i is cast from its own pose
+    and its points are in that pose's frame, as a rotating lidar delivers them (the motion compensation of
+    csrc/k_deskew.hip undoes it).  A callable is given the sweep fraction of every column, its (jittered) azimuth's
+    share of the turn in [0, 1) -- a counter-clockwise sensor whose sweep starts at azimuth 0 -- and returns the poses.  ``pose`` stays the pose the scan is attributed to, and draws what it always draws:
+    with ``column_poses`` absent every returned byte is what it was."""
     without = frozenset(int(b) for b in without)
     T = trajectory_pose(k) if pose is None else np.asarray(pose, dtype=np.float64)
+    if column_poses is not None:
+        return _generate_raw_sweep(k, n_azimuth, height, noise, seed, semantics, max_range, T, without,
+                                   column_poses)
     rng = np.random.default_rng(seed + 7919 * k)
     el = beam_elevations(height)
     az = (np.arange(n_azimuth) + rng.uniform(-0.3, 0.3, n_azimuth)) * (2 * math.pi / n_azimuth)
@@ -157,6 +166,93 @@ def generate_scan(k: int, n_azimuth: int = 2000, height: int = 64, noise: float 
             c, s = math.cos(yaw[b]), math.sin(yaw[b])
             Rb = np.array([[c, s, 0], [-s, c, 0], [0, 0, 1]])        # world -> box
             ob = Rb @ (o - cz[b])
+            db = d[idx] @ Rb.T
+            inv = 1.0 / db
+            t1 = (-half[b] - ob) * inv
+            t2 = (half[b] - ob) * inv
+            tmin = np.nanmax(np.minimum(t1, t2), axis=1)
+            tmax = np.nanmin(np.maximum(t1, t2), axis=1)
+            ok = (tmax >= tmin) & (tmin > 0)
+            t = np.where(ok, tmin, np.inf)
+            hit = t < t_best[idx]
+            t_best[idx] = np.where(hit, t, t_best[idx])
+            label[idx] = np.where(hit, blabel[b], label[idx])
+
+    keep = np.isfinite(t_best) & (t_best < max_range) & (t_best > 0.5)
+    r = t_best[keep] * (1.0 + (noise * rng.standard_normal(keep.sum())) / np.maximum(t_best[keep], 1.0))
+    pts = np.ones((r.shape[0], 4), dtype=np.float32)
+    pts[:, :3] = (d_local[keep] * r[:, None]).astype(np.float32)
+    if semantics:
+        labels = label[keep].astype(np.float32)
+        probs = np.random.default_rng(42 + k).uniform(0.6, 1.0, r.shape[0]).astype(np.float32)
+    else:
+        labels = np.zeros(r.shape[0], dtype=np.float32)
+        probs = np.zeros(r.shape[0], dtype=np.float32)
+    return pts, labels, probs, T
+
+
+def _generate_raw_sweep(k, n_azimuth, height, noise, seed, semantics, max_range, T, without, Tc):
+    """generate_scan with one pose per azimuth column: the same world, beams, random draws and output order; the rays of
+    column i start at Tc[i]'s origin with its rotation.  The column culling of a box is widened by what the sensor moves
+    and turns within the sweep."""
+    rng = np.random.default_rng(seed + 7919 * k)
+    el = beam_elevations(height)
+    az = (np.arange(n_azimuth) + rng.uniform(-0.3, 0.3, n_azimuth)) * (2 * math.pi / n_azimuth)
+    if callable(Tc):
+        Tc = Tc((az / (2 * math.pi)) % 1.0)
+    Tc = np.asarray(Tc, dtype=np.float64).reshape(n_azimuth, 4, 4)
+    A, E = np.meshgrid(az, el, indexing="ij")
+    A, E = A.ravel(), E.ravel()
+    d_local = np.stack([np.cos(A) * np.cos(E), np.sin(A) * np.cos(E), np.sin(E)], axis=1)
+    col = np.repeat(np.arange(n_azimuth), height)
+    d = np.einsum("nij,nj->ni", Tc[col, :3, :3], d_local)
+    o = Tc[col, :3, 3]
+    n_rays = d.shape[0]
+    t_best = np.full(n_rays, np.inf)
+    label = np.zeros(n_rays, dtype=np.float32)
+    Tinv = np.linalg.inv(T)
+    # how far the column poses stray from the scan's pose: metres, and radians of heading
+    moved = float(np.max(np.linalg.norm(Tc[:, :3, 3] - T[:3, 3], axis=1)))
+    rel_rot = np.einsum("ij,njk->nik", Tinv[:3, :3], Tc[:, :3, :3])
+    turned = float(np.max(np.arccos(np.clip(0.5 * (np.trace(rel_rot, axis1=1, axis2=2) - 1.0), -1.0, 1.0))))
+
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(d[:, 2] < 0, -o[:, 2] / d[:, 2], np.inf)
+        hit = t < t_best
+        t_best = np.where(hit, t, t_best)
+        label = np.where(hit, LABEL_ROAD, label)
+        for wy in (WALL_Y, -WALL_Y):
+            t = (wy - o[:, 1]) / d[:, 1]
+            z = o[:, 2] + t * d[:, 2]
+            ok = (t > 0) & (z >= 0) & (z <= 6.0)
+            t = np.where(ok, t, np.inf)
+            hit = t < t_best
+            t_best = np.where(hit, t, t_best)
+            label = np.where(hit, LABEL_BUILDING, label)
+        cz, half, yaw, blabel = _boxes(k)
+        for b in range(cz.shape[0]):
+            if b in without:
+                continue
+            rel = Tinv[:3, :3] @ (cz[b] - T[:3, 3])
+            dist = math.hypot(rel[0], rel[1])
+            rad = float(np.linalg.norm(half[b, :2])) + moved
+            if dist - rad > max_range:
+                continue
+            if dist <= rad * 1.05:
+                cols = np.arange(n_azimuth)
+            else:
+                bearing = math.atan2(rel[1], rel[0]) % (2 * math.pi)
+                hw = math.asin(min(1.0, rad / dist)) + turned + 2.0 * (2 * math.pi / n_azimuth)
+                if hw >= math.pi:
+                    cols = np.arange(n_azimuth)
+                else:
+                    i0 = int(math.floor((bearing - hw) / (2 * math.pi) * n_azimuth))
+                    i1 = int(math.ceil((bearing + hw) / (2 * math.pi) * n_azimuth))
+                    cols = np.unique(np.arange(i0, i1 + 1) % n_azimuth)
+            idx = (cols[:, None] * height + np.arange(height)[None, :]).ravel()
+            c, s = math.cos(yaw[b]), math.sin(yaw[b])
+            Rb = np.array([[c, s, 0], [-s, c, 0], [0, 0, 1]])
+            ob = (o[idx] - cz[b]) @ Rb.T
             db = d[idx] @ Rb.T
             inv = 1.0 / db
             t1 = (-half[b] - ob) * inv

@@ -221,6 +221,25 @@ class NovelParams(C.Structure):
         return p
 
 
+DESKEW_TIME_AZIMUTH, DESKEW_TIME_TIMES = 0, 1
+DESKEW_MOTION_NONE, DESKEW_MOTION_INCREMENT, DESKEW_MOTION_OVERRIDE = 0, 1, 2
+
+
+class DeskewParams(C.Structure):
+    """``struct suma_deskew_params``: how the motion compensation of raw sweeps (csrc/k_deskew.hip) times a point and
+    which instant of the sweep it refers to; ``DeskewParams.defaults()`` = suma_deskew_params_default"""
+    _fields_ = [("time_source", i32), ("clockwise", i32), ("start_azimuth", f32), ("t_ref", f32), ("scale", f32)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "DeskewParams":
+        p = cls(time_source=DESKEW_TIME_AZIMUTH, clockwise=0, start_azimuth=0.0, t_ref=0.5, scale=1.0)
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        return p
+
+
 class NovelFuseParams(C.Structure):
     """``struct suma_novel_fuse_params``; ``NovelFuseParams.defaults(params)`` = suma_novel_fuse_params_default: the
     confidence new records get is confidence_threshold + 1, so that the localiser renders them"""

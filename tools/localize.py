@@ -11,7 +11,8 @@ every scan's totals and, with --prune-out, writes the map without the records th
 objects out of the synthetic world the localised scans see).  --novel collects the surfaces no record of the map explains
 (csrc/k_novel.hip), prints every scan's counts and, with --update-out, writes the updated map: the records the rule keeps
 (all of them without --evidence) followed by the fused new ones (--map-without takes objects out of the world the mapping
-run sees).  With --relocalize the first scan goes through Localizer.relocalize against a place index (core.PlaceIndex) -- the mapping
+run sees).  --deskew motion compensates the localised scans with the localiser's last increment (csrc/k_deskew.hip), for
+sensors that deliver raw sweeps.  With --relocalize the first scan goes through Localizer.relocalize against a place index (core.PlaceIndex) -- the mapping
 run's own scans, or with --map the file tools/export_map.py --places wrote (--places).  Needs a GPU.
     python tools/localize.py [--map-scans 80] [--first 10] [--scans 60] [--voxel 0.1] [--width 2048] [--kitti sequences/08]
     python tools/localize.py --map map.ply --start 12.0 0.5 0.0 3.0 --first 11 --scans 20
@@ -20,6 +21,7 @@ run's own scans, or with --map the file tools/export_map.py --places wrote (--pl
     python tools/localize.py --map map.ply --places map.places.npz --relocalize --first 11 --scans 20
     python tools/localize.py --evidence --without 2 41 --prune-out pruned.ply   # cube 2 and a building are gone
     python tools/localize.py --map-without 2 41 --novel --update-out new.ply    # cube 2 and a building have arrived
+    python tools/localize.py --kitti raw/sequence --deskew   # raw (uncompensated) sweeps: corrected in front of K1
 """
 import argparse
 import ctypes as C
@@ -162,6 +164,9 @@ def main():
     ap.add_argument("--prune-out", default=None, metavar="FILE.ply", help="with --evidence: write the map the default rule keeps")
     ap.add_argument("--without", type=int, nargs="*", default=[], metavar="BOX",
                     help="synthetic scans: boxes of synth._boxes the localised scans do not see (0-22 cubes, 23.. buildings)")
+    ap.add_argument("--deskew", action="store_true",
+                    help="the localised scans are raw sweeps: motion compensate them with the last increment (azimuth time, "
+                         "counter-clockwise, t_ref 0.5)")
     ap.add_argument("--novel", action="store_true", help="collect the surfaces no map record explains and print every scan's counts")
     ap.add_argument("--update-out", default=None, metavar="FILE.ply",
                     help="with --novel: write the updated map (what the rule keeps, then the fused new records)")
@@ -228,6 +233,9 @@ def main():
         loc.enableEvidence()
     if args.novel:
         loc.enableNovelty()
+    if args.deskew:
+        loc.enableDeskew()
+        res["deskew"] = True
     t = time.perf_counter()
     dropped = loc.setMap(records)
     res.update(map_records=int(len(records)), dropped=dropped, set_map_ms=round(1e3 * (time.perf_counter() - t), 3))
