@@ -6,7 +6,7 @@
  * in the reference does this: its stability log-odds (K9) exist inside a mapping run only.
  *
  * Kernels (VGPRs: tools/isa_stats.py k_change.hip; none uses scratch):
- *   kc_observe  lane per window record, blocks of 256: finds its span by binary search (as kl_gather), loads the record's
+ *   kc_observe  lane per window record, blocks of 256: finds its span by binary search (loc_window_record), loads the record's
  *               three 16-byte pieces and its 16-byte evidence word together, then -- the one dependent round trip -- the
  *               three texels of the frame the record projects to (K9's header, k_update.hip: the chain of dependent loads
  *               is the cost, so everything that does not depend on the projection is in flight before it).  The record
@@ -46,6 +46,7 @@
  *   misses >= min_misses && (float)misses > miss_ratio * (float)hits.  occluded and label_changes do not enter it.
  */
 #include "suma_internal.h"
+#include "group_by_key.h"
 
 #define CHG_THREADS 256
 enum { CHG_WINDOW = 0, CHG_UNSEEN, CHG_NO_RETURN, CHG_OCCLUDED, CHG_MISSES, CHG_GRAZING, CHG_HITS, CHG_NEAR, CHG_LABEL, CHG_TOTALS };
@@ -69,13 +70,7 @@ __global__ void __launch_bounds__(CHG_THREADS) kc_observe(ChangeArgs a) {
   __syncthreads();
   const uint32_t o = blockIdx.x * CHG_THREADS + threadIdx.x;
   if (o < a.total) {
-    uint32_t lo = 0, hi = a.n_spans; /* the last span that starts at or before o (no span is empty) */
-    while (hi - lo > 1) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (a.spans[mid].dst <= o) lo = mid; else hi = mid;
-    }
-    const LocSpan sp = a.spans[lo];
-    const size_t k = (size_t)sp.src + (o - sp.dst);
+    const size_t k = loc_window_record(a.spans, a.n_spans, o);
     const float4* src = a.sorted + 3 * k;
     const float4 s0 = src[0], s1 = src[1], s2 = src[2];
     uint4 ev = a.evidence[k];

@@ -55,20 +55,11 @@
  * word saturates near 88 / us) against the hundreds of microseconds a large section streams for.
  */
 #include "suma_internal.h"
+#include "group_by_key.h"
 
 #define KC_THREADS 256
 #define KC_ITEMS 8
 #define KC_GOLDEN 0x9E3779B97F4A7C15ull
-
-/* the last span that starts at or before piece q (empty spans share their start) */
-__device__ __forceinline__ WorldSpan kc_find(const WorldSpan* __restrict__ spans, uint32_t n_spans, uint32_t q) {
-  uint32_t lo = 0, hi = n_spans;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (spans[mid].start <= q) lo = mid; else hi = mid;
-  }
-  return spans[lo];
-}
 
 /* spans == nullptr: one contiguous source at `single` */
 template <bool STORE>
@@ -89,7 +80,7 @@ __device__ __forceinline__ void kc_stream(const WorldSpan* __restrict__ spans, u
       const uint64_t q = chunk + (uint64_t)j * KC_THREADS + threadIdx.x;
       v[j] = make_uint4(0u, 0u, 0u, 0u);
       if (q < n_quads) {
-        if (!((uint32_t)q >= sp.start && (uint32_t)q - sp.start < sp.count)) sp = kc_find(spans, n_spans, (uint32_t)q);
+        if (!((uint32_t)q >= sp.start && (uint32_t)q - sp.start < sp.count)) sp = world_span_find(spans, n_spans, (uint32_t)q);
         v[j] = reinterpret_cast<const uint4*>(sp.base)[(uint32_t)q - sp.start];
       }
     }

@@ -7,13 +7,12 @@
  *
  * Kernels (VGPRs: tools/isa_stats.py k_localize.hip; none uses scratch):
  *   kl_keys     lane per record: tile key and source index; counts the dropped records.
- *   kl_heads    lane per sorted position: 1 where a tile's run begins.
  *   kl_dir      lane per sorted position: the lane at the head of a run writes the tile's key and start.
  *   kl_counts   lane per tile: count = the next tile's start (or the number of kept records) - start.
  *   kl_permute  lane per sorted position: the record moves to its sorted place (16-byte loads and stores).
- *   kl_gather   lane per window record: finds its span by binary search, converts 48 -> 64 bytes (16-byte loads and
- *               stores); lane 0 sets DevState.n_surfels.
- *   between them rocPRIM's radix_sort_pairs and exclusive_scan, as plain library calls (the precedent is k_world.hip).
+ *   kl_gather   lane per window record: finds its span by binary search (loc_window_record, group_by_key.h), converts
+ *               48 -> 64 bytes (16-byte loads and stores); lane 0 sets DevState.n_surfels.
+ *   between kl_keys and kl_dir the sort, the run heads and the scan of k_group.hip.
  *
  * SPECIFICATION (fp32, every operation as written, no contraction: -ffp-contract=off; `/` correctly rounded;
  * tests/localize_shim.c restates it on the host, byte for byte).  SOURCE INDEX = position in the caller's array.
@@ -46,9 +45,8 @@
 #include <cmath>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "suma_internal.h"
+#include "group_by_key.h"
 
 #define LOC_THREADS 256
 #define LOC_GRID 1048576.0f /* 2^20 */
@@ -93,14 +91,6 @@ __global__ void __launch_bounds__(LOC_THREADS)
 }
 
 __global__ void __launch_bounds__(LOC_THREADS)
-    kl_heads(uint32_t n, const unsigned long long* __restrict__ keys, uint32_t* __restrict__ flag) {
-  const uint32_t k = blockIdx.x * LOC_THREADS + threadIdx.x;
-  if (k >= n) return;
-  const unsigned long long key = keys[k];
-  flag[k] = (key != LOC_NO_KEY && (k == 0 || keys[k - 1] != key)) ? 1u : 0u;
-}
-
-__global__ void __launch_bounds__(LOC_THREADS)
     kl_dir(uint32_t n, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ flag,
            const uint32_t* __restrict__ pos, LocTile* __restrict__ dir, uint32_t n_tiles) {
   const uint32_t k = blockIdx.x * LOC_THREADS + threadIdx.x;
@@ -137,13 +127,7 @@ __global__ void __launch_bounds__(LOC_THREADS)
   const uint32_t o = blockIdx.x * LOC_THREADS + threadIdx.x;
   if (o == 0) *n_surfels = total;
   if (o >= total) return;
-  uint32_t lo = 0, hi = n_spans; /* the last span that starts at or before o (no span is empty) */
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (spans[mid].dst <= o) lo = mid; else hi = mid;
-  }
-  const LocSpan sp = spans[lo];
-  const float4* src = sorted + 3 * (size_t)(sp.src + (o - sp.dst));
+  const float4* src = sorted + 3 * loc_window_record(spans, n_spans, o);
   const float4 s0 = src[0], s1 = src[1], s2 = src[2];
   const float L = (float)__float_as_uint(s2.x) / 255.0f;
   float4* dst = out + 4 * (size_t)o; /* 64-byte records */
@@ -179,11 +163,8 @@ int localize_bin(suma_ctx* c, const suma_world_surfel* d_records, uint32_t n, Lo
   uint32_t *idxA = reinterpret_cast<uint32_t*>(keyB + n), *idxB = idxA + n, *flag = idxB + n, *pos = flag + n;
   rocprim::double_buffer<unsigned long long> key(keyA, keyB);
   rocprim::double_buffer<uint32_t> idx(idxA, idxB);
-  size_t bytes = 0, need = 16;
-  HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, bytes, key, idx, (size_t)n, 0u, LOC_KEY_BITS, st));
-  need = bytes > need ? bytes : need;
-  HIP_TRY(c, rocprim::exclusive_scan(nullptr, bytes, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
-  need = bytes > need ? bytes : need;
+  size_t need = 0;
+  HIP_TRY(c, group_tmp_bytes(n, true, st, &need));
   HIP_TRY(c, tmp.alloc(need));
 
   uint32_t h_counters[LOC_COUNTERS] = {0, 0}, last[2] = {0, 0};
@@ -191,11 +172,8 @@ int localize_bin(suma_ctx* c, const suma_world_surfel* d_records, uint32_t n, Lo
     ProfScope ps(c, "loc_bin", 48.0 * n);
     HIP_TRY(c, hipMemsetAsync(counters, 0, LOC_COUNTERS * sizeof(uint32_t), st));
     kl_keys<<<blocks, LOC_THREADS, 0, st>>>(rec, n, c->p.submap_extent, keyA, idxA, counters);
-    bytes = tmp.cap;
-    HIP_TRY(c, rocprim::radix_sort_pairs(tmp.p, bytes, key, idx, (size_t)n, 0u, LOC_KEY_BITS, st));
-    kl_heads<<<blocks, LOC_THREADS, 0, st>>>(n, key.current(), flag);
-    bytes = tmp.cap;
-    HIP_TRY(c, rocprim::exclusive_scan(tmp.p, bytes, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+    HIP_TRY(c, group_sort(tmp.p, tmp.cap, key, idx, n, LOC_KEY_BITS, st));
+    HIP_TRY(c, group_heads(tmp.p, tmp.cap, key.current(), LOC_NO_KEY, flag, pos, n, st));
     HIP_TRY(c, hipGetLastError());
   }
   HIP_TRY(c, hipMemcpyAsync(h_counters, counters, sizeof(h_counters), hipMemcpyDeviceToHost, st));

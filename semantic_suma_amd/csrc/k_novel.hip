@@ -6,7 +6,7 @@
  * (DESIGN.md 12): the candidates are a buffer beside it.  Nothing in the reference does this.
  *
  * Kernels (VGPRs by tools/isa_stats.py k_novel.hip; none spills or uses scratch):
- *   kn_mark     13 VGPRs  lane per window record, blocks of 256: span by binary search (as kc_observe), the record's
+ *   kn_mark     13 VGPRs  lane per window record, blocks of 256: span by binary search (loc_window_record), the record's
  *               position (16 bytes; the normal and the label are not needed), then -- the one dependent round trip -- the
  *               vertex texel it projects to; the classification is written without branches, the mark is a plain byte
  *               store (all writers store 1).
@@ -20,12 +20,11 @@
  *               (P is 131 072 at 64 x 2048: launch count matters more than bandwidth): a collection is one memset and
  *               three launches.
  *   kn_key      22 VGPRs  fusion, lane per candidate: voxel key, vote label, timestamp, index.
- *   kn_gather    4 VGPRs  fusion: the keys in the order a sort left the indices in.
  *   kn_heads    14 VGPRs  fusion, lane per sorted position: the lane at the head of a voxel's run walks it in
  *               (key, timestamp) order and counts the distinct timestamps.
  *   kn_reduce   32 VGPRs  fusion, lane per sorted position: the head of a kept run walks it in (key, label, index) order
  *               and writes the voxel's record.
- *   between them rocPRIM's radix_sort_pairs and exclusive_scan as plain library calls (k_world.hip is the precedent).
+ *   between them the sorts, the key gather and the scan of k_group.hip.
  *
  * SPECIFICATION (fp32, every operation as written, no contraction: -ffp-contract=off; the helpers of dev_math.h; every
  * comparison is written so that a NaN collects nothing; tests/novel_shim.c restates it on the host, byte for byte).
@@ -57,13 +56,13 @@
  *      index ty * W + tx.  The buffer holds max_candidates records: what does not fit is dropped from the end of the
  *      collection and added to n_overflow; stored counts what was written.  The running count lives on the device.
  *   5. FUSION, on request (suma_novel_fuse_params: voxel_size 0.2 m, min_views 2, confidence), over candidates 0 .. n - 1
- *      in creation order.  key = k_world.hip's step 4 on the candidate's position: f_a = floorf(p_a / voxel_size), a
+ *      in creation order.  key = voxel_key (group_by_key.h) of the candidate's position: f_a = floorf(p_a / voxel_size), a
  *      candidate with any |f_a| >= 2^20 (NaN and infinite quotients included) is DROPPED (n_dropped),
  *      key = (ix + 2^20) << 42 | (iy + 2^20) << 21 | (iz + 2^20).  Per distinct key, in ascending key order:
  *        views = the number of distinct timestamps among the members; the voxel is KEPT iff views >= min_views;
  *        representative = the member with the smallest radius (a NaN radius counts as +infinity), on a tie the smallest
  *          candidate index; x, y, z, radius, nx, ny, nz are the representative's; confidence = the parameter;
- *        vote (k_world.hip's): a member votes for L = its label if < 260, else 0, with the weight
+ *        vote (vote_weight and LabelVote, group_by_key.h): a member votes for L = its label if < 260, else 0, with the weight
  *          q = (uint32)rintf(clamp(prob, 0, 1) * 65535.0f) (NaN: 0), summed per label in uint64; label = the label with
  *          the greatest sum, on a tie the smallest id; prob = (float)sum_label / (float)sum_all; sum_all == 0: label =
  *          the representative's L, prob = 0;
@@ -72,21 +71,20 @@
  *      The result is a pure function of the candidates and the parameters.
  *
  * Decomposition of the fusion: two orders over the same sorted keys, each made by two stable radix sorts of (value, index)
- * -- by timestamp (32 bits), then by key (64 bits: dropped candidates carry the all-ones key and sort behind every voxel);
- * and by label (9 bits), then by key.  The runs of both orders begin at the same positions.  In the first a voxel's
- * timestamps are ascending, so views is the number of changes plus one; in the second its members come by label, then by
- * index, so the vote needs one running sum (k_world.hip).  No atomics on records, no order that depends on a race.
+ * (group_sort_by_value_then_key, k_group.hip) -- by timestamp (32 bits), then by key (64 bits: dropped candidates carry
+ * VOXEL_NO_KEY and sort behind every voxel); and by label (9 bits), then by key.  The runs of both orders begin at the
+ * same positions.  In the first a voxel's timestamps are ascending, so views is the number of changes plus one; in the
+ * second its members come by label, then by index, so the vote needs one running sum (LabelVote).  No atomics on records,
+ * no order that depends on a race.
  */
 #include <cmath>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "suma_internal.h"
 #include "draw_vertex.h"
+#include "group_by_key.h"
 
 #define NOV_THREADS 256
-#define NOV_NO_KEY 0xffffffffffffffffull
 /* per-block counts of kn_collect, NOV_BLOCK_WORDS words a block */
 enum { NOV_NO_RETURN = 0, NOV_OUT_OF_RANGE, NOV_GRAZING, NOV_EXPLAINED, NOV_NOVEL, NOV_CATS, NOV_BLOCK_WORDS = 8 };
 
@@ -109,14 +107,7 @@ struct NovelArgs {
 __global__ void __launch_bounds__(NOV_THREADS) kn_mark(NovelArgs a) {
   const uint32_t o = blockIdx.x * NOV_THREADS + threadIdx.x;
   if (o >= a.total) return;
-  uint32_t lo = 0, hi = a.n_spans; /* the last span that starts at or before o (no span is empty) */
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a.spans[mid].dst <= o) lo = mid; else hi = mid;
-  }
-  const LocSpan sp = a.spans[lo];
-  const size_t k = (size_t)sp.src + (o - sp.dst);
-  const v3 p = xyz(a.sorted[3 * k]);
+  const v3 p = xyz(a.sorted[3 * loc_window_record(a.spans, a.n_spans, o)]);
   const v3 v = m4_point(a.Pinv.m, p);
   const float r = len3(v);
   const v3 pr = project01(a.q, v);
@@ -238,11 +229,6 @@ __global__ void __launch_bounds__(NOV_THREADS) kn_emit(NovelArgs a) {
 }
 
 /* ---- fusion ---- */
-/* k_world.hip's world_weight */
-SDEV uint32_t novel_weight(float w) {
-  const float c = (w > 0.0f) ? ((w < 1.0f) ? w : 1.0f) : 0.0f; /* NaN: 0 */
-  return (uint32_t)__builtin_rintf(c * 65535.0f);
-}
 SDEV uint32_t novel_vote_label(uint32_t label) { return label < 260u ? label : 0u; }
 enum { NOVF_DROPPED = 0, NOVF_VOXELS = 1, NOVF_OUT = 2, NOVF_COUNTERS = 4 };
 
@@ -256,16 +242,8 @@ __global__ void __launch_bounds__(NOV_THREADS)
   const uint32_t i = blockIdx.x * NOV_THREADS + threadIdx.x;
   if (i < n) {
     const float4 c0 = cand[3 * (size_t)i], c2 = cand[3 * (size_t)i + 2];
-    const float fx = sdm_floor(c0.x / voxel_size), fy = sdm_floor(c0.y / voxel_size), fz = sdm_floor(c0.z / voxel_size);
-    const bool ok = fabsf(fx) < 1048576.0f && fabsf(fy) < 1048576.0f && fabsf(fz) < 1048576.0f;
-    unsigned long long key = NOV_NO_KEY;
-    if (ok) {
-      const unsigned long long ix = (unsigned long long)((int32_t)fx + 1048576), iy = (unsigned long long)((int32_t)fy + 1048576),
-                               iz = (unsigned long long)((int32_t)fz + 1048576);
-      key = (ix << 42) | (iy << 21) | iz;
-    } else {
-      atomicAdd(&dropped, 1u);
-    }
+    unsigned long long key = VOXEL_NO_KEY;
+    if (!voxel_key(c0.x, c0.y, c0.z, voxel_size, &key)) atomicAdd(&dropped, 1u);
     key0[i] = key;
     stamp[i] = __float_as_uint(c2.z);
     label[i] = novel_vote_label(__float_as_uint(c2.x));
@@ -274,13 +252,6 @@ __global__ void __launch_bounds__(NOV_THREADS)
   }
   __syncthreads();
   if (threadIdx.x == 0 && dropped) atomicAdd(&counters[NOVF_DROPPED], dropped);
-}
-
-__global__ void __launch_bounds__(NOV_THREADS)
-    kn_gather(uint32_t n, const unsigned long long* __restrict__ key0, const uint32_t* __restrict__ idx,
-              unsigned long long* __restrict__ key1) {
-  const uint32_t j = blockIdx.x * NOV_THREADS + threadIdx.x;
-  if (j < n) key1[j] = key0[idx[j]];
 }
 
 /* keys: sorted; idx_a: the candidates by (key, timestamp, index) */
@@ -295,7 +266,7 @@ __global__ void __launch_bounds__(NOV_THREADS)
   if (j < n) {
     const unsigned long long key = keys[j];
     uint32_t keep = 0, nv = 0;
-    if (key != NOV_NO_KEY && (j == 0 || keys[j - 1] != key)) {
+    if (key != VOXEL_NO_KEY && (j == 0 || keys[j - 1] != key)) {
       uint32_t last = 0;
       for (uint32_t k = j; k < n && keys[k] == key; ++k) {
         const uint32_t ts = __float_as_uint(cand[3 * (size_t)idx_a[k] + 2].z);
@@ -324,32 +295,26 @@ __global__ void __launch_bounds__(NOV_THREADS)
   if (j == n - 1u) counters[NOVF_OUT] = o + f;
   if (!f || o >= capacity) return;
   const unsigned long long key = keys[j];
-  unsigned long long sum_all = 0, sum_cur = 0, sum_best = 0;
-  uint32_t lab_cur = 0xffffffffu, lab_best = 0, rep = 0, stamp = 0, support = 0;
+  LabelVote tally;
+  uint32_t rep = 0, stamp = 0, support = 0;
   float rad_best = 0.0f;
   for (uint32_t k = j; k < n && keys[k] == key; ++k) {
     const uint32_t s = idx_b[k];
     const float4 c0 = cand[3 * (size_t)s], c2 = cand[3 * (size_t)s + 2];
-    const uint32_t L = novel_vote_label(__float_as_uint(c2.x)), q = novel_weight(c2.y), ts = __float_as_uint(c2.z);
-    if (L != lab_cur) {
-      if (sum_cur > sum_best) sum_best = sum_cur, lab_best = lab_cur;
-      lab_cur = L, sum_cur = 0;
-    }
-    sum_cur += q;
-    sum_all += q;
+    const uint32_t ts = __float_as_uint(c2.z);
+    tally.add(novel_vote_label(__float_as_uint(c2.x)), vote_weight(c2.y));
     const float rad = (c0.w == c0.w) ? c0.w : INFINITY;
     if (support == 0 || rad < rad_best || (rad == rad_best && s < rep)) rad_best = rad, rep = s;
     stamp = (ts > stamp) ? ts : stamp;
     ++support;
   }
-  if (sum_cur > sum_best) sum_best = sum_cur, lab_best = lab_cur;
   const float4 r0 = cand[3 * (size_t)rep], r1 = cand[3 * (size_t)rep + 1], r2 = cand[3 * (size_t)rep + 2];
-  float prob = 0.0f;
-  if (sum_all != 0) prob = (float)sum_best / (float)sum_all; else lab_best = novel_vote_label(__float_as_uint(r2.x));
+  uint32_t label;
+  const float prob = tally.close(novel_vote_label(__float_as_uint(r2.x)), &label);
   float4* dst = out + 3 * (size_t)o;
   dst[0] = r0;
   dst[1] = f4(r1.x, r1.y, r1.z, confidence);
-  dst[2] = f4(__uint_as_float(lab_best), prob, __uint_as_float(stamp), __uint_as_float(support));
+  dst[2] = f4(__uint_as_float(label), prob, __uint_as_float(stamp), __uint_as_float(support));
   views_out[o] = views[j];
 }
 
@@ -417,18 +382,10 @@ int novel_fuse(suma_ctx* c, Novel& nv, uint32_t n, const suma_novel_fuse_params&
   uint32_t* views = labels + n; /* the identity for the second sort, then the views */
   uint32_t* counters = views + n;
 
-  size_t tmp = 16, b = 0;
-  {
-    rocprim::double_buffer<uint32_t> val(u0, u1), idx(u2, u3);
-    rocprim::double_buffer<unsigned long long> key(keyA, keyB);
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, b, u0, u1, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
-    tmp = b > tmp ? b : tmp;
-    HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, b, val, idx, (size_t)n, 0u, 32u, st));
-    tmp = b > tmp ? b : tmp;
-    HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, b, key, idx, (size_t)n, 0u, 64u, st));
-    tmp = b > tmp ? b : tmp;
-  }
+  size_t tmp = 0;
+  HIP_TRY(c, group_tmp_bytes(n, true, st, &tmp));
   if ((r = grow(c, nv.tmp, tmp, {st})) < 0) return r;
+  const size_t bytes = nv.tmp.cap;
 
   const unsigned blocks = (n + NOV_THREADS - 1) / NOV_THREADS;
   const float4* cand = nv.cand;
@@ -439,11 +396,7 @@ int novel_fuse(suma_ctx* c, Novel& nv, uint32_t n, const suma_novel_fuse_params&
   { /* the first order: by timestamp, then by key */
     rocprim::double_buffer<uint32_t> val(u0, u1), idx(u2, u3);
     rocprim::double_buffer<unsigned long long> key(keyA, keyB);
-    size_t bytes = nv.tmp.cap;
-    HIP_TRY(c, rocprim::radix_sort_pairs(nv.tmp, bytes, val, idx, (size_t)n, 0u, 32u, st));
-    kn_gather<<<blocks, NOV_THREADS, 0, st>>>(n, key0, idx.current(), key.current());
-    bytes = nv.tmp.cap;
-    HIP_TRY(c, rocprim::radix_sort_pairs(nv.tmp, bytes, key, idx, (size_t)n, 0u, 64u, st));
+    HIP_TRY(c, group_sort_by_value_then_key(nv.tmp, bytes, val, 32u, key0, key, 64u, idx, n, st));
     HIP_TRY(c, hipMemcpyAsync(order_a, idx.current(), words, hipMemcpyDeviceToDevice, st));
   }
   /* the second order: by label, then by key */
@@ -451,15 +404,10 @@ int novel_fuse(suma_ctx* c, Novel& nv, uint32_t n, const suma_novel_fuse_params&
   HIP_TRY(c, hipMemcpyAsync(u2, views, words, hipMemcpyDeviceToDevice, st));
   rocprim::double_buffer<uint32_t> val(u0, u1), idx(u2, u3);
   rocprim::double_buffer<unsigned long long> key(keyA, keyB);
-  size_t bytes = nv.tmp.cap;
-  HIP_TRY(c, rocprim::radix_sort_pairs(nv.tmp, bytes, val, idx, (size_t)n, 0u, 9u, st));
-  kn_gather<<<blocks, NOV_THREADS, 0, st>>>(n, key0, idx.current(), key.current());
-  bytes = nv.tmp.cap;
-  HIP_TRY(c, rocprim::radix_sort_pairs(nv.tmp, bytes, key, idx, (size_t)n, 0u, 64u, st));
+  HIP_TRY(c, group_sort_by_value_then_key(nv.tmp, bytes, val, 9u, key0, key, 64u, idx, n, st));
   /* the value pair is free now: head flags and positions */
   kn_heads<<<blocks, NOV_THREADS, 0, st>>>(n, key.current(), order_a, cand, fp.min_views, u0, views, counters);
-  bytes = nv.tmp.cap;
-  HIP_TRY(c, rocprim::exclusive_scan(nv.tmp, bytes, u0, u1, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+  HIP_TRY(c, group_scan(nv.tmp, bytes, u0, u1, n, st));
   kn_reduce<<<blocks, NOV_THREADS, 0, st>>>(n, key.current(), idx.current(), cand, u0, u1, views, fp.confidence,
                                             reinterpret_cast<float4*>(d_out), d_views, capacity, counters);
   HIP_TRY(c, hipGetLastError());

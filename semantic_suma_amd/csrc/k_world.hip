@@ -8,10 +8,8 @@
  *   kw_classify  lane per source record: label, filters, transform, voxel key; a keep flag (flat) or key / label / index /
  *                vote record (voxel mode); counts n_passed and n_dropped.
  *   kw_emit      flat mode, lane per source record: a kept record goes to the position the scan of the flags gives it.
- *   kw_gather    voxel mode: the keys in the order the label sort left the indices in.
- *   kw_heads     voxel mode, lane per sorted position: 1 where a voxel's run begins.
  *   kw_reduce    voxel mode, lane per sorted position: the lane at the head of a run walks it and writes the voxel's record.
- *   between them rocPRIM's exclusive_scan and radix_sort_pairs, as plain library calls (the precedent is k_filters.hip).
+ *   between them the sorts, the key gather, the run heads and the scan of k_group.hip.
  *
  * SPECIFICATION (fp32, every operation as written, no contraction: -ffp-contract=off; `/` correctly rounded;
  * tests/world_shim.c restates it on the host, bit for bit).
@@ -27,32 +25,33 @@
  *      The normal is not re-normalised.  A passed record with a non-finite p.x / p.y / p.z is DROPPED (n_dropped).
  *   3. voxel_size == 0: the output is the stable compaction of the surviving records in source order;
  *      prob = s.w, support = 1, radius / confidence / timestamp copied.
- *   4. voxel_size > 0: f_a = floorf(p_a / voxel_size) per axis; a record with any |f_a| >= 2^20 (an infinite quotient
- *      included) is DROPPED (n_dropped); i_a = (int)f_a; key = (ix + 2^20) << 42 | (iy + 2^20) << 21 | (iz + 2^20).
+ *   4. voxel_size > 0 (voxel_key, group_by_key.h): f_a = floorf(p_a / voxel_size) per axis; a record with any
+ *      |f_a| >= 2^20 (an infinite quotient included) is DROPPED (n_dropped); i_a = (int)f_a;
+ *      key = (ix + 2^20) << 42 | (iy + 2^20) << 21 | (iz + 2^20).
  *      One record per distinct key, in ascending key order:
  *      representative = the member with the greatest confidence, on a tie the smallest source index;
  *        x, y, z, radius, nx, ny, nz, confidence are the representative's.
- *      vote: a member votes for its L with the weight q = (uint32)rintf(clamp(s.w, 0, 1) * 65535.0f) (NaN: 0), summed per
- *        label in uint64 (exact, order-free); label = the label with the greatest sum, on a tie the smallest id;
+ *      vote (vote_weight and LabelVote, group_by_key.h): a member votes for its L with the weight
+ *        q = (uint32)rintf(clamp(s.w, 0, 1) * 65535.0f) (NaN: 0), summed per label in uint64 (exact, order-free);
+ *        label = the label with the greatest sum, on a tie the smallest id;
  *        prob = (float)sum_label / (float)sum_all; sum_all == 0: label = the representative's L, prob = 0.
  *      timestamp = the maximum over the members, support = the member count.
  * The output is a pure function of the source sequence, the pose table and the parameters.
  *
- * Decomposition of the voxel mode: two stable radix sorts of (key, source index), in place in double buffers -- by label (9 bits), then by voxel key
- * (64 bits: records that do not survive carry the all-ones key and sort behind every voxel).  Inside a voxel's run the
- * members are then ordered by label, then by source index, so the vote needs one running sum and the best (sum, label)
- * so far: no per-lane table of 260 sums, no atomics, and no order that depends on a race.
+ * Decomposition of the voxel mode: two stable radix sorts of (key, source index), in place in double buffers
+ * (group_sort_by_value_then_key, k_group.hip) -- by label (9 bits), then by voxel key (64 bits: records that do not
+ * survive carry VOXEL_NO_KEY and sort behind every voxel).  Inside a voxel's run the members are then ordered by label,
+ * then by source index, so the vote needs one running sum and the best (sum, label) so far: no per-lane table of 260
+ * sums, no atomics, and no order that depends on a race.
  */
 #include <cmath>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "suma_internal.h"
 #include "draw_vertex.h"
+#include "group_by_key.h"
 
 #define WORLD_THREADS 256
-#define WORLD_NO_KEY 0xffffffffffffffffull
 #define WORLD_KEEP_WORDS ((SUMA_DRAW_COLORS + 31) / 32)
 
 struct WorldArgs {
@@ -68,19 +67,10 @@ struct WorldArgs {
 enum { WORLD_PASSED = 0, WORLD_DROPPED = 1, WORLD_OUT = 2, WORLD_COUNTERS = 4 };
 
 SDEV const float4* world_source(const WorldArgs& a, uint32_t s) {
-  uint32_t lo = 0, hi = a.n_spans; /* the last span that starts at or before s (empty spans share their start) */
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a.spans[mid].start <= s) lo = mid; else hi = mid;
-  }
-  const WorldSpan sp = a.spans[lo];
+  const WorldSpan sp = world_span_find(a.spans, a.n_spans, s);
   return reinterpret_cast<const float4*>(sp.base + (s - sp.start));
 }
 /* world_label (step 1's rule) is in dev_math.h: k_change.hip reads labels by it too */
-SDEV uint32_t world_weight(float w) {
-  const float c = (w > 0.0f) ? ((w < 1.0f) ? w : 1.0f) : 0.0f; /* NaN: 0 */
-  return (uint32_t)__builtin_rintf(c * 65535.0f);
-}
 SDEV void world_store(suma_world_surfel* out, uint32_t o, const float4& p, float radius, const float4& n, float conf,
                       uint32_t label, float prob, uint32_t timestamp, uint32_t support) {
   float4* dst = reinterpret_cast<float4*>(out) + 3 * (size_t)o; /* 48-byte records: 16-byte aligned */
@@ -95,13 +85,7 @@ SDEV int world_classify(const WorldArgs& a, const float4& s0, const float4& s1, 
   if (!(s1.w > a.min_confidence) || !((a.keep[*L >> 5] >> (*L & 31u)) & 1u)) return 0;
   draw_vertex(a.poses, a.n_poses, s0, s1, s2.w, p, n);
   if (!(finite_f(p->x) && finite_f(p->y) && finite_f(p->z))) return 1;
-  if (a.voxel_size > 0.0f) {
-    const float fx = sdm_floor(p->x / a.voxel_size), fy = sdm_floor(p->y / a.voxel_size), fz = sdm_floor(p->z / a.voxel_size);
-    if (!(fabsf(fx) < 1048576.0f && fabsf(fy) < 1048576.0f && fabsf(fz) < 1048576.0f)) return 1;
-    const unsigned long long ix = (unsigned long long)((int32_t)fx + 1048576), iy = (unsigned long long)((int32_t)fy + 1048576),
-                             iz = (unsigned long long)((int32_t)fz + 1048576);
-    *key = (ix << 42) | (iy << 21) | iz;
-  }
+  if (a.voxel_size > 0.0f && !voxel_key(p->x, p->y, p->z, a.voxel_size, key)) return 1;
   return 2;
 }
 
@@ -127,13 +111,13 @@ __global__ void __launch_bounds__(WORLD_THREADS)
     const float4 s0 = sf[0], s1 = sf[1], s2 = sf[2], s3 = sf[3];
     uint32_t L;
     float4 p, n;
-    unsigned long long key = WORLD_NO_KEY;
+    unsigned long long key = VOXEL_NO_KEY;
     const int cls = world_classify(a, s0, s1, s2, s3, &L, &p, &n, &key);
     if (a.voxel_size > 0.0f) {
-      key0[s] = (cls == 2) ? key : WORLD_NO_KEY;
+      key0[s] = (cls == 2) ? key : VOXEL_NO_KEY;
       u0[s] = L;
       idx0[s] = s;
-      vote[s] = make_uint4(__float_as_uint(s1.w), (world_weight(s3.w) << 16) | L, __float_as_uint(s2.x), 0u);
+      vote[s] = make_uint4(__float_as_uint(s1.w), (vote_weight(s3.w) << 16) | L, __float_as_uint(s2.x), 0u);
     } else {
       u0[s] = (cls == 2) ? 1u : 0u;
     }
@@ -165,21 +149,6 @@ __global__ void __launch_bounds__(WORLD_THREADS)
 }
 
 __global__ void __launch_bounds__(WORLD_THREADS)
-    kw_gather(uint32_t n, const unsigned long long* __restrict__ key0, const uint32_t* __restrict__ idx1,
-              unsigned long long* __restrict__ key1) {
-  const uint32_t j = blockIdx.x * WORLD_THREADS + threadIdx.x;
-  if (j < n) key1[j] = key0[idx1[j]];
-}
-
-__global__ void __launch_bounds__(WORLD_THREADS)
-    kw_heads(uint32_t n, const unsigned long long* __restrict__ keys, uint32_t* __restrict__ flag) {
-  const uint32_t j = blockIdx.x * WORLD_THREADS + threadIdx.x;
-  if (j >= n) return;
-  const unsigned long long key = keys[j];
-  flag[j] = (key != WORLD_NO_KEY && (j == 0 || keys[j - 1] != key)) ? 1u : 0u;
-}
-
-__global__ void __launch_bounds__(WORLD_THREADS)
     kw_reduce(WorldArgs a, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ idx,
               const uint4* __restrict__ vote, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos,
               suma_world_surfel* __restrict__ out, uint32_t capacity, uint32_t* __restrict__ counters) {
@@ -190,32 +159,25 @@ __global__ void __launch_bounds__(WORLD_THREADS)
   if (!f || o >= capacity) return;
   const unsigned long long key = keys[j];
   /* members come by label, then by source index */
-  unsigned long long sum_all = 0, sum_cur = 0, sum_best = 0;
-  uint32_t lab_cur = 0xffffffffu, lab_best = 0, rep = 0, stamp = 0, support = 0;
+  LabelVote tally;
+  uint32_t rep = 0, stamp = 0, support = 0;
   float conf_best = 0.0f;
   for (uint32_t k = j; k < a.n && keys[k] == key; ++k) {
     const uint32_t s = idx[k];
     const uint4 v = vote[s];
     const float conf = __uint_as_float(v.x);
-    const uint32_t L = v.y & 0xffffu, q = v.y >> 16;
-    if (L != lab_cur) {
-      if (sum_cur > sum_best) sum_best = sum_cur, lab_best = lab_cur;
-      lab_cur = L, sum_cur = 0;
-    }
-    sum_cur += q;
-    sum_all += q;
+    tally.add(v.y & 0xffffu, v.y >> 16);
     if (support == 0 || conf > conf_best || (conf == conf_best && s < rep)) conf_best = conf, rep = s;
     stamp = (v.z > stamp) ? v.z : stamp;
     ++support;
   }
-  if (sum_cur > sum_best) sum_best = sum_cur, lab_best = lab_cur;
   const float4* sf = world_source(a, rep);
   const float4 s0 = sf[0], s1 = sf[1], s2 = sf[2], s3 = sf[3];
   float4 p, n;
   draw_vertex(a.poses, a.n_poses, s0, s1, s2.w, &p, &n);
-  float prob = 0.0f;
-  if (sum_all != 0) prob = (float)sum_best / (float)sum_all; else lab_best = world_label(s3.x);
-  world_store(out, o, p, s0.w, n, s1.w, lab_best, prob, stamp, support);
+  uint32_t label;
+  const float prob = tally.close(world_label(s3.x), &label);
+  world_store(out, o, p, s0.w, n, s1.w, label, prob, stamp, support);
 }
 
 /* ---- host side ---- */
@@ -302,19 +264,8 @@ extern "C" int suma_map_export_world(suma_ctx* c, const suma_world_params* wp, s
   uint32_t* u0 = reinterpret_cast<uint32_t*>(base + (voxel ? (size_t)32 * N : 0)); /* labels, then head flags / keep flags */
   uint32_t *u1 = u0 + N /* sorted labels, then positions */, *u2 = u1 + N /* indices, then by voxel */, *u3 = u2 + N /* by label */;
 
-  size_t tmp = 16, b = 0;
-  if (N) {
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, b, u0, u1, 0u, (size_t)N, rocprim::plus<uint32_t>(), c->stream));
-    tmp = b > tmp ? b : tmp;
-    if (voxel) {
-      rocprim::double_buffer<uint32_t> lab(u0, u1), idx(u2, u3);
-      rocprim::double_buffer<unsigned long long> key(keyB, keyA);
-      HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, b, lab, idx, (size_t)N, 0u, 9u, c->stream));
-      tmp = b > tmp ? b : tmp;
-      HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, b, key, idx, (size_t)N, 0u, 64u, c->stream));
-      tmp = b > tmp ? b : tmp;
-    }
-  }
+  size_t tmp = 0;
+  HIP_TRY(c, group_tmp_bytes(N, voxel, c->stream, &tmp));
   if ((r = grow(c, c->world_tmp, tmp, {c->stream})) < 0) return r;
 
   WorldArgs a;
@@ -335,7 +286,7 @@ extern "C" int suma_map_export_world(suma_ctx* c, const suma_world_params* wp, s
   HIP_TRY(c, hipMemsetAsync(c->world_counters, 0, WORLD_COUNTERS * sizeof(uint32_t), st));
   if (N) {
     const unsigned blocks = (N + WORLD_THREADS - 1) / WORLD_THREADS;
-    size_t bytes = c->world_tmp.cap;
+    const size_t bytes = c->world_tmp.cap;
     {
       ProfScope ps(c, "world_classify", 64.0 * N);
       const unsigned per_block = WORLD_THREADS * WORLD_CLASSIFY_ITEMS;
@@ -344,22 +295,17 @@ extern "C" int suma_map_export_world(suma_ctx* c, const suma_world_params* wp, s
     }
     if (!voxel) {
       ProfScope ps(c, "world_emit", 72.0 * N);
-      HIP_TRY(c, rocprim::exclusive_scan(c->world_tmp, bytes, u0, u1, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
+      HIP_TRY(c, group_scan(c->world_tmp, bytes, u0, u1, N, st));
       kw_emit<<<blocks, WORLD_THREADS, 0, st>>>(a, u0, u1, d_out, capacity, c->world_counters);
     } else {
       rocprim::double_buffer<uint32_t> lab(u0, u1), idx(u2, u3); /* labels / source indices as kw_classify wrote them */
-      rocprim::double_buffer<unsigned long long> key(keyB, keyA); /* filled by kw_gather from keyA, which is then dead */
+      rocprim::double_buffer<unsigned long long> key(keyB, keyA); /* keyB is filled from keyA, which is then dead */
       {
         ProfScope ps(c, "world_sort", 64.0 * N);
-        HIP_TRY(c, rocprim::radix_sort_pairs(c->world_tmp, bytes, lab, idx, (size_t)N, 0u, 9u, st));
-        kw_gather<<<blocks, WORLD_THREADS, 0, st>>>(N, keyA, idx.current(), keyB);
-        bytes = c->world_tmp.cap;
-        HIP_TRY(c, rocprim::radix_sort_pairs(c->world_tmp, bytes, key, idx, (size_t)N, 0u, 64u, st));
+        HIP_TRY(c, group_sort_by_value_then_key(c->world_tmp, bytes, lab, 9u, keyA, key, 64u, idx, N, st));
       }
       ProfScope ps(c, "world_reduce", 40.0 * N);
-      kw_heads<<<blocks, WORLD_THREADS, 0, st>>>(N, key.current(), u0);
-      bytes = c->world_tmp.cap;
-      HIP_TRY(c, rocprim::exclusive_scan(c->world_tmp, bytes, u0, u1, 0u, (size_t)N, rocprim::plus<uint32_t>(), st));
+      HIP_TRY(c, group_heads(c->world_tmp, bytes, key.current(), VOXEL_NO_KEY, u0, u1, N, st));
       kw_reduce<<<blocks, WORLD_THREADS, 0, st>>>(a, key.current(), idx.current(), vote, u0, u1, d_out, capacity,
                                                   c->world_counters);
     }

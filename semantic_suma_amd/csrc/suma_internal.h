@@ -15,6 +15,8 @@
 #include <utility>
 #include <vector>
 
+#include <rocprim/types/double_buffer.hpp>
+
 #include "../../include/suma_hip.h"
 #include "dev_math.h"
 
@@ -534,6 +536,27 @@ int loop_ckpt_write(suma_pipeline* s, std::vector<char>* loop, std::vector<char>
 int loop_ckpt_check(suma_ctx* c, const char* loop, const char* graph, const char* opt, uint32_t timestamp,
                     suma_loop_params* params);
 int loop_ckpt_install(suma_pipeline* s, const char* loop, const char* graph, const char* opt);
+
+/* k_group.hip: records grouped by a key, for the world export, the novelty fusion and the localiser's binning.  Every
+ * entry enqueues on st, in the caller's arrays and in the caller's temporary block of tmp_bytes >= group_tmp_bytes(n);
+ * current() of each pair is the sorted array afterwards. */
+/* sorts == false: only group_scan will be called */
+hipError_t group_tmp_bytes(uint32_t n, bool sorts, hipStream_t st, size_t* bytes);
+/* stable sort of (key, idx) by the low key_bits of key */
+hipError_t group_sort(void* tmp, size_t tmp_bytes, rocprim::double_buffer<unsigned long long>& key,
+                      rocprim::double_buffer<uint32_t>& idx, uint32_t n, unsigned key_bits, hipStream_t st);
+/* stable sort of (val, idx) by value_bits of val; key.current()[j] = key0[idx[j]] (key0 may be key's other half); stable
+ * sort of (key, idx) by key_bits: idx is then ordered by (key, val, its order on entry) */
+hipError_t group_sort_by_value_then_key(void* tmp, size_t tmp_bytes, rocprim::double_buffer<uint32_t>& val,
+                                        unsigned value_bits, const unsigned long long* key0,
+                                        rocprim::double_buffer<unsigned long long>& key, unsigned key_bits,
+                                        rocprim::double_buffer<uint32_t>& idx, uint32_t n, hipStream_t st);
+/* pos = the exclusive prefix sum of flag */
+hipError_t group_scan(void* tmp, size_t tmp_bytes, const uint32_t* flag, uint32_t* pos, uint32_t n, hipStream_t st);
+/* flag[j] = 1 where a run of sorted keys begins (keys[j] != no_key, and j == 0 or keys[j - 1] != keys[j]), then
+ * group_scan: pos = the run's rank */
+hipError_t group_heads(void* tmp, size_t tmp_bytes, const unsigned long long* keys, unsigned long long no_key,
+                       uint32_t* flag, uint32_t* pos, uint32_t n, hipStream_t st);
 
 /* k_localize.hip (the specification is there): the world map binned into submap tiles, and the window gather */
 struct LocTile { /* one occupied tile of the directory, ascending by key */
