@@ -182,7 +182,11 @@ int suma_map_download(suma_ctx* ctx, suma_surfel* host, uint32_t cap, uint32_t* 
 int suma_map_export_surfels(suma_ctx* ctx, void** d_ptr, uint32_t* n);
 int suma_map_export_data_surfels(suma_ctx* ctx, void** d_ptr, uint32_t* first, uint32_t* n_data);
 /* replace the active map alone (tests, map surgery); a whole session is saved and resumed with
- * suma_pipeline_checkpoint_save / _load below */
+ * suma_pipeline_checkpoint_save / _load below.  At most max_surfels records are taken.
+ * DOMAIN: every record's `count` (its creation stamp) must be an integer in [0, max_poses).  The update, render and
+ * extraction kernels index the pose table by it unchecked, as the reference's shaders fetch poseBuffer; a record outside
+ * that range makes them read out of bounds.  Position, normal, radius, confidence, weight and the semantic payload may
+ * hold any float (NaN, inf and zero included: tests/test_update_crafted_host.py "bad-records"). */
 int suma_map_upload(suma_ctx* ctx, const suma_surfel* host, uint32_t n, uint32_t timestamp);
 /* intermediates of the last update, for stage-by-stage parity tests */
 int suma_map_download_index_map(suma_ctx* ctx, uint32_t* host);      /* P, surfel id + 1 (uint32, not float) */

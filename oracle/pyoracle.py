@@ -37,7 +37,8 @@ c_f8p = C.POINTER(C.c_double)
 def build(force: bool = False) -> None:
     """Compile the oracle with gcc (seconds)."""
     tgt = os.path.join(_HERE, "libsuma_oracle.so")
-    srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith((".c", ".h"))]
+    srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith((".c", ".h"))] + [os.path.join(_HERE, "Makefile")]
+    srcs += [os.path.join(_HERE, "debug", f) for f in os.listdir(os.path.join(_HERE, "debug")) if f.endswith((".c", ".h"))]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("suma_detmath.h", "suma_types.h")]
     if force or not os.path.exists(tgt) or any(os.path.getmtime(s) > os.path.getmtime(tgt) for s in srcs):
         subprocess.check_call(["make", "-C", _HERE, "all"], stdout=subprocess.DEVNULL)
@@ -113,6 +114,7 @@ def lib(variant: str = ""):
     L.ora_map_last_extraction.restype = C.c_uint32
     L.ora_map_last_extraction.argtypes = [vp, vp]
     L.ora_debug_render_quads.argtypes = [vp, vp, C.c_float, C.c_int, C.c_int32, vp, vp, vp]
+    L.ora_debug_update_terms.argtypes = [vp, vp, C.c_uint32, vp, vp, vp]
     L.ora_debug_raster_quads.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_uint32, C.c_int, C.c_int, vp]
     L.ora_debug_depth24.argtypes = [vp, C.c_uint32, vp]
     L.ora_pipeline_create.restype = vp
@@ -361,6 +363,17 @@ class Oracle:
         pn = np.zeros((max(n, 1), 6), dtype=np.float32)
         self.L.ora_debug_render_quads(self.h, _ptr(po), conf_threshold, mode, thr, _ptr(emitted), _ptr(corners), _ptr(pn))
         return emitted[:n], corners[:n], pn[:n]
+
+    def debug_update_terms(self, pose, frame):
+        """the fp32 terms K9 would compare for the map's surfels in an update at `pose` (oracle/debug/o_update_terms.c;
+        nothing changes): [n, 6] = x01 * W, y01 * H (before the floor), imz, the front-face product, and -- NaN unless both
+        texels are valid -- distance, angle"""
+        n = self.map_size()
+        rec = np.ascontiguousarray(self.map_surfels())
+        po = np.ascontiguousarray(np.asarray(pose, dtype=np.float32).T)
+        terms = np.full((max(n, 1), 6), np.nan, dtype=np.float32)
+        self.L.ora_debug_update_terms(self.h, _ptr(rec), n, _ptr(po), frame.h, _ptr(terms))
+        return terms[:n]
 
     def debug_raster_quads(self, W, H, corners, ids, use_disc=True, use_depth=True):
         """the triangle rasteriser alone on given quads ([n, 4, 3] corners in [0,1]^3): winner id per pixel, -1 = none"""
