@@ -263,6 +263,25 @@ class LieGaussNewton {
   suma_icp_stats stats_;
 };
 
+/* The 2.5-D semantic traversability grid of n world-frame records on the device (suma_world_grid; what exportWorld
+ * writes, or a caller's records after suma_device_upload): gp.width * gp.height cells, row-major, row = y, computed on
+ * the device and returned on the host.  fit_margin >= 0: the raster is first fitted to the records with that many empty
+ * cells around them (suma_world_grid_fit), and gp receives it. */
+inline std::vector<suma_grid_cell> worldGrid(Context& ctx, suma_grid_params& gp, const suma_world_surfel* d_records, uint32_t n,
+                                             int fit_margin = -1, suma_grid_stats* stats = nullptr) {
+  if (fit_margin >= 0) check(ctx.get(), suma_world_grid_fit(ctx.get(), d_records, n, (uint32_t)fit_margin, &gp), "worldGrid");
+  std::vector<suma_grid_cell> out((size_t)gp.width * gp.height);
+  suma_grid_stats st;
+  void* d = nullptr;
+  check(ctx.get(), suma_device_alloc(ctx.get(), (uint64_t)(out.size() ? out.size() : 1) * sizeof(suma_grid_cell), &d), "worldGrid");
+  int rc = suma_world_grid(ctx.get(), &gp, d_records, n, (suma_grid_cell*)d, &st);
+  if (rc == SUMA_OK) rc = suma_device_download(ctx.get(), out.data(), d, (uint64_t)out.size() * sizeof(suma_grid_cell));
+  suma_device_free(ctx.get(), d);
+  check(ctx.get(), rc, "worldGrid");
+  if (stats) *stats = st;
+  return out;
+}
+
 /* src/core/SurfelMap.h:36-78 (draw / setColorMap are visualisation and stay with the GL code) */
 class SurfelMap {
  public:
@@ -355,6 +374,28 @@ class SurfelMap {
     }
     world_capacity_ = st.n_out + st.n_out / 4;
     if (stats) *stats = st;
+    return out;
+  }
+  /* the traversability grid of the whole map (worldGrid above): the flat world export wp selects goes into a device
+   * buffer and is gridded there, so the records never visit the host */
+  std::vector<suma_grid_cell> exportGrid(suma_grid_params& gp, const suma_world_params& wp, int fit_margin = -1,
+                                         suma_grid_stats* stats = nullptr) {
+    if (wp.voxel_size != 0.0f) throw std::runtime_error("SurfelMap::exportGrid: the grid takes the flat export (voxel_size 0)");
+    suma_world_stats st, st2;
+    check(ctx_.get(), suma_map_export_world(ctx_.get(), &wp, nullptr, 0, &st), "SurfelMap::exportGrid"); /* the size */
+    void* d = nullptr;
+    check(ctx_.get(), suma_device_alloc(ctx_.get(), (uint64_t)(st.n_out ? st.n_out : 1) * sizeof(suma_world_surfel), &d),
+          "SurfelMap::exportGrid");
+    std::vector<suma_grid_cell> out;
+    try {
+      check(ctx_.get(), suma_map_export_world(ctx_.get(), &wp, (suma_world_surfel*)d, st.n_out, &st2), "SurfelMap::exportGrid");
+      if (st2.n_out != st.n_out) throw std::runtime_error("SurfelMap::exportGrid: the map changed between two exports");
+      out = worldGrid(ctx_, gp, (const suma_world_surfel*)d, st.n_out, fit_margin, stats);
+    } catch (...) {
+      suma_device_free(ctx_.get(), d);
+      throw;
+    }
+    suma_device_free(ctx_.get(), d);
     return out;
   }
 

@@ -530,6 +530,67 @@ int suma_map_cached_tiles(suma_ctx* ctx, int32_t* ij, uint32_t capacity, uint32_
 int suma_map_export_world(suma_ctx* ctx, const suma_world_params* wp, suma_world_surfel* d_out, uint32_t capacity,
                           suma_world_stats* stats);
 
+/* ---- a 2.5-D semantic traversability grid of world-frame records, for a planner: per cell of an x / y raster the ground
+ *      height, what stands on it within the robot's height, the voted class and a state (k_grid.hip states the
+ *      specification; tests/grid_shim.c restates it on the host, and the grid equals it byte for byte).
+ *      The world frame has z UP: it is the first scan's sensor frame (x forward, y left, z up), so "height" is z and the
+ *      raster spans x (columns) and y (rows). */
+typedef struct suma_grid_params {
+  float cell_size;            /* metres; finite, > 0; default 0.2 */
+  float origin_x, origin_y;   /* world coordinates of the lower corner of cell (0, 0); finite */
+  uint32_t width, height;     /* cells along x / y; >= 1; width * height <= 2^26 */
+  uint8_t ground_label[SUMA_DRAW_COLORS]; /* a label counts as ground iff != 0; default: 40 road, 44 parking, 48 sidewalk,
+                                             49 other-ground, 60 lane-marking, 72 terrain */
+  float min_normal_z;         /* default 0.7: a ground member needs |nz| >= this (a NaN never does) */
+  float step_height;          /* default 0.2 m: a member more than this above the ground is an obstacle; finite */
+  float clearance;            /* default 2.0 m: a member more than this above the ground is an overhang; finite, > step_height */
+  uint32_t fill_radius;       /* default 2 cells; 0 .. 8: how far a cell without ground looks for a neighbour's */
+} suma_grid_params;
+
+enum { SUMA_GRID_UNKNOWN = 0, SUMA_GRID_FREE = 1, SUMA_GRID_OBSTACLE = 2, SUMA_GRID_NO_GROUND = 3 };
+
+typedef struct suma_grid_cell {   /* 48 bytes */
+  float ground_z, ground_rough, z_min, z_max;   /* NaN where undefined */
+  float obstacle_z, prob;         /* the highest obstacle member's z (NaN: none); the voted label's share of the vote */
+  uint32_t label, support;        /* the voted label; the records binned into the cell */
+  uint32_t n_ground, n_obstacle, n_overhang;
+  uint8_t state;          /* 0 UNKNOWN, 1 FREE, 2 OBSTACLE, 3 NO_GROUND */
+  uint8_t ground_source;  /* 0 none, 1 own, 2 filled from a neighbour */
+  uint8_t pad[2];         /* 0 */
+} suma_grid_cell;
+
+typedef struct suma_grid_stats {
+  uint32_t n_records, n_dropped, n_outside, n_binned; /* n_records = n_dropped + n_outside + n_binned */
+  uint32_t n_occupied;                                /* cells with support > 0 = n_free + n_obstacle + n_no_ground */
+  uint32_t n_free, n_obstacle, n_no_ground;           /* cells by state */
+  uint32_t n_filled;                                  /* cells with ground_source 2 */
+} suma_grid_stats;
+
+/* the defaults above; origin 0, 0 and width = height = 0: to be set, or fitted by suma_world_grid_fit */
+void suma_grid_params_default(suma_grid_params* gp);
+/* Both entries take a DEVICE array of n records, 16-byte aligned (what suma_map_export_world writes, or a caller's records
+ *   after suma_device_upload), run on the ctx stream and block once, for their result.  They write only scratch of the ctx
+ *   and the caller's d_cells: the records, the map and every counter of the ctx stay as they are.
+ *   SUMA_ERR_INVALID with a message, and nothing launched: a NULL ctx / gp / stats / d_cells, a NULL d_records with n > 0,
+ *   a misaligned d_records / d_cells, n >= 2^31, and any parameter outside the ranges stated at suma_grid_params.
+ * suma_world_grid_fit: sets gp's origin, width and height (cell_size is read) to the raster that holds every record whose
+ *   x, y and z are finite, with margin_cells (<= 2^20) empty cells around it:
+ *   origin_a = (floorf(min_a / cell_size) - margin_cells) * cell_size,
+ *   width = (uint)(floorf(max_x / cell_size) - floorf(min_x / cell_size)) + 1 + 2 * margin_cells, height likewise.
+ *   (A record within an ulp of a cell edge may fall into the neighbouring cell when the grid divides (x - origin_x): a
+ *   margin of one cell keeps every record inside.)  SUMA_ERR_CAPACITY, gp untouched, when width, height or
+ *   width * height would exceed 2^26; SUMA_ERR_INVALID when no record is finite.
+ * suma_world_grid: d_cells = width * height cells, row-major, row = y (cell (ix, iy) at iy * width + ix); every cell is
+ *   written.  Two calls on the same input give the same bytes.
+ *   Scratch, kept by the ctx and grown by its one rule: 48 bytes per record (a 16-byte member record and the double
+ *   buffers of the two sorts: keys 2 x 8, labels 2 x 4, indices 2 x 4; it is the block suma_map_export_world's voxel mode
+ *   uses, as are the sorts' histograms) and 16 bytes per cell (the cell's run in the sorted records, its ground count
+ *   and ground height). */
+int suma_world_grid_fit(suma_ctx* ctx, const suma_world_surfel* d_records, uint32_t n, uint32_t margin_cells,
+                        suma_grid_params* gp);
+int suma_world_grid(suma_ctx* ctx, const suma_grid_params* gp, const suma_world_surfel* d_records, uint32_t n,
+                    suma_grid_cell* d_cells, suma_grid_stats* stats);
+
 /* ---- device scratch for callers that keep scans resident in HBM (bench, replay) */
 int suma_device_alloc(suma_ctx* ctx, uint64_t bytes, void** d_ptr);
 int suma_device_free(suma_ctx* ctx, void* d_ptr);

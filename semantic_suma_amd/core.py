@@ -32,6 +32,7 @@ import numpy as np
 from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX_LIGHTS, SURFEL_DTYPE, DrawParams,
                     IcpStats, LoopParams, LoopStatus, PosegraphParams, PosegraphStats, SemanticKnnParams,
                     SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats, CheckpointInfo,
+                    GRID_CELL_DTYPE, GridParams, GridStats,
                     ChangeCounts, ChangeParams, ChangeRule, DeskewParams, EVIDENCE_DTYPE, NovelCounts, NovelFuseParams, NovelParams, NovelStats, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -252,6 +253,10 @@ def lib():
     L.suma_world_params_default.restype = None
     L.suma_map_cached_tiles.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.suma_map_export_world.argtypes = [vp, C.POINTER(WorldParams), vp, u32, C.POINTER(WorldStats)]
+    L.suma_grid_params_default.argtypes = [C.POINTER(GridParams)]
+    L.suma_grid_params_default.restype = None
+    L.suma_world_grid_fit.argtypes = [vp, vp, u32, u32, C.POINTER(GridParams)]
+    L.suma_world_grid.argtypes = [vp, C.POINTER(GridParams), vp, u32, vp, C.POINTER(GridStats)]
     L.suma_device_alloc.argtypes = [vp, C.c_uint64, pp]
     L.suma_device_free.argtypes = [vp, vp]
     L.suma_device_upload.argtypes = [vp, vp, vp, C.c_uint64]
@@ -758,6 +763,43 @@ def _dev(p):
     return None if p is None or int(p) == 0 else C.c_void_p(int(p))
 
 
+def world_grid(ctx: "Context", records, n: int = None, params: GridParams = None, fit_margin: int = None, **kw):
+    """The 2.5-D semantic traversability grid of world-frame records (suma_world_grid; csrc/k_grid.hip states the rules):
+    -> (cells[height, width] of GRID_CELL_DTYPE, row = y, the GridParams used, the stats as a dict).  ``records``: a
+    WORLD_SURFEL_DTYPE array (uploaded for the call), or a device address / torch tensor with ``n`` records.  ``params``:
+    a GridParams, or the keywords of GridParams.defaults.  The raster is fitted to the records (suma_world_grid_fit, with
+    ``fit_margin`` empty cells around them, default 1) when ``fit_margin`` is given or the parameters carry no size."""
+    gp = GridParams.defaults(**kw) if params is None else GridParams.from_buffer_copy(params)
+    L, h = ctx.L, ctx.h
+    owned = None
+    if isinstance(records, np.ndarray):
+        rec = np.ascontiguousarray(records, dtype=WORLD_SURFEL_DTYPE).reshape(-1)
+        n = rec.shape[0] if n is None else int(n)
+        if n > rec.shape[0]:
+            raise ValueError("world_grid: n exceeds the records given")
+        d_rec = owned = ctx.device_array(rec[:n]) if n else None
+    else:
+        if n is None:
+            raise ValueError("world_grid: n is needed with a device address")
+        d_rec = records
+    d_cells = C.c_void_p()
+    try:
+        if fit_margin is not None or gp.width == 0 or gp.height == 0:
+            ctx.check(L.suma_world_grid_fit(h, _dev(d_rec), n, 1 if fit_margin is None else int(fit_margin), C.byref(gp)),
+                      "suma_world_grid_fit")
+        cells = np.zeros((gp.height, gp.width), dtype=GRID_CELL_DTYPE)
+        st = GridStats()
+        ctx.check(L.suma_device_alloc(h, max(cells.nbytes, 48), C.byref(d_cells)), "suma_device_alloc")
+        ctx.check(L.suma_world_grid(h, C.byref(gp), _dev(d_rec), n, d_cells, C.byref(st)), "suma_world_grid")
+        ctx.check(L.suma_device_download(h, _ptr(cells), d_cells, cells.nbytes), "suma_device_download")
+    finally:
+        if d_cells:
+            L.suma_device_free(h, d_cells)
+        if owned:
+            L.suma_device_free(h, C.c_void_p(owned))
+    return cells, gp, st.as_dict()
+
+
 class SurfelMap:
     """SurfelMap.h:36-78"""
 
@@ -967,6 +1009,26 @@ class SurfelMap:
             cap = st.n_out
         self._world_capacity = st.n_out + st.n_out // 4
         return (out, st.as_dict()) if stats else out
+
+    def export_grid(self, cell_size: float = 0.2, params: GridParams = None, fit_margin: int = None,
+                    min_confidence=None, keep_labels=None, **kw):
+        """The traversability grid of the whole map (core.world_grid): the flat world export (``min_confidence``,
+        ``keep_labels`` as export_world) into a device buffer, gridded there -- the records never visit the host.
+        ``params`` / ``fit_margin`` / the keywords are world_grid's.  -> (cells[height, width], GridParams, stats dict)"""
+        wp = WorldParams.defaults(0.0, min_confidence, keep_labels)
+        L, h = self.ctx.L, self.ctx.h
+        n = self.export_world_device(wp, None, 0).n_out  # the size
+        d = C.c_void_p()
+        self.ctx.check(L.suma_device_alloc(h, max(n, 1) * WORLD_SURFEL_DTYPE.itemsize, C.byref(d)), "suma_device_alloc")
+        try:
+            st = self.export_world_device(wp, d.value, n)
+            if st.n_out != n:
+                raise SumaError("suma_map_export_world: the map changed between two exports")
+            if params is None:
+                kw = dict(kw, cell_size=cell_size)
+            return world_grid(self.ctx, d.value, n, params, fit_margin, **kw)
+        finally:
+            L.suma_device_free(h, d)
 
     def counts(self):
         """(S' survivors of K9, D new surfels of K10, surfels parked in submap caches, submap origin)"""

@@ -248,6 +248,11 @@ struct suma_ctx {
   DevBuf<char> world_scratch, world_tmp;
   DevBuf<uint32_t> world_counters;
   PinnedBuf<uint32_t> world_counters_h;
+  /* suma_world_grid / _fit (k_grid.hip), allocated on first use: 16 bytes a raster cell and the counters; the per-record
+   * arrays and the sorts' storage are world_scratch and world_tmp (both run on the ctx stream, one behind the other) */
+  DevBuf<uint4> grid_runs;
+  DevBuf<uint32_t> grid_counters;
+  PinnedBuf<uint32_t> grid_counters_h;
   /* suma_pipeline_checkpoint_save / _load (k_checkpoint.hip), allocated on first use: the staged image, the span table
    * of kc_pack and one digest word per section */
   DevBuf<char> ckpt_image;
@@ -557,6 +562,19 @@ hipError_t group_scan(void* tmp, size_t tmp_bytes, const uint32_t* flag, uint32_
  * group_scan: pos = the run's rank */
 hipError_t group_heads(void* tmp, size_t tmp_bytes, const unsigned long long* keys, unsigned long long no_key,
                        uint32_t* flag, uint32_t* pos, uint32_t n, hipStream_t st);
+
+/* k_grid.hip (the specification is there): the traversability grid of world-frame records.  Both enqueue on c->stream. */
+enum { GRID_DROPPED = 0, GRID_OUTSIDE, GRID_OCCUPIED, GRID_FREE, GRID_OBSTACLE, GRID_NO_GROUND, GRID_FILLED,
+       GRID_FIT_MIN_X, GRID_FIT_MIN_Y, GRID_FIT_MAX_X, GRID_FIT_MAX_Y, GRID_COUNTERS = 16 };
+#define GRID_SCRATCH_PER_RECORD 48u
+/* the caller has grown c->world_scratch to GRID_SCRATCH_PER_RECORD * n bytes, c->world_tmp to group_tmp_bytes(n, true),
+ * c->grid_runs to width * height entries and c->grid_counters to GRID_COUNTERS words (zeroed here) */
+hipError_t launch_grid(suma_ctx* c, const suma_grid_params& gp, const suma_world_surfel* d_records, uint32_t n,
+                       suma_grid_cell* d_cells);
+/* c->grid_counters[GRID_FIT_*] = the extent of the finite records as ordered integers (grid_ordered_float inverts them);
+ * MIN_X stays 0xffffffff when there is none */
+hipError_t launch_grid_fit(suma_ctx* c, const suma_world_surfel* d_records, uint32_t n);
+float grid_ordered_float(uint32_t o);
 
 /* k_localize.hip (the specification is there): the world map binned into submap tiles, and the window gather */
 struct LocTile { /* one occupied tile of the directory, ascending by key */

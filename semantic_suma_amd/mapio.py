@@ -2,13 +2,18 @@
 
     write_ply(path, world_surfels, color_map=None)   x y z nx ny nz radius confidence label prob support + red green blue
     read_ply(path) -> (world_surfels, rgb)           the round trip (timestamp, which the file does not carry, reads 0)
+
+and core.world_grid's traversability grid as one .npz:
+
+    write_grid(path, cells, params)                  the cells [height, width] and the GridParams that made them
+    read_grid(path) -> (cells, params)
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import kitti
-from .types import WORLD_SURFEL_DTYPE
+from .types import GRID_CELL_DTYPE, WORLD_SURFEL_DTYPE, GridParams
 
 # the PLY vertex: name, PLY type, numpy type
 _PLY_FIELDS = [("x", "float", "<f4"), ("y", "float", "<f4"), ("z", "float", "<f4"),
@@ -84,3 +89,27 @@ def read_ply(path: str):
         if name in dt.names:
             rgb[:, k] = v[name]
     return ws, rgb
+
+
+def write_grid(path: str, cells: np.ndarray, params: GridParams) -> None:
+    """``cells``: GRID_CELL_DTYPE [height, width] as core.world_grid returns them; ``params``: the GridParams of that call
+    (cell size, origin and size place the raster in the world frame).  ``path`` is written as given (end it in .npz)."""
+    c = np.ascontiguousarray(cells, dtype=GRID_CELL_DTYPE)
+    if c.shape != (params.height, params.width):
+        raise ValueError(f"write_grid: cells {c.shape} against a raster of {params.height} x {params.width}")
+    with open(path, "wb") as f:
+        np.savez_compressed(f, cells=c.view(np.uint8).reshape(c.shape + (GRID_CELL_DTYPE.itemsize,)),
+                            params=np.frombuffer(bytes(params), dtype=np.uint8))
+
+
+def read_grid(path: str):
+    """-> (GRID_CELL_DTYPE cells [height, width], GridParams) of a file write_grid made"""
+    with np.load(path) as z:
+        raw, par = z["cells"], z["params"]
+    if par.dtype != np.uint8 or par.size != len(bytes(GridParams())) or raw.dtype != np.uint8 or raw.ndim != 3 or \
+            raw.shape[2] != GRID_CELL_DTYPE.itemsize:
+        raise ValueError(f"{path}: not a grid file")
+    gp = GridParams.from_buffer_copy(par.tobytes())
+    if raw.shape[:2] != (gp.height, gp.width):
+        raise ValueError(f"{path}: cells {raw.shape[:2]} against a raster of {gp.height} x {gp.width}")
+    return np.ascontiguousarray(raw).view(GRID_CELL_DTYPE).reshape(gp.height, gp.width), gp

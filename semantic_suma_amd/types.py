@@ -124,6 +124,52 @@ class WorldStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# numpy view of the 48-byte cell of the traversability grid (``struct suma_grid_cell``, core.world_grid)
+GRID_CELL_DTYPE = np.dtype([
+    ("ground_z", "<f4"), ("ground_rough", "<f4"), ("z_min", "<f4"), ("z_max", "<f4"),
+    ("obstacle_z", "<f4"), ("prob", "<f4"), ("label", "<u4"), ("support", "<u4"),
+    ("n_ground", "<u4"), ("n_obstacle", "<u4"), ("n_overhang", "<u4"),
+    ("state", "u1"), ("ground_source", "u1"), ("pad", "u1", (2,)),
+])
+assert GRID_CELL_DTYPE.itemsize == 48
+GRID_UNKNOWN, GRID_FREE, GRID_OBSTACLE, GRID_NO_GROUND = 0, 1, 2, 3
+GRID_GROUND_LABELS = (40, 44, 48, 49, 60, 72)  # road, parking, sidewalk, other-ground, lane-marking, terrain
+
+
+class GridParams(C.Structure):
+    """``struct suma_grid_params``: the raster (cell size, origin, width x height) and the rules of core.world_grid;
+    ``GridParams.defaults()`` = suma_grid_params_default"""
+    _fields_ = [("cell_size", f32), ("origin_x", f32), ("origin_y", f32), ("width", u32), ("height", u32),
+                ("ground_label", C.c_uint8 * DRAW_COLORS), ("min_normal_z", f32), ("step_height", f32),
+                ("clearance", f32), ("fill_radius", u32)]
+
+    @classmethod
+    def defaults(cls, cell_size: float = 0.2, origin=(0.0, 0.0), width: int = 0, height: int = 0, ground_labels=None,
+                 min_normal_z: float = 0.7, step_height: float = 0.2, clearance: float = 2.0,
+                 fill_radius: int = 2) -> "GridParams":
+        """``ground_labels``: None (GRID_GROUND_LABELS), or the label ids that count as ground; width = height = 0: to
+        be fitted (core.world_grid does so)"""
+        p = cls(cell_size=cell_size, origin_x=origin[0], origin_y=origin[1], width=width, height=height,
+                min_normal_z=min_normal_z, step_height=step_height, clearance=clearance, fill_radius=fill_radius)
+        for l in (GRID_GROUND_LABELS if ground_labels is None else ground_labels):
+            p.ground_label[int(l)] = 1
+        return p
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "ground_label"}
+        d["ground_labels"] = [l for l in range(DRAW_COLORS) if self.ground_label[l]]
+        return d
+
+
+class GridStats(C.Structure):
+    """``struct suma_grid_stats``: records dropped / outside / binned, cells by state"""
+    _fields_ = [("n_records", u32), ("n_dropped", u32), ("n_outside", u32), ("n_binned", u32), ("n_occupied", u32),
+                ("n_free", u32), ("n_obstacle", u32), ("n_no_ground", u32), ("n_filled", u32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # SurfelMap's constructor (SurfelMap.cpp:195-229): the value each uniform of draw_surfels_ is left with.  Only light 0
 # is used (num_lights = 1); lights 1-4 are the "evenly distributed sun light" it also sets.
 DRAW_LIGHTS = [

@@ -6,9 +6,13 @@ csrc/k_world.hip) and writes it as a binary PLY (semantic_suma_amd/mapio.py).  P
 time of the export alone; --compare also times the host route (getAllSurfels + per-tile downloads + a numpy transform).
 --places FILE adds every scan's frame to a place index (core.PlaceIndex, csrc/k_place.hip) right behind the scan and
 writes it with the final trajectory -- the pose table, i.e. with loop closing the poses after integration -- for
-tools/localize.py --relocalize (semantic_suma_amd/places.py).  Needs a GPU.
+tools/localize.py --relocalize (semantic_suma_amd/places.py).
+--grid FILE.npz also writes the map's 2.5-D traversability grid for a planner (SurfelMap.export_grid, csrc/k_grid.hip;
+mapio.write_grid), --grid-png a picture of its cell states (white unknown, green free, red obstacle, grey no ground);
+with --compare the grid's device time is printed next to a numpy binning of the downloaded records.  Needs a GPU.
     python tools/export_map.py --out map.ply [--scans 40] [--kitti sequences/08] [--voxel 0.2] [--min-confidence 0]
                                [--close-loops] [--width 2048] [--compare] [--places map.places.npz]
+                               [--grid map.grid.npz [--grid-cell 0.2] [--grid-png map.grid.png]]
 """
 import argparse
 import json
@@ -54,6 +58,66 @@ def host_route(smap, max_poses):
     return p.astype(np.float32)
 
 
+GRID_STATE_RGBA = np.array([[255, 255, 255, 255], [60, 170, 80, 255], [200, 40, 40, 255], [128, 128, 128, 255]], np.uint8)
+
+
+def numpy_grid_route(world, gp):
+    """the host route to a grid: the downloaded records binned in numpy -- the cell index, the occupancy and the lowest
+    and highest z per cell only; no vote, no ground rule, no fill.  -> (occupied cells, z_min, z_max per cell)"""
+    fx = np.floor((world["x"] - np.float32(gp.origin_x)) / np.float32(gp.cell_size))
+    fy = np.floor((world["y"] - np.float32(gp.origin_y)) / np.float32(gp.cell_size))
+    ok = np.isfinite(world["z"]) & (fx >= 0) & (fx < gp.width) & (fy >= 0) & (fy < gp.height)
+    c = (fy[ok].astype(np.int64) * gp.width + fx[ok].astype(np.int64))
+    z = world["z"][ok]
+    lo = np.full(gp.width * gp.height, np.inf, np.float32)
+    hi = np.full(gp.width * gp.height, -np.inf, np.float32)
+    np.minimum.at(lo, c, z)
+    np.maximum.at(hi, c, z)
+    return int(np.count_nonzero(np.bincount(c, minlength=gp.width * gp.height))), lo, hi
+
+
+def export_grid(args, pipe, res):
+    """--grid: the grid from the device, its file and picture, the timings"""
+    from draw_map import write_png
+    smap, ctx = pipe.map, pipe.ctx
+    times = []
+    for _ in range(max(1, args.repeat)):
+        t = time.perf_counter()
+        cells, gp, gst = smap.export_grid(cell_size=args.grid_cell, min_confidence=args.min_confidence, fit_margin=1)
+        times.append(time.perf_counter() - t)
+    mapio.write_grid(args.grid, cells, gp)
+    res.update(grid=args.grid, grid_stats=gst, grid_size=[gp.width, gp.height], grid_cell=args.grid_cell,
+               grid_export_wall_ms=[round(1e3 * x, 3) for x in times])
+    if args.grid_png:
+        write_png(args.grid_png, GRID_STATE_RGBA[cells["state"][::-1]])  # row 0 of the picture is the greatest y
+    if args.compare:
+        world = smap.export_world(min_confidence=args.min_confidence)
+        d = ctx.device_array(world)
+        try:
+            wall = []
+            for rep in range(3):  # the last run with the ctx's kernel timers on
+                ctx.profile(rep == 2)
+                ctx.profile_reset()
+                t = time.perf_counter()
+                core.world_grid(ctx, d, len(world), cell_size=args.grid_cell, fit_margin=1)
+                wall.append(round(1e3 * (time.perf_counter() - t), 3))
+            res["grid_kernels_us"] = {k["name"]: round(1e3 * k["total_ms"], 1) for k in ctx.profile_get()
+                                      if k["name"].startswith("grid_")}
+            ctx.profile(0)
+        finally:
+            ctx.device_free(d)
+        res["grid_device_call_wall_ms"] = wall  # fit + grid + the cells' download, from records on the device
+        t = time.perf_counter()
+        world = smap.export_world(min_confidence=args.min_confidence)
+        occupied = numpy_grid_route(world, gp)[0]
+        res["grid_numpy_route_wall_ms"] = round(1e3 * (time.perf_counter() - t), 3)
+        res["grid_numpy_route_occupied"] = occupied
+        t = time.perf_counter()
+        vox, vst = smap.export_world(voxel_size=args.grid_cell, min_confidence=args.min_confidence, stats=True)
+        res["voxel_export_same_cell_wall_ms"] = round(1e3 * (time.perf_counter() - t), 3)
+        res["voxel_export_same_cell_out"] = vst["n_out"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="map.ply")
@@ -67,6 +131,9 @@ def main():
     ap.add_argument("--compare", action="store_true", help="also time the host route")
     ap.add_argument("--places", default=None, help="write a place index of every scan with the final trajectory (.npz)")
     ap.add_argument("--place-range", type=float, default=80.0, help="max_range of the place descriptor in metres")
+    ap.add_argument("--grid", default=None, help="also write the traversability grid (.npz, mapio.write_grid)")
+    ap.add_argument("--grid-cell", type=float, default=0.2, help="cell size of the grid in metres")
+    ap.add_argument("--grid-png", default=None, help="a picture of the grid's cell states")
     args = ap.parse_args()
     p = params_with_size(args.width, 64)
     pipe = core.SurfelMapping(p, loop_params=LoopParams.defaults() if args.close_loops else None)
@@ -92,6 +159,8 @@ def main():
         pts = host_route(smap, p.max_poses)
         res["host_route_wall_ms"] = round(1e3 * (time.perf_counter() - t), 3)
         res["host_route_points"] = int(pts.shape[0])
+    if args.grid:
+        export_grid(args, pipe, res)
     print(json.dumps(res))
 
 
