@@ -282,6 +282,52 @@ inline std::vector<suma_grid_cell> worldGrid(Context& ctx, suma_grid_params& gp,
   return out;
 }
 
+/* Planning on a traversability grid (suma_grid_plan_field): clearance, traversability and the cost-to-go to `goals` (cell
+ * indices; suma_grid_cell_index makes one of a world position) of the gp.width * gp.height cells in `cells`, computed on
+ * the device and returned on the host, row-major like the grid. */
+inline std::vector<suma_plan_cell> planField(Context& ctx, const suma_grid_params& gp, const suma_plan_params& pp,
+                                             const std::vector<suma_grid_cell>& cells, const std::vector<int64_t>& goals,
+                                             suma_plan_stats* stats = nullptr) {
+  if (cells.size() != (size_t)gp.width * gp.height) throw std::runtime_error("planField: cells do not match the raster");
+  std::vector<suma_plan_cell> out(cells.size());
+  suma_plan_stats st;
+  void *d_cells = nullptr, *d_field = nullptr;
+  const uint64_t cell_bytes = (uint64_t)(cells.size() ? cells.size() : 1) * sizeof(suma_grid_cell);
+  check(ctx.get(), suma_device_alloc(ctx.get(), cell_bytes, &d_cells), "planField");
+  int rc = suma_device_alloc(ctx.get(), (uint64_t)(out.size() ? out.size() : 1) * sizeof(suma_plan_cell), &d_field);
+  if (rc == SUMA_OK) rc = suma_device_upload(ctx.get(), d_cells, cells.data(), (uint64_t)cells.size() * sizeof(suma_grid_cell));
+  if (rc == SUMA_OK)
+    rc = suma_grid_plan_field(ctx.get(), &gp, &pp, (const suma_grid_cell*)d_cells, goals.data(), (uint32_t)goals.size(),
+                              (suma_plan_cell*)d_field, &st);
+  if (rc == SUMA_OK) rc = suma_device_download(ctx.get(), out.data(), d_field, (uint64_t)out.size() * sizeof(suma_plan_cell));
+  if (d_field) suma_device_free(ctx.get(), d_field);
+  suma_device_free(ctx.get(), d_cells);
+  check(ctx.get(), rc, "planField");
+  if (stats) *stats = st;
+  return out;
+}
+
+/* The paths from `starts` (cell indices; negative or beyond the raster: SUMA_PATH_START_OUTSIDE) down a field of planField
+ * (suma_grid_plan_paths): one result per start, and in path_cells one row of path_capacity cell indices per start, the
+ * start first, 0xffffffff behind the path's end. */
+inline std::vector<suma_plan_path> planPaths(Context& ctx, const suma_grid_params& gp, const std::vector<suma_plan_cell>& field,
+                                             const std::vector<int64_t>& starts, uint32_t path_capacity,
+                                             std::vector<uint32_t>& path_cells) {
+  if (field.size() != (size_t)gp.width * gp.height) throw std::runtime_error("planPaths: the field does not match the raster");
+  std::vector<suma_plan_path> out(starts.size());
+  path_cells.assign(starts.size() * (size_t)path_capacity, 0xffffffffu);
+  void* d_field = nullptr;
+  check(ctx.get(), suma_device_alloc(ctx.get(), (uint64_t)(field.size() ? field.size() : 1) * sizeof(suma_plan_cell), &d_field),
+        "planPaths");
+  int rc = suma_device_upload(ctx.get(), d_field, field.data(), (uint64_t)field.size() * sizeof(suma_plan_cell));
+  if (rc == SUMA_OK)
+    rc = suma_grid_plan_paths(ctx.get(), &gp, (const suma_plan_cell*)d_field, starts.data(), (uint32_t)starts.size(), path_capacity,
+                              path_cells.data(), out.data());
+  suma_device_free(ctx.get(), d_field);
+  check(ctx.get(), rc, "planPaths");
+  return out;
+}
+
 /* src/core/SurfelMap.h:36-78 (draw / setColorMap are visualisation and stay with the GL code) */
 class SurfelMap {
  public:

@@ -591,6 +591,82 @@ int suma_world_grid_fit(suma_ctx* ctx, const suma_world_surfel* d_records, uint3
 int suma_world_grid(suma_ctx* ctx, const suma_grid_params* gp, const suma_world_surfel* d_records, uint32_t n,
                     suma_grid_cell* d_cells, suma_grid_stats* stats);
 
+/* ---- planning on the traversability grid: per cell the clearance to the nearest blocked cell, whether a robot of a given
+ *      radius may stand there, the cost-to-go to a set of goal cells and the direction of the cheapest way, and paths read
+ *      off that field (k_plan.hip states the specification; tests/plan_shim.c restates it on the host, and the field and the
+ *      paths equal it byte for byte).  Every quantity is an integer or one fp32 comparison. */
+#define SUMA_PLAN_MAX_CLEAR_CELLS 64u
+#define SUMA_PLAN_MAX_GOALS 4096u
+#define SUMA_PLAN_MAX_STARTS 4096u
+#define SUMA_PLAN_UNREACHED 0xffffffffu /* the cost of a cell no goal is reached from */
+
+typedef struct suma_plan_params {
+  float robot_radius;       /* metres; default 0.4; finite, 0 <= robot_radius <= max_clear_cells * cell_size */
+  float max_step;           /* default 0.15: a move needs |ground_z(c) - ground_z(n)| <= max_step; not NaN */
+  float max_rough;          /* default NaN = off: a cell with ground_rough > max_rough is blocked */
+  uint32_t unknown_blocked; /* default 1; 0 or 1: an UNKNOWN cell is blocked */
+  uint32_t max_clear_cells; /* R, default 16; 1 .. 64: the clearance is exact below (R + 1)^2 and capped there */
+  uint32_t soft_cells;      /* default 3; 0 .. R + 1: cells nearer than this to a blocked cell cost more */
+  uint32_t soft_weight;     /* default 2; 0 .. 255: by this much per cell of missing distance */
+  uint8_t label_cost[SUMA_DRAW_COLORS]; /* default all 1: the cost of standing on a label; 0 = forbidden (blocked) */
+} suma_plan_params;
+
+/* direction k of a move, as (dx, dy); the row index grows with y:
+ *   0 E (1, 0), 1 NE (1, 1), 2 N (0, 1), 3 NW (-1, 1), 4 W (-1, 0), 5 SW (-1, -1), 6 S (0, -1), 7 SE (1, -1) */
+enum { SUMA_PLAN_E = 0, SUMA_PLAN_NE, SUMA_PLAN_N, SUMA_PLAN_NW, SUMA_PLAN_W, SUMA_PLAN_SW, SUMA_PLAN_S, SUMA_PLAN_SE,
+       SUMA_PLAN_AT_GOAL = 8, SUMA_PLAN_NO_DIRECTION = 255 };
+enum { SUMA_PLAN_BLOCKED = 1, SUMA_PLAN_TRAVERSABLE = 2, SUMA_PLAN_REACHED = 4 }; /* bits of suma_plan_cell.flags */
+
+typedef struct suma_plan_cell { /* 8 bytes */
+  uint32_t cost;   /* cost-to-go to the nearest goal; SUMA_PLAN_UNREACHED */
+  uint16_t clear2; /* squared distance in cells to the nearest blocked cell, capped at (R + 1)^2; 0 on a blocked cell */
+  uint8_t flags;   /* SUMA_PLAN_BLOCKED | SUMA_PLAN_TRAVERSABLE | SUMA_PLAN_REACHED */
+  uint8_t next;    /* the direction of the cheapest move; 8 at a goal, 255 where unreached */
+} suma_plan_cell;
+
+typedef struct suma_plan_stats {
+  uint32_t n_blocked, n_traversable, n_reached;
+  uint32_t n_goals, n_goals_ignored; /* goal entries given / of these not traversable (a cell given twice counts twice) */
+  uint32_t max_cost;                 /* the largest finite cost; 0 when nothing is reached */
+  uint32_t n_rounds;                 /* diagnostic: relaxation rounds launched until one changed nothing */
+} suma_plan_stats;
+
+enum { SUMA_PATH_OK = 0, SUMA_PATH_UNREACHED = 1, SUMA_PATH_START_OUTSIDE = 2, SUMA_PATH_TRUNCATED = 3, SUMA_PATH_BAD_FIELD = 4 };
+
+typedef struct suma_plan_path { /* 16 bytes: the result for one start */
+  uint32_t length; /* cells on the path, the start and the goal included (the full length, also when TRUNCATED);
+                      0 for UNREACHED / START_OUTSIDE; for BAD_FIELD the cells visited before the bad step */
+  uint32_t status; /* SUMA_PATH_* */
+  uint32_t cost;   /* the field's cost at the start; SUMA_PLAN_UNREACHED for START_OUTSIDE */
+  uint32_t pad;    /* 0 */
+} suma_plan_path;
+
+/* the defaults above */
+void suma_plan_params_default(suma_plan_params* pp);
+/* Host only: the cell of a world position in the grid's own fp32 expression, iy * width + ix with
+ *   ix = floorf((x - origin_x) / cell_size), iy likewise; -1 outside the raster, for a non-finite x or y, and for a NULL gp.
+ *   How a goal or a start given in world coordinates becomes a cell. */
+int64_t suma_grid_cell_index(const suma_grid_params* gp, float x, float y);
+/* Both entries run on the ctx stream, use scratch of the ctx grown by its one rule, and write only that scratch and the
+ *   caller's output: the grid cells, the map and every counter of the ctx stay as they are.  Of gp only width, height and
+ *   cell_size are read (the ranges of suma_world_grid).  SUMA_ERR_INVALID with a message, and nothing launched or written:
+ *   a NULL argument, a misaligned device pointer (d_cells 16 bytes, d_field 8), a count of 0 or above 4096, and any
+ *   parameter outside the ranges stated at suma_plan_params.
+ * suma_grid_plan_field: d_cells = the width * height cells suma_world_grid wrote (device); goals = n_goals cell indices on
+ *   the host, each 0 <= g < width * height (SUMA_ERR_INVALID otherwise); a goal that is not traversable is ignored and
+ *   counted.  d_field = width * height suma_plan_cell (device), row-major like the grid; every cell is written.
+ *   SUMA_ERR_CAPACITY when width * height * 28 * (255 + soft_weight * soft_cells) >= 2^32: a cost could wrap.
+ *   Blocks once per batch of relaxation rounds, for one word.  Scratch: 21 bytes a cell.
+ * suma_grid_plan_paths: d_field = a field (device; the walk does not trust it); starts = n_starts cell indices on the
+ *   host (a negative one, or one beyond the raster: START_OUTSIDE); path_capacity = 1 .. 2^20 cells per path, n_starts *
+ *   path_capacity <= 2^26.  path_cells (host) = n_starts rows of path_capacity cell indices, the start first; entries
+ *   behind min(length, path_capacity) are 0xffffffff.  results (host) = n_starts records.  The paths are made in scratch
+ *   of the ctx and come back with one blocking read. */
+int suma_grid_plan_field(suma_ctx* ctx, const suma_grid_params* gp, const suma_plan_params* pp, const suma_grid_cell* d_cells,
+                         const int64_t* goals, uint32_t n_goals, suma_plan_cell* d_field, suma_plan_stats* stats);
+int suma_grid_plan_paths(suma_ctx* ctx, const suma_grid_params* gp, const suma_plan_cell* d_field, const int64_t* starts,
+                         uint32_t n_starts, uint32_t path_capacity, uint32_t* path_cells, suma_plan_path* results);
+
 /* ---- device scratch for callers that keep scans resident in HBM (bench, replay) */
 int suma_device_alloc(suma_ctx* ctx, uint64_t bytes, void** d_ptr);
 int suma_device_free(suma_ctx* ctx, void* d_ptr);

@@ -33,6 +33,7 @@ from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX
                     IcpStats, LoopParams, LoopStatus, PosegraphParams, PosegraphStats, SemanticKnnParams,
                     SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats, CheckpointInfo,
                     GRID_CELL_DTYPE, GridParams, GridStats,
+                    PLAN_CELL_DTYPE, PLAN_PATH_DTYPE, PATH_OK, PATH_TRUNCATED, PlanParams, PlanStats,
                     ChangeCounts, ChangeParams, ChangeRule, DeskewParams, EVIDENCE_DTYPE, NovelCounts, NovelFuseParams, NovelParams, NovelStats, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -257,6 +258,12 @@ def lib():
     L.suma_grid_params_default.restype = None
     L.suma_world_grid_fit.argtypes = [vp, vp, u32, u32, C.POINTER(GridParams)]
     L.suma_world_grid.argtypes = [vp, C.POINTER(GridParams), vp, u32, vp, C.POINTER(GridStats)]
+    L.suma_plan_params_default.argtypes = [C.POINTER(PlanParams)]
+    L.suma_plan_params_default.restype = None
+    L.suma_grid_cell_index.argtypes = [C.POINTER(GridParams), C.c_float, C.c_float]
+    L.suma_grid_cell_index.restype = C.c_int64
+    L.suma_grid_plan_field.argtypes = [vp, C.POINTER(GridParams), C.POINTER(PlanParams), vp, vp, u32, vp, C.POINTER(PlanStats)]
+    L.suma_grid_plan_paths.argtypes = [vp, C.POINTER(GridParams), vp, vp, u32, u32, vp, vp]
     L.suma_device_alloc.argtypes = [vp, C.c_uint64, pp]
     L.suma_device_free.argtypes = [vp, vp]
     L.suma_device_upload.argtypes = [vp, vp, vp, C.c_uint64]
@@ -798,6 +805,150 @@ def world_grid(ctx: "Context", records, n: int = None, params: GridParams = None
         if owned:
             L.suma_device_free(h, C.c_void_p(owned))
     return cells, gp, st.as_dict()
+
+
+def grid_cell_index(gp: GridParams, x: float, y: float) -> int:
+    """the cell iy * width + ix of a world position in the grid's own fp32 expression (suma_grid_cell_index); -1 outside
+    the raster or for a non-finite coordinate"""
+    return int(lib().suma_grid_cell_index(C.byref(gp), float(x), float(y)))
+
+
+def _cell_indices(v, what: str) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.int64).reshape(-1))
+    if a.size == 0:
+        raise ValueError(f"{what}: no cell given")
+    return a
+
+
+def grid_plan(ctx: "Context", cells, gp: GridParams, goals, params: PlanParams = None, field_out=None, **kw):
+    """Clearance, traversability and the cost-to-go field of a traversability grid (suma_grid_plan_field; csrc/k_plan.hip
+    states the rules): -> (field[height, width] of PLAN_CELL_DTYPE, the stats as a dict).  ``cells``: the GRID_CELL_DTYPE
+    array of core.world_grid (uploaded for the call), or a device address / torch tensor of gp.width * gp.height cells.
+    ``goals``: cell indices (grid_cell_index makes one of a world position).  ``params``: a PlanParams, or the keywords
+    of PlanParams.defaults.  ``field_out``: a device address to leave the field at; the return is then (None, stats)."""
+    pp = PlanParams.defaults(**kw) if params is None else PlanParams.from_buffer_copy(params)
+    g = _cell_indices(goals, "grid_plan")
+    L, h = ctx.L, ctx.h
+    n_cells = int(gp.width) * int(gp.height)
+    owned, d_field = None, C.c_void_p()
+    if isinstance(cells, np.ndarray):
+        arr = np.ascontiguousarray(cells, dtype=GRID_CELL_DTYPE).reshape(-1)
+        if arr.shape[0] != n_cells:
+            raise ValueError(f"grid_plan: {arr.shape[0]} cells against a raster of {gp.height} x {gp.width}")
+        cells = owned = ctx.device_array(arr)
+    st = PlanStats()
+    try:
+        if field_out is None:
+            ctx.check(L.suma_device_alloc(h, n_cells * PLAN_CELL_DTYPE.itemsize, C.byref(d_field)), "suma_device_alloc")
+        ctx.check(L.suma_grid_plan_field(h, C.byref(gp), C.byref(pp), _dev(cells), _ptr(g), g.shape[0],
+                                         d_field if field_out is None else _dev(field_out), C.byref(st)), "suma_grid_plan_field")
+        field = None
+        if field_out is None:
+            field = np.zeros((gp.height, gp.width), dtype=PLAN_CELL_DTYPE)
+            ctx.check(L.suma_device_download(h, _ptr(field), d_field, field.nbytes), "suma_device_download")
+    finally:
+        if d_field:
+            L.suma_device_free(h, d_field)
+        if owned:
+            L.suma_device_free(h, C.c_void_p(owned))
+    return field, st.as_dict()
+
+
+def grid_paths(ctx: "Context", field, gp: GridParams, starts, capacity: int = None):
+    """The paths from ``starts`` (cell indices; negative or beyond the raster: START_OUTSIDE) down a field of grid_plan
+    (suma_grid_plan_paths): -> (results of PLAN_PATH_DTYPE [n], path cells uint32 [n, capacity], the start first, 0xffffffff
+    behind a path's end).  ``field``: the PLAN_CELL_DTYPE array (uploaded for the call) or a device address / torch
+    tensor.  ``capacity``: cells of room per path, default width + height (a path longer than that is TRUNCATED and
+    reports its full length)."""
+    s = _cell_indices(starts, "grid_paths")
+    L, h = ctx.L, ctx.h
+    capacity = int(gp.width) + int(gp.height) if capacity is None else int(capacity)
+    owned = None
+    if isinstance(field, np.ndarray):
+        arr = np.ascontiguousarray(field, dtype=PLAN_CELL_DTYPE).reshape(-1)
+        if arr.shape[0] != int(gp.width) * int(gp.height):
+            raise ValueError(f"grid_paths: {arr.shape[0]} cells against a raster of {gp.height} x {gp.width}")
+        field = owned = ctx.device_array(arr)
+    results = np.zeros(s.shape[0], dtype=PLAN_PATH_DTYPE)
+    path_cells = np.zeros((s.shape[0], max(capacity, 0)), dtype=np.uint32)
+    try:
+        ctx.check(L.suma_grid_plan_paths(h, C.byref(gp), _dev(field), _ptr(s), s.shape[0], max(capacity, 0), _ptr(path_cells),
+                                         _ptr(results)), "suma_grid_plan_paths")
+    finally:
+        if owned:
+            L.suma_device_free(h, C.c_void_p(owned))
+    return results, path_cells
+
+
+class GridPlanner:
+    """A traversability grid and its cost-to-go field kept on the device: goals and starts are world (x, y), a path comes
+    back as the world coordinates of its cells' centres with its cost.
+
+        planner = GridPlanner(ctx, cells, gp, robot_radius=0.4)
+        stats = planner.set_goals([(x, y)])
+        xy, cost, status = planner.path((x0, y0))"""
+
+    def __init__(self, ctx: "Context", cells: np.ndarray, gp: GridParams, params: PlanParams = None, **kw):
+        self.ctx, self.gp = ctx, GridParams.from_buffer_copy(gp)
+        self.params = PlanParams.defaults(**kw) if params is None else PlanParams.from_buffer_copy(params)
+        arr = np.ascontiguousarray(cells, dtype=GRID_CELL_DTYPE).reshape(-1)
+        if arr.shape[0] != int(gp.width) * int(gp.height):
+            raise ValueError(f"GridPlanner: {arr.shape[0]} cells against a raster of {gp.height} x {gp.width}")
+        self._cells = ctx.device_array(arr)
+        self._field = ctx.device_array(np.zeros(arr.shape[0], dtype=PLAN_CELL_DTYPE))
+        self.stats = None
+
+    def close(self):
+        for name in ("_cells", "_field"):
+            if getattr(self, name, None):
+                self.ctx.device_free(getattr(self, name))
+                setattr(self, name, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def cell(self, xy) -> int:
+        return grid_cell_index(self.gp, xy[0], xy[1])
+
+    def centre(self, cells) -> np.ndarray:
+        """world (x, y) of the centres of cells given by index: float64 [n, 2]"""
+        c = np.asarray(cells, dtype=np.int64).reshape(-1)
+        ix, iy = c % self.gp.width, c // self.gp.width
+        return np.stack([self.gp.origin_x + (ix + 0.5) * self.gp.cell_size, self.gp.origin_y + (iy + 0.5) * self.gp.cell_size], axis=1)
+
+    def set_goals(self, goals_xy) -> dict:
+        """the field towards these world positions; one outside the raster is an error.  -> the stats"""
+        g = [self.cell(xy) for xy in np.asarray(goals_xy, dtype=np.float64).reshape(-1, 2)]
+        if min(g) < 0:
+            raise ValueError("GridPlanner.set_goals: a goal lies outside the raster")
+        _, self.stats = grid_plan(self.ctx, self._cells, self.gp, g, self.params, field_out=self._field)
+        return self.stats
+
+    def field(self) -> np.ndarray:
+        """the field [height, width] of PLAN_CELL_DTYPE, downloaded"""
+        if self.stats is None:
+            raise SumaError("GridPlanner.field: no goals set")
+        n = int(self.gp.width) * int(self.gp.height) * PLAN_CELL_DTYPE.itemsize
+        return self.ctx.device_download(self._field, n).view(PLAN_CELL_DTYPE).reshape(self.gp.height, self.gp.width)
+
+    def paths(self, starts_xy, capacity: int = None):
+        """-> a list of (xy float64 [length, 2], cost, status) per start; xy is empty unless the status is PATH_OK or
+        PATH_TRUNCATED (then it holds the first ``capacity`` cells)"""
+        if self.stats is None:
+            raise SumaError("GridPlanner.paths: no goals set")
+        s = [self.cell(xy) for xy in np.asarray(starts_xy, dtype=np.float64).reshape(-1, 2)]
+        res, cells = grid_paths(self.ctx, self._field, self.gp, s, capacity)
+        out = []
+        for r, row in zip(res, cells):
+            keep = min(int(r["length"]), row.shape[0]) if int(r["status"]) in (PATH_OK, PATH_TRUNCATED) else 0
+            out.append((self.centre(row[:keep]), int(r["cost"]), int(r["status"])))
+        return out
+
+    def path(self, start_xy, capacity: int = None):
+        return self.paths([start_xy], capacity)[0]
 
 
 class SurfelMap:

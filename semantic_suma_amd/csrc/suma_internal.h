@@ -253,6 +253,11 @@ struct suma_ctx {
   DevBuf<uint4> grid_runs;
   DevBuf<uint32_t> grid_counters;
   PinnedBuf<uint32_t> grid_counters_h;
+  /* suma_grid_plan_field / _paths (k_plan.hip), allocated on first use: PLAN_SCRATCH_PER_CELL bytes a raster cell, the
+   * counters and round flags, and the goals / starts / paths exchanged with the host (words; pinned on the way in) */
+  DevBuf<char> plan_scratch;
+  DevBuf<uint32_t> plan_counters, plan_io;
+  PinnedBuf<uint32_t> plan_counters_h, plan_io_h;
   /* suma_pipeline_checkpoint_save / _load (k_checkpoint.hip), allocated on first use: the staged image, the span table
    * of kc_pack and one digest word per section */
   DevBuf<char> ckpt_image;
@@ -575,6 +580,25 @@ hipError_t launch_grid(suma_ctx* c, const suma_grid_params& gp, const suma_world
  * MIN_X stays 0xffffffff when there is none */
 hipError_t launch_grid_fit(suma_ctx* c, const suma_world_surfel* d_records, uint32_t n);
 float grid_ordered_float(uint32_t o);
+
+/* k_plan.hip (the specification is there): clearance, cost-to-go field and paths on the traversability grid.  All enqueue
+ * on c->stream; only launch_plan_relax waits, once per batch of rounds, for the batch's flags. */
+enum { PLAN_BLOCKED = 0, PLAN_TRAVERSABLE, PLAN_REACHED, PLAN_GOALS_IGNORED, PLAN_MAX_COST, PLAN_ROUND_FLAGS = 8,
+       PLAN_ROUND_BATCH = 8, PLAN_COUNTERS = 16 };
+#define PLAN_TILE 32u /* the relaxation's tile: PLAN_TILE x PLAN_TILE cells a block, one cell of halo */
+#define PLAN_SCRATCH_PER_CELL 21u
+/* bytes of c->plan_scratch for a raster: PLAN_SCRATCH_PER_CELL a cell (each array 16-byte aligned) and two flags a tile */
+size_t plan_scratch_bytes(uint32_t width, uint32_t height);
+/* classify, clearance, edges, goals (c->plan_io holds n_goals cell indices): everything in front of the relaxation;
+ * zeroes c->plan_counters (PLAN_COUNTERS words) and starts every cell of d_field */
+hipError_t launch_plan_prepare(suma_ctx* c, const suma_grid_params& gp, const suma_plan_params& pp, const suma_grid_cell* d_cells,
+                               uint32_t n_goals, suma_plan_cell* d_field);
+/* rounds until one changes nothing; SUMA_OK, SUMA_ERR_HIP, or SUMA_ERR_CAPACITY at the bound of width * height rounds */
+int launch_plan_relax(suma_ctx* c, const suma_grid_params& gp, uint32_t* n_rounds);
+hipError_t launch_plan_next(suma_ctx* c, const suma_grid_params& gp, suma_plan_cell* d_field);
+/* c->plan_io: 4 words a result, then the n_starts cell indices (0xffffffff: outside), then n_starts * capacity path cells */
+hipError_t launch_plan_walk(suma_ctx* c, const suma_grid_params& gp, const suma_plan_cell* d_field, uint32_t n_starts,
+                            uint32_t capacity);
 
 /* k_localize.hip (the specification is there): the world map binned into submap tiles, and the window gather */
 struct LocTile { /* one occupied tile of the directory, ascending by key */

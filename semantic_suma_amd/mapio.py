@@ -7,13 +7,18 @@ and core.world_grid's traversability grid as one .npz:
 
     write_grid(path, cells, params)                  the cells [height, width] and the GridParams that made them
     read_grid(path) -> (cells, params)
+
+and core.grid_plan's field beside it:
+
+    write_plan(path, field, grid_params, plan_params)   the field [height, width] and both parameter structs
+    read_plan(path) -> (field, grid_params, plan_params)
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import kitti
-from .types import GRID_CELL_DTYPE, WORLD_SURFEL_DTYPE, GridParams
+from .types import GRID_CELL_DTYPE, PLAN_CELL_DTYPE, WORLD_SURFEL_DTYPE, GridParams, PlanParams
 
 # the PLY vertex: name, PLY type, numpy type
 _PLY_FIELDS = [("x", "float", "<f4"), ("y", "float", "<f4"), ("z", "float", "<f4"),
@@ -113,3 +118,32 @@ def read_grid(path: str):
     if raw.shape[:2] != (gp.height, gp.width):
         raise ValueError(f"{path}: cells {raw.shape[:2]} against a raster of {gp.height} x {gp.width}")
     return np.ascontiguousarray(raw).view(GRID_CELL_DTYPE).reshape(gp.height, gp.width), gp
+
+
+def write_plan(path: str, field: np.ndarray, grid_params: GridParams, plan_params: PlanParams) -> None:
+    """``field``: PLAN_CELL_DTYPE [height, width] as core.grid_plan returns it, with the GridParams of the grid it was
+    planned on and the PlanParams of that call.  ``path`` is written as given (end it in .npz)."""
+    f_ = np.ascontiguousarray(field, dtype=PLAN_CELL_DTYPE)
+    if f_.shape != (grid_params.height, grid_params.width):
+        raise ValueError(f"write_plan: field {f_.shape} against a raster of {grid_params.height} x {grid_params.width}")
+    with open(path, "wb") as f:
+        np.savez_compressed(f, field=f_.view(np.uint8).reshape(f_.shape + (PLAN_CELL_DTYPE.itemsize,)),
+                            params=np.frombuffer(bytes(grid_params), dtype=np.uint8),
+                            plan_params=np.frombuffer(bytes(plan_params), dtype=np.uint8))
+
+
+def read_plan(path: str):
+    """-> (PLAN_CELL_DTYPE field [height, width], GridParams, PlanParams) of a file write_plan made"""
+    with np.load(path) as z:
+        if not {"field", "params", "plan_params"} <= set(z.files):
+            raise ValueError(f"{path}: not a plan file")
+        raw, par, ppar = z["field"], z["params"], z["plan_params"]
+    if par.dtype != np.uint8 or par.size != len(bytes(GridParams())) or ppar.dtype != np.uint8 or \
+            ppar.size != len(bytes(PlanParams())) or raw.dtype != np.uint8 or raw.ndim != 3 or \
+            raw.shape[2] != PLAN_CELL_DTYPE.itemsize:
+        raise ValueError(f"{path}: not a plan file")
+    gp = GridParams.from_buffer_copy(par.tobytes())
+    if raw.shape[:2] != (gp.height, gp.width):
+        raise ValueError(f"{path}: field {raw.shape[:2]} against a raster of {gp.height} x {gp.width}")
+    return (np.ascontiguousarray(raw).view(PLAN_CELL_DTYPE).reshape(gp.height, gp.width), gp,
+            PlanParams.from_buffer_copy(ppar.tobytes()))

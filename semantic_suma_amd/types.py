@@ -170,6 +170,61 @@ class GridStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# numpy view of the 8-byte cell of the planner's field (``struct suma_plan_cell``, core.grid_plan)
+PLAN_CELL_DTYPE = np.dtype([("cost", "<u4"), ("clear2", "<u2"), ("flags", "u1"), ("next", "u1")])
+assert PLAN_CELL_DTYPE.itemsize == 8
+# the result for one start of core.grid_paths (``struct suma_plan_path``)
+PLAN_PATH_DTYPE = np.dtype([("length", "<u4"), ("status", "<u4"), ("cost", "<u4"), ("pad", "<u4")])
+PLAN_UNREACHED = 0xffffffff
+PLAN_MAX_CLEAR_CELLS, PLAN_MAX_GOALS, PLAN_MAX_STARTS = 64, 4096, 4096
+# direction k of a move as (dx, dy): E, NE, N, NW, W, SW, S, SE; the row index grows with y
+PLAN_DIRECTIONS = ((1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1))
+PLAN_AT_GOAL, PLAN_NO_DIRECTION = 8, 255
+PLAN_BLOCKED, PLAN_TRAVERSABLE, PLAN_REACHED = 1, 2, 4  # bits of the cell's flags
+PATH_OK, PATH_UNREACHED, PATH_START_OUTSIDE, PATH_TRUNCATED, PATH_BAD_FIELD = 0, 1, 2, 3, 4
+PATH_STATUS_NAMES = ("OK", "UNREACHED", "START_OUTSIDE", "TRUNCATED", "BAD_FIELD")
+
+
+class PlanParams(C.Structure):
+    """``struct suma_plan_params``: the robot (radius, step, roughness), the clearance window and the costs of
+    core.grid_plan; ``PlanParams.defaults()`` = suma_plan_params_default"""
+    _fields_ = [("robot_radius", f32), ("max_step", f32), ("max_rough", f32), ("unknown_blocked", u32),
+                ("max_clear_cells", u32), ("soft_cells", u32), ("soft_weight", u32), ("label_cost", C.c_uint8 * DRAW_COLORS)]
+
+    @classmethod
+    def defaults(cls, robot_radius: float = 0.4, max_step: float = 0.15, max_rough: float = float("nan"),
+                 unknown_blocked: bool = True, max_clear_cells: int = 16, soft_cells: int = 3, soft_weight: int = 2,
+                 label_cost=None) -> "PlanParams":
+        """``label_cost``: None (all 1), a dict label -> cost over a base of 1, or 260 values; 0 = forbidden"""
+        p = cls(robot_radius=robot_radius, max_step=max_step, max_rough=max_rough, unknown_blocked=int(bool(unknown_blocked)),
+                max_clear_cells=max_clear_cells, soft_cells=soft_cells, soft_weight=soft_weight)
+        cost = [1] * DRAW_COLORS
+        if isinstance(label_cost, dict):
+            for l, v in label_cost.items():
+                cost[int(l)] = int(v)
+        elif label_cost is not None:
+            cost = [int(v) for v in label_cost]
+            if len(cost) != DRAW_COLORS:
+                raise ValueError(f"label_cost: {len(cost)} values, {DRAW_COLORS} wanted")
+        for l in range(DRAW_COLORS):
+            p.label_cost[l] = cost[l]
+        return p
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "label_cost"}
+        d["label_cost"] = {l: self.label_cost[l] for l in range(DRAW_COLORS) if self.label_cost[l] != 1}
+        return d
+
+
+class PlanStats(C.Structure):
+    """``struct suma_plan_stats``: cells blocked / traversable / reached, goals given / ignored, the largest cost, rounds"""
+    _fields_ = [("n_blocked", u32), ("n_traversable", u32), ("n_reached", u32), ("n_goals", u32), ("n_goals_ignored", u32),
+                ("max_cost", u32), ("n_rounds", u32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # SurfelMap's constructor (SurfelMap.cpp:195-229): the value each uniform of draw_surfels_ is left with.  Only light 0
 # is used (num_lights = 1); lights 1-4 are the "evenly distributed sun light" it also sets.
 DRAW_LIGHTS = [
