@@ -115,6 +115,8 @@ def lib(variant: str = ""):
     L.ora_map_last_extraction.argtypes = [vp, vp]
     L.ora_debug_render_quads.argtypes = [vp, vp, C.c_float, C.c_int, C.c_int32, vp, vp, vp]
     L.ora_debug_update_terms.argtypes = [vp, vp, C.c_uint32, vp, vp, vp]
+    L.ora_debug_preprocess_point_terms.argtypes = [vp, vp, C.c_uint32, vp]
+    L.ora_debug_preprocess_map_terms.argtypes = [vp, vp, vp]
     L.ora_debug_raster_quads.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_uint32, C.c_int, C.c_int, vp]
     L.ora_debug_depth24.argtypes = [vp, C.c_uint32, vp]
     L.ora_pipeline_create.restype = vp
@@ -374,6 +376,21 @@ class Oracle:
         terms = np.full((max(n, 1), 6), np.nan, dtype=np.float32)
         self.L.ora_debug_update_terms(self.h, _ptr(rec), n, _ptr(po), frame.h, _ptr(terms))
         return terms[:n]
+
+    def debug_preprocess_point_terms(self, points):
+        """the fp32 terms K1 compares, per point (oracle/debug/o_preprocess_terms.c): [n, 3] = the texel coordinates
+        before the floor, the window depth before the 24-bit rounding"""
+        points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
+        terms = np.full((max(points.shape[0], 1), 3), np.nan, dtype=np.float32)
+        self.L.ora_debug_preprocess_point_terms(self.h, _ptr(points), points.shape[0], _ptr(terms))
+        return terms[:points.shape[0]]
+
+    def debug_preprocess_map_terms(self, vertex):
+        """the fp32 terms K2 / K3 compare, per texel of a vertex map: [H, W, 2] = |un x vn|, |xyz|"""
+        vertex = np.ascontiguousarray(vertex, dtype=np.float32)
+        terms = np.full(vertex.shape[:2] + (2,), np.nan, dtype=np.float32)
+        self.L.ora_debug_preprocess_map_terms(self.h, _ptr(vertex), _ptr(terms))
+        return terms
 
     def debug_raster_quads(self, W, H, corners, ids, use_disc=True, use_depth=True):
         """the triangle rasteriser alone on given quads ([n, 4, 3] corners in [0,1]^3): winner id per pixel, -1 = none"""

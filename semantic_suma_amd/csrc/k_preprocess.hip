@@ -95,10 +95,11 @@ __global__ void __launch_bounds__(PRE_TX* PRE_TY)
   for (int t = tid; t < PRE_SW * PRE_SH; t += PRE_TX * PRE_TY) {
     const int ly = t / PRE_SW, lx = t - ly * PRE_SW;
     int32_t gx = x0 + lx - PRE_H3, gy = y0 + ly - PRE_H3;
-    if (gx >= W) gx -= W; /* gen_normalmap.frag:24-32 wrap() */
-    if (gx < 0) gx += W;
-    /* a patch that overhangs the right image edge (W not a multiple of the tile) may wrap twice */
-    if (gx >= W) gx -= W;
+    /* gen_normalmap.frag:24-32 wrap(): a loop, as there.  A patch that overhangs the right image edge (W not a
+     * multiple of the tile) wraps more than once, and an image narrower than tile + halo wraps many times; the
+     * index below is inside the row for every W > 0 */
+    while (gx >= W) gx -= W;
+    while (gx < 0) gx += W;
     float4 v = f4(0.f, 0.f, 0.f, 0.f), s = v;
     if (gy >= 0 && gy < H) {
       v = V[(size_t)gy * W + gx];
