@@ -28,10 +28,7 @@
 #include <cstring>
 
 #include "suma_internal.h"
-#define EXDIV_FN __device__ __forceinline__
-#include "exact_div.h"
-
-enum { TIE_LOW_INDEX = 0, TIE_HIGH_INDEX_OLD = 1, TIE_HIGH_INDEX_NEW = 2 };
+#include "raster_quad.h"
 
 struct RenderSlot {
   int enabled;
@@ -62,82 +59,6 @@ struct RenderArgs {
   proj_t k7_q;
   unsigned long long* k7_zbuf;
 };
-
-struct rvtx {
-  int32_t X, Y; /* window coordinates in 1/256 pixel (|X| < 2^21: 20 bits of image + seam unwrap) */
-  float z, tu, tv;
-};
-
-/* Edge function of the directed edge a->b at point (px, py): an exact integer below 2^47 in magnitude (the four
- * differences are below 2^23).  Formed in binary64: each product of two such integers is exact (46 bits), and the fused
- * multiply-add delivers their exact difference (representable, so its one rounding rounds nothing) -- the same integer
- * the 64-bit form (b.X - a.X) * (py - a.Y) - (b.Y - a.Y) * (px - a.X) computes, as a double.  Why: the 64-bit form costs
- * two 32 x 32 -> 64-bit multiplies, add-with-carry pairs and 64-bit compares per edge, and its conversion to float is a
- * dozen instructions (count leading zeros, shifts, rounding) where v_cvt_f32_f64 is one; binary64 issues at the ordinary
- * VALU rate on gfx950 (profiles/r05_instr_rate_gfx950.txt).  Per pair of pixel tests 831 -> 684 VALU instructions; the
- * pass is 5 % faster where it is issue-bound (50 M surfels) and unchanged at the steady 1 M map
- * (profiles/r05_second_session_experiments.txt).  The one value the integer form cannot produce is -0 (two zero products
- * of unlike sign): comparisons do not see it, and edge_to_float() turns it into the +0 an integer 0 converts to. */
-__device__ __forceinline__ double edge_fn(const rvtx& a, const rvtx& b, int32_t px, int32_t py) {
-  const double ux = (double)(b.X - a.X), uy = (double)(b.Y - a.Y), vx = (double)(px - a.X), vy = (double)(py - a.Y);
-  return __builtin_fma(ux, vy, -(uy * vx));
-}
-__device__ __forceinline__ float edge_to_float(double w) { return (float)(w + 0.0); } /* (float)(long long): -0 -> +0 */
-/* ownership of a pixel centre exactly on an edge: antisymmetric in the edge direction, so a
- * pixel on the diagonal shared by the two strip triangles is produced exactly once */
-__device__ __forceinline__ bool owns_edge(const rvtx& s, const rvtx& t) {
-  int32_t dx = t.X - s.X, dy = t.Y - s.Y;
-  return dy > 0 || (dy == 0 && dx < 0);
-}
-
-__device__ __forceinline__ unsigned long long render_key(uint32_t z24, uint32_t id, int tie) {
-  /* GL_LESS, in order: equal depth keeps the earlier primitive (lower id).  GL_LEQUAL
-   * (render_composed, SurfelMap.cpp:1126): equal depth takes the later primitive, and the "new"
-   * pass is drawn after the "old" pass into the same depth buffer. */
-  if (tie == TIE_LOW_INDEX) return ((unsigned long long)z24 << 32) | id;
-  unsigned long long pass = (tie == TIE_HIGH_INDEX_OLD) ? 1u : 0u;
-  return ((unsigned long long)z24 << 33) | (pass << 32) | (unsigned long long)(0xffffffffu - id);
-}
-
-/* One triangle at one pixel centre: coverage (top-left style ownership rule), affine interpolation
- * of depth and disc coordinates, disc + near/far tests.  Returns the z-buffer key of the fragment or
- * SUMA_EMPTY_KEY if the triangle produces none.  Every quantity is a function of the triangle and the
- * pixel only, so the work can be distributed freely over lanes. */
-__device__ __forceinline__ unsigned long long raster_key(rvtx A, rvtx B, rvtx C, int32_t i, int32_t j, uint32_t id,
-                                                         int tie) {
-  double area = edge_fn(A, B, C.X, C.Y);
-  if (area < 0) {
-    rvtx t = B;
-    B = C;
-    C = t;
-    area = -area;
-  }
-  const int32_t px = 256 * i + 128, py = 256 * j + 128;
-  const double w0 = edge_fn(B, C, px, py), w1 = edge_fn(C, A, px, py), w2 = edge_fn(A, B, px, py);
-  const bool covered = (area != 0) && (w0 > 0 || (w0 == 0 && owns_edge(B, C))) &&
-                       (w1 > 0 || (w1 == 0 && owns_edge(C, A))) && (w2 > 0 || (w2 == 0 && owns_edge(A, B)));
-  unsigned long long key = SUMA_EMPTY_KEY;
-  if (covered) {
-    const float fa = (float)area;
-#ifdef SUMA_BARY_PLAIN_DIV
-    float b0 = edge_to_float(w0) / fa, b1 = edge_to_float(w1) / fa, b2 = edge_to_float(w2) / fa;
-#else
-    /* three quotients by one denominator; the operands are integers in [0, 2^46] over a positive integer area (X, Y
-     * below 2^21, so every edge function is below 2^45 in magnitude), and a zero numerator gives an exact 0: the short
-     * sequence of exact_div.h is correctly rounded there (tools/div_study.c) -- 18 instead of 33 instructions, the
-     * same bits as the three `/` (the parity suite is the check) */
-    const float fr = exdiv_refine(fa, __builtin_amdgcn_rcpf(fa));
-    float b0 = exdiv_quot(edge_to_float(w0), fa, fr), b1 = exdiv_quot(edge_to_float(w1), fa, fr),
-          b2 = exdiv_quot(edge_to_float(w2), fa, fr);
-#endif
-    float tu = (b0 * A.tu + b1 * B.tu) + b2 * C.tu;
-    float tv = (b0 * A.tv + b1 * B.tv) + b2 * C.tv;
-    float z = (b0 * A.z + b1 * B.z) + b2 * C.z;
-    /* render_surfels.frag:22 disc test; near / far clipping */
-    if (!((tu * tu + tv * tv) > 1.0f) && (z >= 0.0f && z <= 1.0f)) key = render_key(depth24(z), id, tie);
-  }
-  return key;
-}
 
 /* (inv_pose * surfelPose) * v, render_surfels.vert:44-48 */
 __device__ __forceinline__ void surfel_to_sensor(const float* __restrict__ poses, const float* inv_pose, float count,
@@ -218,8 +139,8 @@ __device__ __forceinline__ uint32_t render_block_rank(bool flag, uint32_t* s_w, 
 
 template <bool BIG> /* see the row / column split in phase 2 */
 __global__ void __launch_bounds__(RENDER_THREADS) __attribute__((amdgpu_waves_per_eu(5, 8))) k_render(RenderArgs a) {
-  __shared__ float s_cand[RENDER_THREADS][9];   /* p.xyz, n.xyz, radius, pp.x, surfel id (bits) */
-  __shared__ int32_t s_rec[RENDER_THREADS][17]; /* X0..3, Y0..3, z0..3 (float bits), i0, j0, w, surfel id; 17: a row stride of 16 words puts all lanes of a write on two banks */
+  __shared__ float s_cand[RENDER_THREADS][9];   /* p.xyz, n.xyz, radius, pp.x, surfel id (bits); behind phase 1b, in the row of a quad with tests: its set-up (fa0, fa1, word of T2, fr0, fr1) */
+  __shared__ int32_t s_rec[RENDER_THREADS][17]; /* X0..3, Y0..3, z0..3 (float bits), i0, j0, w, surfel id, slot mask (bits 1-2 of the set-up word of T1); 17: a row stride of 16 words puts all lanes of a write on two banks */
   __shared__ uint32_t s_incl[RENDER_THREADS];
   __shared__ uint32_t s_w[2][RENDER_WAVES], s_w2[RENDER_WAVES];
   __shared__ uint8_t s_mask[RENDER_THREADS]; /* slot mask of a candidate, by candidate rank */
@@ -415,7 +336,31 @@ __global__ void __launch_bounds__(RENDER_THREADS) __attribute__((amdgpu_waves_pe
               q[13] = j0;
               q[14] = w;
               q[15] = __float_as_int(r[8]);
+#ifdef SUMA_RASTER_PER_TEST
               q[16] = (int32_t)s_mask[threadIdx.x];
+#else
+              /* What the pixel tests of this quad share (raster_quad.h), once, and only for a quad that has tests.  It goes
+               * into this thread's OWN candidate row: every word of s_cand[threadIdx.x] was read above, by this thread
+               * alone, and no one reads a candidate row again in this trip -- no LDS beyond the lists.  Phase 2 reads it
+               * from another thread: the first barrier of the block prefix below orders these writes before those reads,
+               * as it does for s_rec; the closing barrier of the trip orders the reads before phase 1a refills the row. */
+              rvtx vt[4];
+#pragma unroll
+              for (int k = 0; k < 4; ++k) {
+                vt[k].X = X[k];
+                vt[k].Y = Y[k];
+              }
+              const QuadSetup qs = quad_setup(vt[0], vt[1], vt[2], vt[3]);
+              float* g = s_cand[threadIdx.x];
+              g[0] = qs.fa[0];
+              g[1] = qs.fa[1];
+              g[2] = __uint_as_float(qs.tri[1]);
+#ifndef SUMA_BARY_PLAIN_DIV
+              g[3] = qs.fr[0];
+              g[4] = qs.fr[1];
+#endif
+              q[16] = (int32_t)(qs.tri[0] | ((uint32_t)s_mask[threadIdx.x] << 1)); /* the slot mask: bits 1 and 2 */
+#endif
             }
           }
         }
@@ -494,11 +439,29 @@ __global__ void __launch_bounds__(RENDER_THREADS) __attribute__((amdgpu_waves_pe
             }
             const uint32_t id = (uint32_t)r[15];
             /* triangle strip: (v0,v1,v2), (v2,v1,v3) */
+#ifdef SUMA_RASTER_PER_TEST /* the form before the per-quad set-up, for A/B runs: everything again for every test */
             const unsigned long long ka = raster_key(vt[0], vt[1], vt[2], pi, pj, id, slot.tie);
             const unsigned long long kb = raster_key(vt[2], vt[1], vt[3], pi, pj, id, slot.tie);
             key[u] = ka < kb ? ka : kb;
+#else
+            const float* g = s_cand[src];
+            QuadSetup qs;
+            qs.fa[0] = g[0];
+            qs.fa[1] = g[1];
+            qs.tri[0] = (uint32_t)r[16];
+            qs.tri[1] = __float_as_uint(g[2]);
+#ifndef SUMA_BARY_PLAIN_DIV
+            qs.fr[0] = g[3];
+            qs.fr[1] = g[4];
+#endif
+            key[u] = quad_test(qs, vt[0], vt[1], vt[2], vt[3], pi, pj, id, slot.tie);
+#endif
             pix[u] = __umul24((uint32_t)pj, (uint32_t)a.q.W) + (uint32_t)pi; /* row, width < 2^24 */
+#ifdef SUMA_RASTER_PER_TEST
             msk[u] = (uint32_t)r[16];
+#else
+            msk[u] = ((uint32_t)r[16] >> 1) & 3u;
+#endif
           }
         }
         /* a z-buffer a fragment does not go to reads as 0: no key is smaller, no atomic follows */

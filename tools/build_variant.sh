@@ -4,7 +4,7 @@
 OUT=$1; shift
 D=$(mktemp -d); C=semantic_suma_amd/csrc
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -mllvm -amdgpu-kernarg-preload-count=16 -w"
-SRC="k_preprocess k_filters k_icp k_render k_update suma_api suma_ingest k_sync suma_runner"
+SRC=$(sed -n 's/^SRC = //p' $C/Makefile | sed 's/\.hip//g') # the product's own list: a variant must load like the product
 pids=()
 for f in $SRC; do
   hipcc $FLAGS "$@" -c $C/$f.hip -o $D/$f.o &
