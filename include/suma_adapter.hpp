@@ -887,6 +887,41 @@ class Localizer {
     out.insert(out.end(), fresh.begin(), fresh.end());
     return out;
   }
+  /* objects in front of the robot (csrc/k_objects.hip): with novelty on, every collection is followed by one
+   * segmentation of its unexplained texels into objects; nothing else the localiser gives changes */
+  void enableObjects(const suma_object_params* op = nullptr) {
+    chk(suma_localizer_enable_objects(l_, op), "Localizer::enableObjects");
+  }
+  void disableObjects() { chk(suma_localizer_disable_objects(l_), "Localizer::disableObjects"); }
+  /* the objects of the last segmentation in ascending root order; *segmented = false (and nothing returned) when the
+   * last scan or collectFrame segmented nothing.  Throws when more than max_objects were found */
+  std::vector<suma_scan_object> objects(suma_object_counts* counts = nullptr, bool* segmented = nullptr) {
+    uint32_t n = 0;
+    int32_t seg = 0;
+    suma_object_counts c;
+    int rc = suma_localizer_objects(l_, nullptr, 0, &n, &c, &seg);
+    if (rc != SUMA_ERR_CAPACITY) chk(rc, "Localizer::objects");
+    std::vector<suma_scan_object> out(n);
+    if (n) chk(suma_localizer_objects(l_, out.data(), n, &n, &c, &seg), "Localizer::objects");
+    else chk(rc, "Localizer::objects");
+    if (counts) *counts = c;
+    if (segmented) *segmented = seg != 0;
+    return out;
+  }
+  /* the id image of the last segmentation: the object number of every texel, 0xffffffff for none */
+  std::vector<uint32_t> objectIds() {
+    uint32_t n = 0;
+    chk(suma_localizer_object_ids(l_, nullptr, 0, &n), "Localizer::objectIds");
+    std::vector<uint32_t> out(n);
+    if (n) chk(suma_localizer_object_ids(l_, out.data(), n, &n), "Localizer::objectIds");
+    return out;
+  }
+  /* the primitive on a caller's flag image (one byte a texel of the data image) */
+  suma_object_counts segmentFlags(const suma_frame* frame, const double T[16], const uint8_t* flags, uint32_t scan_id) {
+    suma_object_counts c;
+    chk(suma_localizer_segment_flags(l_, frame, T, flags, scan_id, &c), "Localizer::segmentFlags");
+    return c;
+  }
   suma_localizer* get() const { return l_; }
   suma_ctx* ctx() const { return suma_localizer_ctx(l_); }
 

@@ -1094,6 +1094,73 @@ int suma_localizer_novel_marks(suma_localizer* l, uint8_t* host, uint32_t capaci
  * when n_overflow > 0 (the downloads' convention). */
 int suma_localizer_clear_novelty(suma_localizer* l);
 
+/* ---- objects in front of the robot: "what stands there now that yesterday's map does not contain?"  With novelty on,
+ *      every collection ends with a flag byte per texel, 1 = no record of the window explains the return.  With objects
+ *      on as well, each collection is followed on the ctx stream by one segmentation of those texels into connected
+ *      components of the wrapped range image, and every component of at least min_texels texels is reduced to one
+ *      64-byte record: class, box, centroid, nearest range.  The records are those of the LAST segmentation; they are
+ *      not accumulated, enter no checkpoint, and neither the grid nor the planner reads them.  csrc/k_objects.hip states
+ *      the fp32 specification, tests/object_shim.c restates it; DESIGN.md 19 has the decomposition and what is out of
+ *      scope (tracking, velocities, oriented boxes).  With objects on every other output of the localiser is
+ *      bit-identical to a run with them off. */
+typedef struct suma_object_params {
+  float link_base;       /* default 0.3 m: neighbouring texels this close belong together at any range; finite, >= 0 */
+  float link_slope;      /* default 0.03: ... plus this much per metre of the nearer texel's range; finite, >= 0 */
+  uint32_t min_texels;   /* default 5: a component of fewer texels is no object; >= 1 */
+  uint32_t max_objects;  /* default 4096 (64 bytes each); 1 .. 65 536 */
+} suma_object_params;
+typedef struct suma_scan_object {
+  uint32_t root;         /* the smallest texel index (ty * width + tx) of the object: objects ascend by it */
+  uint32_t n_texels;
+  uint32_t label;        /* the weighted vote of the members (suma_world_surfel's rule) */
+  float prob;
+  uint32_t n_dynamic;    /* members whose own label is one of the moving classes */
+  float min[3], max[3];  /* the box of the members' world positions */
+  float centroid[3];     /* their mean, from integer sums of 1/1024 m */
+  float r_min;           /* the smallest range of a member: how near the object is to the sensor */
+  uint32_t scan_id;
+} suma_scan_object;
+/* n_small + n_objects = n_components; stored = min(n_objects, max_objects) */
+typedef struct suma_object_counts {
+  uint32_t n_texels, n_members, n_components, n_small, n_objects, stored;
+} suma_object_counts;
+/* 0.3f, 0.03f, 5, 4096 */
+void suma_object_params_default(suma_object_params* op);
+/* host only, no device: SUMA_OK, or SUMA_ERR_INVALID for values outside the ranges above, the text in
+ * suma_last_error(NULL).  suma_localizer_enable_objects applies the same rule. */
+int suma_object_params_check(const suma_object_params* op);
+/* switches objects on (op NULL = the defaults) and allocates their blocks (about 130 bytes a texel of the data image and
+ * 64 bytes an object).  Needs novelty on: SUMA_ERR_INVALID otherwise, and for values outside the ranges above or a data
+ * image of more than 2^22 texels, with a message and nothing launched.  Enabling again replaces the parameters and
+ * forgets the last segmentation. */
+int suma_localizer_enable_objects(suma_localizer* l, const suma_object_params* op);
+/* switches them off and gives the blocks back; suma_localizer_disable_novelty does this too */
+int suma_localizer_disable_objects(suma_localizer* l);
+/* With objects on, every collection -- a scan's own or suma_localizer_collect_frame's -- is followed by one segmentation
+ * of that collection's flags, frame, pose and scan_id; it is only enqueued, the scan path does not wait for it.  A scan
+ * or a call that collects nothing leaves "no segmentation".  These return the objects of the last segmentation in
+ * ascending root order: *n = the objects stored, min(*n, capacity) are copied; *counts and *segmented are optional;
+ * without a segmentation *n = 0, the counts are 0 and *segmented = 0.  Blocking.  SUMA_ERR_CAPACITY after filling the
+ * outputs when n_objects > max_objects (the downloads' convention). */
+int suma_localizer_objects(suma_localizer* l, suma_scan_object* host, uint32_t capacity, uint32_t* n,
+                           suma_object_counts* counts, int32_t* segmented);
+int suma_localizer_objects_device(suma_localizer* l, suma_scan_object* d_out, uint32_t capacity, uint32_t* n,
+                                  suma_object_counts* counts, int32_t* segmented);
+/* the id image of the last segmentation, one uint32 a texel of the data image: the object number of a member of a stored
+ * object, else 0xffffffff.  *n = its size (0 without a segmentation), min(*n, capacity) are copied.  Blocking. */
+int suma_localizer_object_ids(suma_localizer* l, uint32_t* host, uint32_t capacity, uint32_t* n);
+/* the flag image of the last collection, one byte a texel of the data image, 1 = novel: what the segmentation behind that
+ * collection read (suma_localizer_novel_marks' convention; needs novelty on, not objects).  Blocking. */
+int suma_localizer_novel_flags(suma_localizer* l, uint8_t* host, uint32_t capacity, uint32_t* n);
+/* the data frame the localiser preprocesses its scans into (K1-K3 of the last suma_localizer_process_scan): what that
+ * scan's collection and segmentation read.  Owned by the localiser; NULL for a NULL handle. */
+suma_frame* suma_localizer_frame(suma_localizer* l);
+/* the primitive on a caller's flag image (host, one byte a texel of the data image) in place of a collection's: one
+ * segmentation of a frame of the localiser's ctx at the sensor pose T (column-major, world frame, finite).  It needs no
+ * map and no window and touches no candidate.  *counts is optional.  Blocking (the flags are uploaded). */
+int suma_localizer_segment_flags(suma_localizer* l, const suma_frame* frame, const double T[16], const uint8_t* host_flags,
+                                 uint32_t scan_id, suma_object_counts* counts);
+
 /* ---- place recognition and global relocalisation: "the sensor was switched on somewhere inside yesterday's map".  A
  *      place index holds one descriptor per scan of a mapping session: a polar height map about the sensor (sectors x
  *      rings, the highest kept point of each cell), made on the device from the vertex map of a frame the pipeline

@@ -12,7 +12,8 @@ stand for (PRBonn/semantic_suma, src/core):
                                                              compensated in front of the preprocessing (no counterpart)
     Localizer        (no counterpart)                        setMap / setPose / processScan / relocalize in a finished map;
                                                              enableEvidence / evidence / prunedMap: which records still hold;
-                                                             enableNovelty / novel / updatedMap: what is new
+                                                             enableNovelty / novel / updatedMap: what is new;
+                                                             enableObjects / objects: each scan's unexplained texels as objects
     PlaceIndex       (no counterpart)                        addFrame / queryFrame: place recognition over a session's scans
     Posegraph        src/core/Posegraph.h:10-78              setInitial / addEdge / optimize / poses
 
@@ -34,7 +35,8 @@ from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX
                     SemanticParams, SumaParams, WORLD_SURFEL_DTYPE, WorldParams, WorldStats, CheckpointInfo,
                     GRID_CELL_DTYPE, GridParams, GridStats,
                     PLAN_CELL_DTYPE, PLAN_PATH_DTYPE, PATH_OK, PATH_TRUNCATED, PlanParams, PlanStats,
-                    ChangeCounts, ChangeParams, ChangeRule, DeskewParams, EVIDENCE_DTYPE, NovelCounts, NovelFuseParams, NovelParams, NovelStats, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
+                    ChangeCounts, ChangeParams, ChangeRule, DeskewParams, EVIDENCE_DTYPE, NovelCounts, NovelFuseParams, NovelParams, NovelStats,
+                    ObjectCounts, ObjectParams, SCAN_OBJECT_DTYPE, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -322,6 +324,19 @@ def lib():
     L.suma_localizer_novel_device.argtypes = [vp, nfp, vp, vp, u32, nsp]
     L.suma_localizer_novel_marks.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.suma_localizer_clear_novelty.argtypes = [vp]
+    opp, ocp = C.POINTER(ObjectParams), C.POINTER(ObjectCounts)
+    L.suma_object_params_default.argtypes = [opp]
+    L.suma_object_params_default.restype = None
+    L.suma_object_params_check.argtypes = [opp]
+    L.suma_localizer_enable_objects.argtypes = [vp, opp]
+    L.suma_localizer_disable_objects.argtypes = [vp]
+    L.suma_localizer_objects.argtypes = [vp, vp, u32, C.POINTER(u32), ocp, C.POINTER(i32)]
+    L.suma_localizer_objects_device.argtypes = [vp, vp, u32, C.POINTER(u32), ocp, C.POINTER(i32)]
+    L.suma_localizer_object_ids.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_localizer_segment_flags.argtypes = [vp, vp, vp, vp, u32, ocp]
+    L.suma_localizer_novel_flags.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_localizer_frame.argtypes = [vp]
+    L.suma_localizer_frame.restype = vp
     dkp = C.POINTER(DeskewParams)
     L.suma_deskew_params_default.argtypes = [dkp]
     L.suma_deskew_params_default.restype = None
@@ -2071,6 +2086,65 @@ class Localizer(_DeskewSwitch):
             ev = None
         kept = records if ev is None else pruned_map(records, ev, rule)[0]
         return np.concatenate([kept, self.novel(fuse_params)[0]])
+
+    # -- objects in front of the robot (csrc/k_objects.hip)
+    def enableObjects(self, params: ObjectParams = None):
+        """from now on every collection (novelty must be on) is followed by one segmentation of its unexplained texels
+        into objects; nothing else the localiser gives changes"""
+        self.ctx.check(self.L.suma_localizer_enable_objects(self.h, None if params is None else C.byref(params)),
+                       "suma_localizer_enable_objects")
+
+    def disableObjects(self):
+        self.ctx.check(self.L.suma_localizer_disable_objects(self.h), "suma_localizer_disable_objects")
+
+    def objects(self, allow_overflow: bool = False):
+        """(SCAN_OBJECT_DTYPE records in ascending root order, the suma_object_counts dict) of the last segmentation, or
+        None when the last scan or collectFrame segmented nothing.  More objects than max_objects raise unless
+        ``allow_overflow``, which takes the first max_objects"""
+        n, cnt, seg = C.c_uint32(0), ObjectCounts(), C.c_int32(0)
+        self._novel_check(self.L.suma_localizer_objects(self.h, None, 0, C.byref(n), C.byref(cnt), C.byref(seg)),
+                          "suma_localizer_objects", True)
+        if not seg.value:
+            return None
+        rec = np.zeros(n.value, dtype=SCAN_OBJECT_DTYPE)
+        self._novel_check(self.L.suma_localizer_objects(self.h, _ptr(rec) if n.value else None, n.value, C.byref(n),
+                                                        C.byref(cnt), C.byref(seg)), "suma_localizer_objects", allow_overflow)
+        return rec[:n.value], cnt.as_dict()
+
+    def objectIds(self):
+        """H x W uint32: the object number of every texel of the last segmentation, 0xffffffff for none; None when
+        nothing was segmented"""
+        p = self.params
+        out = np.zeros((p.data_height, p.data_width), dtype=np.uint32)
+        n = C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_object_ids(self.h, _ptr(out), out.size, C.byref(n)), "suma_localizer_object_ids")
+        return out if n.value else None
+
+    def scanFrame(self) -> Frame:
+        """the data frame of the last processScan (vertex, normal, semantic): what its collection and segmentation read"""
+        p = self.params
+        return Frame(self.ctx, p.data_width, p.data_height, handle=self.L.suma_localizer_frame(self.h))
+
+    def novelFlags(self) -> np.ndarray:
+        """the flag image of the last collection, H x W uint8: 1 where the texel was novel -- what its segmentation read"""
+        p = self.params
+        out = np.zeros((p.data_height, p.data_width), dtype=np.uint8)
+        n = C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_novel_flags(self.h, _ptr(out), out.size, C.byref(n)), "suma_localizer_novel_flags")
+        return out
+
+    def segmentFlags(self, frame: Frame, pose, flags, scan_id: int) -> dict:
+        """the primitive: one segmentation of a data-sized frame of this localiser's ctx at a sensor pose (row-major 4x4,
+        world frame) over the caller's flag image (H x W, non-zero = take the texel); returns its counts"""
+        p = self.params
+        fl = np.ascontiguousarray(flags, dtype=np.uint8)
+        if fl.size != p.data_width * p.data_height:
+            raise ValueError("flags must have one byte per texel of the data image")
+        T = _cm(pose, np.float64)
+        cnt = ObjectCounts()
+        self.ctx.check(self.L.suma_localizer_segment_flags(self.h, frame.h, _ptr(T), _ptr(fl), scan_id, C.byref(cnt)),
+                       "suma_localizer_segment_flags")
+        return cnt.as_dict()
 
     def modelFrame(self) -> Frame:
         """the window as the last scan's render saw it (the ctx's oldMapFrame)"""

@@ -665,6 +665,35 @@ int novel_collect(suma_ctx* c, Novel& nv, const LocMap& m, uint32_t n_spans, uin
 int novel_fuse(suma_ctx* c, Novel& nv, uint32_t n, const suma_novel_fuse_params& fp, suma_world_surfel* d_out,
                uint32_t* d_views, uint32_t capacity, uint32_t counters_out[3]);
 
+/* k_objects.hip (the specification is there): the objects of one scan's unexplained texels */
+struct ObjAcc { /* what the members of a component add up at their root, 96 bytes */
+  uint32_t n, n_dyn, obj, rmin;           /* members, dynamic members, the object number (or none), ordered r_min */
+  uint32_t mn[3], pad0, mx[3], pad1;      /* the box as ordered integers */
+  unsigned long long S[3], sum_all, best; /* centroid sums (int64), the vote's total, its best sum << 9 | 511 - label */
+  unsigned long long pad2;
+};
+struct Objects {
+  bool on = false;
+  suma_object_params op;
+  uint32_t n_texels = 0;         /* of the data image the blocks below were made for */
+  int32_t segmented = 0;         /* the blocks hold a segmentation */
+  DevBuf<uint32_t> label;        /* one a texel: a member's root, or none */
+  DevBuf<ObjAcc> acc;            /* one a texel, used at roots */
+  DevBuf<uint32_t> hkey;         /* the vote table, two slots a texel: root * 512 + label + 1 */
+  DevBuf<unsigned long long> hsum;
+  DevBuf<uint32_t> block_counts; /* kob_vote's counts, 4 words a block of 256 texels */
+  DevBuf<uint32_t> state;        /* suma_object_counts of the last segmentation */
+  DevBuf<float4> rec;            /* 4 float4 a record, op.max_objects of them */
+  DevBuf<uint32_t> ids;
+  DevBuf<uint8_t> flags_in;      /* suma_localizer_segment_flags' flag image */
+  PinnedBuf<uint32_t> stage_h;   /* the counts on their way to the host */
+};
+/* the blocks for P texels and op.max_objects records; the caller has drained the stream */
+int objects_alloc(suma_ctx* c, Objects& ob, const suma_object_params& op, uint32_t P);
+/* one segmentation of frame f's flagged texels (d_flags: P bytes on the device) at pose T, enqueued */
+int objects_segment(suma_ctx* c, Objects& ob, const suma_frame* f, const uint8_t* d_flags, const double T[16],
+                    uint32_t scan_id);
+
 /* k_deskew.hip (the specification is there): what kd_deskew receives by value -- the twist of one sweep, made once on the
  * host in fp64 (deskew_twist) and rounded to fp32 */
 #define SUMA_DESKEW_SMALL_THETA 1e-6

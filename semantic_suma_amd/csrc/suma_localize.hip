@@ -39,6 +39,8 @@ struct suma_localizer {
   Novel nv;
   uint32_t scan_count = 0;     /* process_scan calls since the last set_map */
   int32_t last_collected = 0;
+  /* objects (k_objects.hip): the segmentation behind every collection */
+  Objects ob;
   /* motion compensation (k_deskew.hip): the correction of process_scan's points, and the staging of a host scan that is
    * corrected (an uncorrected one goes through suma_preprocess's own staging) */
   Deskew dk;
@@ -99,13 +101,19 @@ int observe(suma_localizer* l, const suma_frame* f, const double T[16], suma_cha
   return SUMA_OK;
 }
 
-/* one collection over the current window, enqueued on the ctx stream */
+/* one collection over the current window, enqueued on the ctx stream; with objects on, its segmentation behind it.  A
+ * call that collects nothing leaves no segmentation */
 int collect(suma_localizer* l, const suma_frame* f, const double T[16], uint32_t scan_id) {
   suma_ctx* c = l->c;
+  l->ob.segmented = 0;
   if (!l->n_window) return SUMA_OK;
   if (c->gate_pending) HIP_TRY(c, flush_gate(c));
   const_cast<suma_frame*>(f)->last_access = ++c->enq_seq;
-  return novel_collect(c, l->nv, l->map, (uint32_t)l->spans.size(), l->n_window, f, T, scan_id);
+  int r = novel_collect(c, l->nv, l->map, (uint32_t)l->spans.size(), l->n_window, f, T, scan_id);
+  if (r || !l->ob.on) return r;
+  r = objects_segment(c, l->ob, f, l->nv.flag, T, scan_id); /* behind the collection on the same stream, enqueued only */
+  if (!r) l->ob.segmented = 1;
+  return r;
 }
 
 int change_params_check(const suma_change_params& q, std::string* why) {
@@ -172,6 +180,7 @@ extern "C" void suma_localizer_destroy(suma_localizer* l) {
   l->map = LocMap(); /* device blocks go before the ctx */
   l->ev_totals.reset(), l->ev_totals_h.reset(), l->ev_source.reset();
   l->nv = Novel();
+  l->ob = Objects();
   l->dk.points.reset(), l->dk_points.reset(), l->dk_labels.reset(), l->dk_probs.reset();
   suma_frame_destroy(l->frame);
   suma_ctx_destroy(l->c);
@@ -191,6 +200,7 @@ extern "C" int suma_localizer_set_map_device(suma_localizer* l, const suma_world
   if (l->nv.on) HIP_TRY(c, hipMemsetAsync(l->nv.state, 0, sizeof(NovelState), c->stream));
   l->scan_count = 0;
   l->last_collected = 0;
+  l->ob.segmented = 0;
   memset(&l->last_counts, 0, sizeof(l->last_counts));
   l->last_observed = 0;
   l->have_map = true;
@@ -360,6 +370,7 @@ static int process_scan(suma_localizer* l, const suma_float4* points, const floa
     const uint32_t scan_id = l->scan_count++;
     if (l->nv.on) {
       l->last_collected = 0;
+      l->ob.segmented = 0;
       if (l->n_window && (res->tracked || !l->nv.np.tracked_only) && finite16(pose)) {
         int r = collect(l, l->frame, pose, scan_id);
         if (r) return r;
@@ -747,6 +758,7 @@ extern "C" int suma_localizer_enable_novelty(suma_localizer* l, const suma_novel
     }
     HIP_TRY(c, hipMemsetAsync(nw.state, 0, sizeof(NovelState), c->stream));
     HIP_TRY(c, hipMemsetAsync(nw.mark, 0, P, c->stream));
+    HIP_TRY(c, hipMemsetAsync(nw.flag, 0, P, c->stream)); /* suma_localizer_novel_flags in front of the first collection */
     nv = std::move(nw);
     l->last_collected = 0;
   }
@@ -761,6 +773,7 @@ extern "C" int suma_localizer_disable_novelty(suma_localizer* l) {
   if (l->nv.on) {
     HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a collection may still write them */
     l->nv = Novel();
+    l->ob = Objects(); /* the segmentation reads the collection's flags: off with it */
   }
   l->last_collected = 0;
   return SUMA_OK;
@@ -795,6 +808,7 @@ extern "C" int suma_localizer_collect_frame(suma_localizer* l, const suma_frame*
   if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_collect_frame: non-finite pose");
   if (counts) memset(counts, 0, sizeof(*counts));
   l->last_collected = 0;
+  l->ob.segmented = 0;
   if (!l->have_map || !l->n_window) return SUMA_OK;
   r = collect(l, frame, T, scan_id);
   if (r) return r;
@@ -947,5 +961,174 @@ extern "C" int suma_localizer_clear_novelty(suma_localizer* l) {
   if (r) return r;
   HIP_TRY(c, hipMemsetAsync(l->nv.state, 0, sizeof(NovelState), c->stream));
   l->last_collected = 0;
+  l->ob.segmented = 0;
   return SUMA_OK;
+}
+
+/* ---- objects (include/suma_hip.h states the entries, k_objects.hip the specification) ---- */
+extern "C" void suma_object_params_default(suma_object_params* op) {
+  if (!op) return;
+  op->link_base = 0.3f;
+  op->link_slope = 0.03f;
+  op->min_texels = 5u;
+  op->max_objects = 4096u;
+}
+
+/* NULL, or what is wrong with the values */
+static const char* object_params_why(const suma_object_params& q) {
+  if (!(std::isfinite(q.link_base) && q.link_base >= 0.0f)) return "link_base must be finite and >= 0";
+  if (!(std::isfinite(q.link_slope) && q.link_slope >= 0.0f)) return "link_slope must be finite and >= 0";
+  if (q.min_texels < 1u) return "min_texels must be at least 1";
+  if (q.max_objects < 1u || q.max_objects > 65536u) return "max_objects must be 1 .. 65536";
+  return nullptr;
+}
+
+extern "C" int suma_object_params_check(const suma_object_params* op) {
+  if (!op) return fail_without_ctx(SUMA_ERR_INVALID, "suma_object_params_check: NULL parameters");
+  if (const char* why = object_params_why(*op)) return fail_without_ctx(SUMA_ERR_INVALID, std::string("suma_object_params_check: ") + why);
+  return SUMA_OK;
+}
+
+static int objects_ready(suma_localizer* l, const char* who) {
+  if (!l->ob.on) return fail(l->c, SUMA_ERR_INVALID, std::string(who) + ": objects are off (suma_localizer_enable_objects)");
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_enable_objects(suma_localizer* l, const suma_object_params* op) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (!l->nv.on)
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_enable_objects: novelty is off (suma_localizer_enable_novelty): the "
+                                     "objects are made of its flags");
+  suma_object_params q;
+  suma_object_params_default(&q);
+  if (op) q = *op;
+  if (const char* why = object_params_why(q)) return fail(c, SUMA_ERR_INVALID, std::string("suma_localizer_enable_objects: ") + why);
+  const uint64_t P = (uint64_t)c->p.data_width * (uint64_t)c->p.data_height;
+  if (P > (1u << 22)) /* the bound that keeps the centroid's int64 sums from overflowing (k_objects.hip, step 5) */
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_enable_objects: the data image has " + std::to_string(P) +
+                                     " texels, more than 2^22");
+  Objects& ob = l->ob;
+  if (!ob.on || ob.op.max_objects != q.max_objects || ob.n_texels != (uint32_t)P) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a segmentation may still write the old blocks */
+    int r = objects_alloc(c, ob, q, (uint32_t)P);
+    if (r) return r;
+  }
+  ob.op = q;
+  ob.on = true;
+  ob.segmented = 0;
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_disable_objects(suma_localizer* l) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (l->ob.on) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a segmentation may still write them */
+    l->ob = Objects();
+  }
+  return SUMA_OK;
+}
+
+/* the counts of the last segmentation into host words (blocking) */
+static int objects_counts(suma_localizer* l, suma_object_counts* out) {
+  suma_ctx* c = l->c;
+  HIP_TRY(c, hipMemcpyAsync(l->ob.stage_h, l->ob.state, sizeof(suma_object_counts), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(out, l->ob.stage_h.p, sizeof(*out));
+  return SUMA_OK;
+}
+
+static int objects_download(suma_localizer* l, suma_scan_object* out, uint32_t capacity, uint32_t* n,
+                            suma_object_counts* counts, int32_t* segmented, bool to_device, const char* who) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = objects_ready(l, who);
+  if (r) return r;
+  if (!n || (capacity && !out)) return fail(c, SUMA_ERR_INVALID, std::string(who) + ": NULL argument");
+  *n = 0;
+  if (counts) memset(counts, 0, sizeof(*counts));
+  if (segmented) *segmented = l->ob.segmented;
+  if (!l->ob.segmented) return SUMA_OK;
+  suma_object_counts cnt;
+  r = objects_counts(l, &cnt);
+  if (r) return r;
+  if (counts) *counts = cnt;
+  *n = cnt.stored;
+  const uint32_t m = cnt.stored < capacity ? cnt.stored : capacity;
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(out, l->ob.rec, (size_t)m * sizeof(suma_scan_object),
+                              to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  if (cnt.n_objects > cnt.stored)
+    return fail(c, SUMA_ERR_CAPACITY, std::string(who) + ": " + std::to_string(cnt.n_objects - cnt.stored) +
+                                      " objects did not fit into max_objects = " + std::to_string(l->ob.op.max_objects));
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_objects(suma_localizer* l, suma_scan_object* host, uint32_t capacity, uint32_t* n,
+                                      suma_object_counts* counts, int32_t* segmented) {
+  return objects_download(l, host, capacity, n, counts, segmented, false, "suma_localizer_objects");
+}
+
+extern "C" int suma_localizer_objects_device(suma_localizer* l, suma_scan_object* d_out, uint32_t capacity, uint32_t* n,
+                                             suma_object_counts* counts, int32_t* segmented) {
+  return objects_download(l, d_out, capacity, n, counts, segmented, true, "suma_localizer_objects_device");
+}
+
+extern "C" int suma_localizer_object_ids(suma_localizer* l, uint32_t* host, uint32_t capacity, uint32_t* n) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = objects_ready(l, "suma_localizer_object_ids");
+  if (r) return r;
+  if (!n || (capacity && !host)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_object_ids: NULL argument");
+  *n = l->ob.segmented ? l->ob.n_texels : 0u;
+  const uint32_t m = *n < capacity ? *n : capacity;
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(host, l->ob.ids, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return SUMA_OK;
+}
+
+extern "C" suma_frame* suma_localizer_frame(suma_localizer* l) { return l ? l->frame : nullptr; }
+
+extern "C" int suma_localizer_novel_flags(suma_localizer* l, uint8_t* host, uint32_t capacity, uint32_t* n) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = novelty_ready(l, "suma_localizer_novel_flags");
+  if (r) return r;
+  if (!n || (capacity && !host)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_novel_flags: NULL argument");
+  *n = (uint32_t)c->p.data_width * (uint32_t)c->p.data_height;
+  const uint32_t m = *n < capacity ? *n : capacity;
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(host, l->nv.flag, m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_segment_flags(suma_localizer* l, const suma_frame* frame, const double T[16],
+                                            const uint8_t* host_flags, uint32_t scan_id, suma_object_counts* counts) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = objects_ready(l, "suma_localizer_segment_flags");
+  if (r) return r;
+  if (!frame || !T || !host_flags) return fail(c, SUMA_ERR_INVALID, "suma_localizer_segment_flags: NULL argument");
+  if (frame->ctx != c) return fail(c, SUMA_ERR_INVALID, "suma_localizer_segment_flags: the frame belongs to another ctx");
+  if (frame->width != c->p.data_width || frame->height != c->p.data_height)
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_segment_flags: the frame must have the data image's size");
+  if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_segment_flags: non-finite pose");
+  if (counts) memset(counts, 0, sizeof(*counts));
+  Objects& ob = l->ob;
+  ob.segmented = 0;
+  if (c->gate_pending) HIP_TRY(c, flush_gate(c));
+  const_cast<suma_frame*>(frame)->last_access = ++c->enq_seq;
+  HIP_TRY(c, hipMemcpyAsync(ob.flags_in, host_flags, ob.n_texels, hipMemcpyHostToDevice, c->stream));
+  r = objects_segment(c, ob, frame, ob.flags_in, T, scan_id);
+  HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a pageable source: the copy has left it */
+  if (r) return r;
+  ob.segmented = 1;
+  return counts ? objects_counts(l, counts) : SUMA_OK;
 }

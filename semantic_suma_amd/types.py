@@ -377,6 +377,40 @@ class NovelStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class ObjectParams(C.Structure):
+    """``struct suma_object_params``: when neighbouring unexplained texels of a scan belong to one object
+    (csrc/k_objects.hip) and how many objects a segmentation keeps; ``ObjectParams.defaults()`` =
+    suma_object_params_default"""
+    _fields_ = [("link_base", f32), ("link_slope", f32), ("min_texels", u32), ("max_objects", u32)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "ObjectParams":
+        p = cls(link_base=0.3, link_slope=0.03, min_texels=5, max_objects=4096)
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        return p
+
+
+class ObjectCounts(C.Structure):
+    """``struct suma_object_counts``: what one segmentation made of the texels of the frame"""
+    _fields_ = [("n_texels", u32), ("n_members", u32), ("n_components", u32), ("n_small", u32), ("n_objects", u32),
+                ("stored", u32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+OBJECT_COUNTS = tuple(k for k, _ in ObjectCounts._fields_)
+
+# numpy view of ``struct suma_scan_object``: one per object of a scan, in ascending root order
+SCAN_OBJECT_DTYPE = np.dtype([("root", "<u4"), ("n_texels", "<u4"), ("label", "<u4"), ("prob", "<f4"), ("n_dynamic", "<u4"),
+                              ("min", "<f4", (3,)), ("max", "<f4", (3,)), ("centroid", "<f4", (3,)), ("r_min", "<f4"),
+                              ("scan_id", "<u4")])
+assert SCAN_OBJECT_DTYPE.itemsize == 64
+
+
 PLACE_MAX_DIM = 64       # SUMA_PLACE_MAX_DIM: rings and sectors
 PLACE_MAX_MATCHES = 32   # SUMA_PLACE_MAX_MATCHES
 # is_dynamic_label (csrc/dev_math.h): the moving classes K1 drops at the start of a run

@@ -11,7 +11,8 @@ every scan's totals and, with --prune-out, writes the map without the records th
 objects out of the synthetic world the localised scans see).  --novel collects the surfaces no record of the map explains
 (csrc/k_novel.hip), prints every scan's counts and, with --update-out, writes the updated map: the records the rule keeps
 (all of them without --evidence) followed by the fused new ones (--map-without takes objects out of the world the mapping
-run sees).  --deskew motion compensates the localised scans with the localiser's last increment (csrc/k_deskew.hip), for
+run sees).  --objects (with --novel) segments each scan's unexplained texels into objects (csrc/k_objects.hip) and prints,
+per scan, their number and each one's class, size, centroid and nearest range; --objects-out writes them as JSON.  --deskew motion compensates the localised scans with the localiser's last increment (csrc/k_deskew.hip), for
 sensors that deliver raw sweeps.  With --relocalize the first scan goes through Localizer.relocalize against a place index (core.PlaceIndex) -- the mapping
 run's own scans, or with --map the file tools/export_map.py --places wrote (--places).  Needs a GPU.
     python tools/localize.py [--map-scans 80] [--first 10] [--scans 60] [--voxel 0.1] [--width 2048] [--kitti sequences/08]
@@ -21,6 +22,7 @@ run's own scans, or with --map the file tools/export_map.py --places wrote (--pl
     python tools/localize.py --map map.ply --places map.places.npz --relocalize --first 11 --scans 20
     python tools/localize.py --evidence --without 2 41 --prune-out pruned.ply   # cube 2 and a building are gone
     python tools/localize.py --map-without 2 41 --novel --update-out new.ply    # cube 2 and a building have arrived
+    python tools/localize.py --map-without 2 41 --novel --objects [--objects-out objects.json]   # ... as objects, per scan
     python tools/localize.py --kitti raw/sequence --deskew   # raw (uncompensated) sweeps: corrected in front of K1
 """
 import argparse
@@ -130,6 +132,76 @@ def collect_timing(loc, scan, pose, n_window):
     return out
 
 
+def objects_timing(loc, scan, pose):
+    """the event times of one segmentation's two kernel groups (suma_profile: kob_init + kob_merge + kob_flatten, and
+    kob_vote + kob_emit + kob_ids) over the flags of one collection, each against an event-timed device-to-device copy of
+    the bytes it touches (about 150 and 40 a texel: the vertex and semantic texels, the labels, the vote table, the ids; 96
+    more per member for its accumulator are left out), and the host route timed in the same run: the flag, vertex and
+    semantic images downloaded, then tests/object_shim.c (gcc -O2, one thread) over them"""
+    import subprocess
+    import tempfile
+    from semantic_suma_amd.types import ObjectCounts, ObjectParams, SCAN_OBJECT_DTYPE
+    ctx, p = loc.ctx, loc.params
+    W, H = p.data_width, p.data_height
+    frame = core.Frame(ctx, W, H)
+    core.Preprocessing(ctx).process(scan[0], frame, scan[1], scan[2], p.active_timestamps + 10)
+    held = loc.novelCandidates(allow_overflow=True)
+    loc.collectFrame(frame, pose, 0)
+    loc.setNovelCandidates(held)
+    flags = loc.novelFlags()
+    ctx.profile(1)
+    label, reduce_ = [], []
+    for k in range(13):
+        ctx.profile_reset()
+        counts = loc.segmentFlags(frame, pose, flags, 0)
+        ms = {r["name"]: r["total_ms"] for r in ctx.profile_get()}
+        if k >= 3:
+            label.append(ms["objects_label"])
+            reduce_.append(ms["objects_reduce"])
+    ctx.profile(0)
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    out = dict(counts=counts)
+    for name, nbytes, kernel in (("label", 150 * W * H, label), ("reduce", 40 * W * H, reduce_)):
+        src, dst = ctx.device_array(np.zeros(nbytes, dtype=np.uint8)), ctx.device_array(np.zeros(nbytes, dtype=np.uint8))
+        copy = event_ms(ctx, lambda: hip.hipMemcpyAsync(dst, src, nbytes, 3, C.c_void_p(ctx.stream)))
+        ctx.device_free(src)
+        ctx.device_free(dst)
+        k, c = float(np.median(kernel)), float(np.median(copy))
+        out[name] = dict(launches=3, bytes=nbytes, kernel_us_median10=round(1e3 * k, 2), d2d_copy_us_median10=round(1e3 * c, 2),
+                         kernel_over_copy=round(k / c, 3), samples=dict(kernel_ms=kernel, d2d_copy_ms=copy))
+    # the host route
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with tempfile.TemporaryDirectory() as tmp:
+        so = os.path.join(tmp, "object_shim.so")
+        subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-ffp-contract=off", "-fPIC", "-shared",
+                               os.path.join(root, "tests", "object_shim.c"), "-o", so, "-lm"])
+        shim = C.CDLL(so)
+        shim.object_shim_segment.argtypes = [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(ObjectParams),
+                                                                 C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(ObjectCounts)]
+        shim.object_shim_segment.restype = None
+        op, cnt = ObjectParams.defaults(), ObjectCounts()
+        rec, ids = np.zeros(op.max_objects, dtype=SCAN_OBJECT_DTYPE), np.zeros(W * H, dtype=np.uint32)
+        Tc = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).T)
+        download, host = [], []
+        for k in range(13):
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            fl, V, S = loc.novelFlags(), frame.download(0), frame.download(2)
+            t1 = time.perf_counter()
+            shim.object_shim_segment(V.ctypes.data, S.ctypes.data, fl.ctypes.data, W, H, Tc.ctypes.data, C.byref(op), 0,
+                                     rec.ctypes.data, ids.ctypes.data, C.byref(cnt))
+            t2 = time.perf_counter()
+            if k >= 3:
+                download.append(1e3 * (t1 - t0))
+                host.append(1e3 * (t2 - t1))
+        same = cnt.as_dict() == counts and rec[:cnt.stored].tobytes() == loc.objects(allow_overflow=True)[0].tobytes()
+    out["host_route"] = dict(download_us_median10=round(1e3 * float(np.median(download)), 2),
+                             shim_us_median10=round(1e3 * float(np.median(host)), 2), equals_device=bool(same),
+                             samples=dict(download_ms=download, shim_ms=host))
+    return out
+
+
 def pose_from(x, y, z, yaw_deg):
     a = np.deg2rad(yaw_deg)
     T = np.eye(4)
@@ -170,6 +242,9 @@ def main():
     ap.add_argument("--novel", action="store_true", help="collect the surfaces no map record explains and print every scan's counts")
     ap.add_argument("--update-out", default=None, metavar="FILE.ply",
                     help="with --novel: write the updated map (what the rule keeps, then the fused new records)")
+    ap.add_argument("--objects", action="store_true",
+                    help="with --novel: segment each scan's unexplained texels into objects and print them")
+    ap.add_argument("--objects-out", default=None, metavar="FILE.json", help="with --objects: write every scan's objects")
     ap.add_argument("--map-without", type=int, nargs="*", default=[], metavar="BOX",
                     help="synthetic scans: boxes of synth._boxes the mapping run does not see")
     args = ap.parse_args()
@@ -177,6 +252,10 @@ def main():
         ap.error("--prune-out needs --evidence")
     if args.update_out and not args.novel:
         ap.error("--update-out needs --novel")
+    if args.objects and not args.novel:
+        ap.error("--objects needs --novel")
+    if args.objects_out and not args.objects:
+        ap.error("--objects-out needs --objects")
     over = {k: v for k, v in (("submap_extent", args.extent), ("submap_dimension", args.dimension)) if v is not None}
     p = params_with_size(args.width, args.height, **over)
     n_map = args.map_scans if args.map_scans is not None else (300 if args.timing else 80)
@@ -233,6 +312,8 @@ def main():
         loc.enableEvidence()
     if args.novel:
         loc.enableNovelty()
+    if args.objects:
+        loc.enableObjects()
     if args.deskew:
         loc.enableDeskew()
         res["deskew"] = True
@@ -244,7 +325,7 @@ def main():
         loc.setPose(start)
     scans = [read_scan(args, k, tuple(args.without)) for k in ks]
     host_scans = scans
-    observations, collections = [], []
+    observations, collections, objects = [], [], []
     if args.timing:
         scans = [resident(loc.ctx, sc) for sc in scans]
         loc.ctx.synchronize()
@@ -271,6 +352,8 @@ def main():
                 observations.append(loc.lastObservation())
             if args.novel and not args.timing:  # the counts wait for the device: a timed run asks once, at the end
                 collections.append(loc.lastCollection(allow_overflow=True))
+            if args.objects and not args.timing:
+                objects.append(loc.objects(allow_overflow=True))
         except core.SumaError as e:  # a run that has left the map ends on a pose that is no longer finite
             res.update(lost_at_scan=k, error=str(e))
             break
@@ -308,6 +391,28 @@ def main():
             upd = np.concatenate([core.pruned_map(records, loc.evidence())[0] if args.evidence else records, fused])
             mapio.write_ply(args.update_out, upd)
             res.update(updated_map=args.update_out, updated_records=int(len(upd)))
+    if args.objects:
+        listing = []
+        for k, got in zip(ks[len(ks) - len(objects):] if args.relocalize else ks, objects):
+            rec, cnt = got if got is not None else ((), dict(n_objects=0, n_small=0, n_members=0))
+            print(f"scan {k:5d}  objects {cnt['n_objects']}  small {cnt['n_small']}  members {cnt['n_members']}")
+            for o in rec:
+                size = o["max"] - o["min"]
+                print(f"            class {int(o['label']):3d} ({float(o['prob']):.2f})  texels {int(o['n_texels']):5d}  "
+                      f"dynamic {int(o['n_dynamic']):4d}  size {size[0]:6.2f} {size[1]:6.2f} {size[2]:6.2f}  "
+                      f"centroid {o['centroid'][0]:9.3f} {o['centroid'][1]:9.3f} {o['centroid'][2]:7.3f}  "
+                      f"nearest {float(o['r_min']):7.3f} m")
+            listing.append(dict(scan=k, counts=cnt, objects=[
+                dict(root=int(o["root"]), n_texels=int(o["n_texels"]), label=int(o["label"]), prob=float(o["prob"]),
+                     n_dynamic=int(o["n_dynamic"]), min=[float(v) for v in o["min"]], max=[float(v) for v in o["max"]],
+                     centroid=[float(v) for v in o["centroid"]], r_min=float(o["r_min"])) for o in rec]))
+        last = loc.objects(allow_overflow=True)
+        res["objects"] = dict(per_scan=[e["counts"]["n_objects"] for e in listing] if listing else None,
+                              last_scan=None if last is None else last[1])
+        if args.objects_out:
+            with open(args.objects_out, "w") as f:
+                json.dump(listing, f)
+            res["objects_file"] = args.objects_out
     origin, n_window, rebuilds = loc.window()
     res.update(tracked=sum(r["tracked"] for r in out), window_rebuilds=sum(r["window_rebuilt"] for r in out),
                n_window=n_window, worst_distance_to_mapping_pose_m=round(worst, 4))
@@ -326,6 +431,8 @@ def main():
             res["observe"] = observe_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], loc.window()[1])
         if args.novel and "lost_at_scan" not in res:
             res["collect"] = collect_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], loc.window()[1])
+        if args.objects and "lost_at_scan" not in res:
+            res["segment"] = objects_timing(loc, host_scans[len(out) - 1], out[-1]["pose"])
     loc.close()
     print(json.dumps(res))
 
