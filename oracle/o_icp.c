@@ -198,6 +198,13 @@ void ora_solve6(const double* A, const double* b, double* x) {
     for (int k = i + 1; k < 6; ++k) s -= L[6 * i + k] * x[k];
     x[i] = s;
   }
+  /* Containment (documented deviations): a pivot that is not > 0 (zero, negative or NaN) or a solution
+   * component that is not finite makes the step the zero twist.  On an all-zero system (no inlier pair) that is what
+   * Eigen's pivoted LDL^T returns; without it 0/0 gives a NaN step that rule :64 reports as converged. */
+  int ok = 1;
+  for (int i = 0; i < 6; ++i) ok &= (D[i] > 0.0) & (isfinite(x[i]) != 0);
+  if (!ok)
+    for (int i = 0; i < 6; ++i) x[i] = 0.0;
 }
 
 static void o_mul4d(const double* A, const double* B, double* C) {

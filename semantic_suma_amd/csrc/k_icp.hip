@@ -277,6 +277,15 @@ __device__ __forceinline__ void solve6_wave(const double* val, int lane, double*
     for (int k = i + 1; k < 6; ++k) sacc -= bcast_d(Lrow[i], k) * x[k]; /* L[i][k] lives in row k */
     x[i] = sacc;
   }
+  /* Containment (documented deviations): a pivot that is not > 0 (zero, negative or NaN) or a solution
+   * component that is not finite makes the step the zero twist.  Lane j holds pivot j (lanes >= 6 shadow lane 5), so
+   * one compare and a ballot test all six; x[] is wave-uniform: six independent class tests, and-ed without
+   * short-circuit branches, then six selects. */
+  bool ok = __builtin_amdgcn_ballot_w64(Dmine > 0.0) == __builtin_amdgcn_ballot_w64(true);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) ok = ok & (bool)__builtin_isfinite(x[i]);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) x[i] = ok ? x[i] : 0.0;
 }
 
 /* SE3::exp, lie_algebra.cpp:4-34; x = (v, omega); column-major */

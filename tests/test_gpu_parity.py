@@ -971,7 +971,8 @@ def test_async_ingest_equals_resident_scans(hip):
         b.ctx.check(b.L.suma_pipeline_process_scan_async(b.h, pts.ctypes.data if pts.size else None, None, None,
                                                          pts.shape[0], 5), "async")
         c.processScan(pts, lab, prob, fixed_iterations=5)
-    assert b.getCurrentPose().tobytes() == c.getCurrentPose().tobytes()  # NaN after the empty scan, on both paths
+    assert b.getCurrentPose().tobytes() == c.getCurrentPose().tobytes()
+    assert np.isfinite(b.getCurrentPose()).all()  # an empty scan's singular system gives the zero step, not NaN
     assert b.map.getAllSurfels().tobytes() == c.map.getAllSurfels().tobytes()
     # misuse is reported
     with pytest.raises(hip.SumaError):
