@@ -70,7 +70,7 @@ def main():
             spm = re.search(r"\.sgpr_spill_count:\s+(\d+)", md.group(1)) if md else None
             sp = spm.group(1) if spm else "?"
             a, l = stats(body), stats(largest_loop(body))
-            short = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().split("(")[0][:44]
+            short = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().split("(")[0].replace(", ", ",")[:44]  # one word per name
             print(f"{short:44s} {vg:>4s} {sp:>9s} | {a['valu']:5d} "
                   f"{a['readlane']:6d} {a['writelane']:6d} {a['nop']:5d} {a['div']:4d} {a['smem']:4d} {a['vmem']:4d} {a['lds']:4d} | "
                   f"{'':13s} {l['valu']:5d} {l['readlane']:6d} {l['nop']:5d} {l['div']:4d} {l['smem']:4d}")
