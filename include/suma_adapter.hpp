@@ -922,12 +922,72 @@ class Localizer {
     chk(suma_localizer_segment_flags(l_, frame, T, flags, scan_id, &c), "Localizer::segmentFlags");
     return c;
   }
+  /* live obstacles for the planner (csrc/k_live.hip): with novelty on, every collection is followed by one update of a
+   * layer over the static grid gp / cells (host cells, uploaded for the call); nothing else the localiser gives changes */
+  void enableLiveGrid(const suma_grid_params& gp, const std::vector<suma_grid_cell>& cells, const suma_live_params* lp = nullptr) {
+    if (cells.size() != (size_t)gp.width * gp.height) throw std::runtime_error("Localizer::enableLiveGrid: cells do not fit the raster");
+    void* d = nullptr;
+    chk(suma_device_alloc(ctx(), cells.size() * sizeof(suma_grid_cell), &d), "Localizer::enableLiveGrid");
+    int rc = suma_device_upload(ctx(), d, cells.data(), cells.size() * sizeof(suma_grid_cell));
+    if (rc == SUMA_OK) rc = suma_localizer_enable_live_grid(l_, &gp, (const suma_grid_cell*)d, lp);
+    std::string why = rc == SUMA_OK ? "" : suma_last_error(ctx());
+    suma_device_free(ctx(), d);
+    if (rc != SUMA_OK) throw std::runtime_error("Localizer::enableLiveGrid: " + why);
+    live_cells_ = cells.size();
+  }
+  /* the device form: d_cells = what suma_world_grid wrote for gp, only read */
+  void enableLiveGridDevice(const suma_grid_params& gp, const suma_grid_cell* d_cells, const suma_live_params* lp = nullptr) {
+    chk(suma_localizer_enable_live_grid(l_, &gp, d_cells, lp), "Localizer::enableLiveGrid");
+    live_cells_ = (size_t)gp.width * gp.height;
+  }
+  void disableLiveGrid() {
+    chk(suma_localizer_disable_live_grid(l_), "Localizer::disableLiveGrid");
+    live_cells_ = 0;
+  }
+  void clearLiveGrid() { chk(suma_localizer_clear_live_grid(l_), "Localizer::clearLiveGrid"); }
+  suma_live_counts liveUpdateFlags(const suma_frame* frame, const double T[16], const uint8_t* flags, uint32_t scan_id) {
+    suma_live_counts c;
+    chk(suma_localizer_live_update_flags(l_, frame, T, flags, scan_id, &c), "Localizer::liveUpdateFlags");
+    return c;
+  }
+  /* the counts of the last update; *updated = false when there was none */
+  suma_live_counts liveCounts(bool* updated = nullptr) {
+    suma_live_counts c;
+    int32_t u = 0;
+    chk(suma_localizer_live_counts(l_, &c, &u), "Localizer::liveCounts");
+    if (updated) *updated = u != 0;
+    return c;
+  }
+  /* composes: the static cells with the live obstacles written into them, what suma_grid_plan_field takes; mask: one byte
+   * a cell, 1 live, 2 pending */
+  std::vector<suma_grid_cell> liveCells(std::vector<uint8_t>* mask = nullptr, suma_live_stats* stats = nullptr) {
+    std::vector<suma_grid_cell> out(live_cells_);
+    void *d = nullptr, *dm = nullptr;
+    chk(suma_device_alloc(ctx(), live_cells_ * sizeof(suma_grid_cell) + 48, &d), "Localizer::liveCells");
+    int rc = suma_device_alloc(ctx(), live_cells_ + 16, &dm);
+    if (rc == SUMA_OK) rc = suma_localizer_live_cells_device(l_, (suma_grid_cell*)d, (uint8_t*)dm, stats);
+    if (rc == SUMA_OK && live_cells_) rc = suma_device_download(ctx(), out.data(), d, live_cells_ * sizeof(suma_grid_cell));
+    if (rc == SUMA_OK && mask) {
+      mask->resize(live_cells_);
+      if (live_cells_) rc = suma_device_download(ctx(), mask->data(), dm, live_cells_);
+    }
+    std::string why = rc == SUMA_OK ? "" : suma_last_error(ctx());
+    suma_device_free(ctx(), d);
+    if (dm) suma_device_free(ctx(), dm);
+    if (rc != SUMA_OK) throw std::runtime_error("Localizer::liveCells: " + why);
+    return out;
+  }
+  /* the device form, for suma_grid_plan_field to read the cells where they are */
+  void liveCellsDevice(suma_grid_cell* d_out, uint8_t* d_mask = nullptr, suma_live_stats* stats = nullptr) {
+    chk(suma_localizer_live_cells_device(l_, d_out, d_mask, stats), "Localizer::liveCells");
+  }
   suma_localizer* get() const { return l_; }
   suma_ctx* ctx() const { return suma_localizer_ctx(l_); }
 
  private:
   void chk(int rc, const char* what) { check(suma_localizer_ctx(l_), rc, what); }
   suma_localizer* l_ = nullptr;
+  size_t live_cells_ = 0; /* of the live layer's raster; 0: off */
 };
 
 }  // namespace suma_hip

@@ -1161,6 +1161,75 @@ suma_frame* suma_localizer_frame(suma_localizer* l);
 int suma_localizer_segment_flags(suma_localizer* l, const suma_frame* frame, const double T[16], const uint8_t* host_flags,
                                  uint32_t scan_id, suma_object_counts* counts);
 
+/* ---- live obstacles for the planner: "what stands there now goes into the grid the planner reads".  A live layer holds
+ *      16 bytes of state per cell over the raster of a static traversability grid (suma_world_grid's cells).  With the
+ *      layer on, every collection -- after its segmentation when objects are on -- is followed on the ctx stream by one
+ *      update: the unexplained texels that stand between step_height and clearance above a cell's ground enter a hit into
+ *      that cell, and the scan's rays clear the cells they pass through below the top of what was seen there earlier.
+ *      Composing gives the static cells with the live obstacles written into them, in the suma_grid_cell layout:
+ *      suma_grid_plan_field takes the result unchanged.  csrc/k_live.hip states the specification, tests/live_shim.c
+ *      restates it; DESIGN.md 20 has the decomposition and what is out of scope (the layer in checkpoints and during
+ *      mapping, exact cell traversal, tracking).  The scan path, the candidates, the objects, the grid and the planner
+ *      keep their results bit for bit. */
+typedef struct suma_live_params {
+  uint32_t hold_scans;   /* default 10: a hit keeps its cell an obstacle for this many scans; 1 .. 65 535 */
+  uint32_t min_hits;     /* default 2: hits in a row (none further apart than hold_scans) before a cell is live; 1 .. 65 535 */
+  float carve_range;     /* default 20 m: how far along a ray cells are cleared; finite, >= 0; 0 switches carving off */
+  float carve_margin;    /* default 0.5 m: a ray stops clearing this far in front of its return; finite, >= 0 */
+} suma_live_params;
+/* the raw state of one cell (suma_localizer_live_state): stamp = scan_id + 1 of an update, 0 = never */
+typedef struct suma_live_cell {
+  uint64_t hit;          /* stamp of the last hit << 32 | the highest hit z of that scan as an ordered integer */
+  uint32_t clear;        /* stamp of the last scan a ray cleared the cell in */
+  uint32_t hits;         /* hits in a row, saturating at 65 535 */
+} suma_live_cell;
+/* one update.  n_members = n_outside + n_no_ground + n_low + n_high + n_hit_texels; n_rays = 0 with carving off */
+typedef struct suma_live_counts {
+  uint32_t n_texels, n_members, n_outside, n_no_ground, n_low, n_high, n_hit_texels, n_hit_cells, n_rays, n_cleared;
+} suma_live_counts;
+/* one compose: the cells with a hit are live, pending (too few hits yet), carved (a ray cleared them after the hit) or
+ * expired (the hit is hold_scans old) */
+typedef struct suma_live_stats {
+  uint32_t n_live, n_pending, n_expired, n_carved;
+} suma_live_stats;
+/* 10, 2, 20.0f, 0.5f */
+void suma_live_params_default(suma_live_params* lp);
+/* host only, no device: SUMA_OK, or SUMA_ERR_INVALID for values outside the ranges above, the text in
+ * suma_last_error(NULL).  suma_localizer_enable_live_grid applies the same rule. */
+int suma_live_params_check(const suma_live_params* lp);
+/* switches the layer on over the raster gp (lp NULL = the defaults).  d_cells: the gp->width * gp->height DEVICE cells
+ * suma_world_grid wrote for gp, 16-byte aligned; they may come from another ctx on the same device and are only read: the
+ * layer keeps a copy (48 bytes a cell) and allocates and zeroes 20 bytes a cell of state.  Blocking.  Needs novelty on;
+ * objects are optional.  SUMA_ERR_INVALID with a message, nothing launched: novelty off, a NULL or misaligned d_cells,
+ * gp outside the ranges stated at suma_grid_params, lp outside the ranges above.  Enabling again replaces the layer. */
+int suma_localizer_enable_live_grid(suma_localizer* l, const suma_grid_params* gp, const suma_grid_cell* d_cells,
+                                    const suma_live_params* lp);
+/* switches it off and gives the blocks back; suma_localizer_disable_novelty does this too */
+int suma_localizer_disable_live_grid(suma_localizer* l);
+/* zeroes the state (no cell has a hit, the last stamp is 0); suma_localizer_set_map does this too */
+int suma_localizer_clear_live_grid(suma_localizer* l);
+/* the primitive on a caller's flag image (host, one byte a texel of the data image), the counterpart of
+ * suma_localizer_segment_flags: uploads the flags, segments them when objects are on, then updates the layer with the
+ * frame (of the localiser's ctx, data-sized) at the sensor pose T (column-major, world frame, finite).  It needs no map.
+ * *counts is optional.  Blocking.  A scan_id whose stamp scan_id + 1 is not greater than the last update's returns
+ * SUMA_ERR_INVALID and launches nothing; so does a collection's own update (suma_localizer_process_scan counts its
+ * scans from the last suma_localizer_set_map; suma_localizer_collect_frame takes the caller's scan_id). */
+int suma_localizer_live_update_flags(suma_localizer* l, const suma_frame* frame, const double T[16], const uint8_t* host_flags,
+                                     uint32_t scan_id, suma_live_counts* counts);
+/* the counts of the last update; *updated = 0 and zero counts when there was none since the layer was enabled or cleared.
+ * Both outputs are optional.  Blocking. */
+int suma_localizer_live_counts(suma_localizer* l, suma_live_counts* counts, int32_t* updated);
+/* composes: d_out_cells = width * height cells (DEVICE, 16-byte aligned), the static cells with state = OBSTACLE and
+ * obstacle_z raised to the hit's top where the cell is live; d_out_mask (DEVICE, optional) = one byte a cell, 1 live,
+ * 2 pending, 0 otherwise.  Writes only the caller's buffers; two calls give the same bytes.  Blocking. */
+int suma_localizer_live_cells_device(suma_localizer* l, suma_grid_cell* d_out_cells, uint8_t* d_out_mask,
+                                     suma_live_stats* stats);
+/* the raw state, one suma_live_cell a cell: *n = width * height, min(*n, capacity) are copied.  Blocking. */
+int suma_localizer_live_state(suma_localizer* l, suma_live_cell* host, uint32_t capacity, uint32_t* n);
+/* replaces the raw state (n = width * height cells) and the last stamp: a saved layer put back, and how the tests reach
+ * states that would take 65 535 updates.  Blocking. */
+int suma_localizer_set_live_state(suma_localizer* l, const suma_live_cell* host, uint32_t n, uint32_t last_stamp);
+
 /* ---- place recognition and global relocalisation: "the sensor was switched on somewhere inside yesterday's map".  A
  *      place index holds one descriptor per scan of a mapping session: a polar height map about the sensor (sectors x
  *      rings, the highest kept point of each cell), made on the device from the vertex map of a frame the pipeline

@@ -14,6 +14,7 @@ stand for (PRBonn/semantic_suma, src/core):
                                                              enableEvidence / evidence / prunedMap: which records still hold;
                                                              enableNovelty / novel / updatedMap: what is new;
                                                              enableObjects / objects: each scan's unexplained texels as objects
+                                                             enableLiveGrid / liveCells: live obstacles in the planner's grid
     PlaceIndex       (no counterpart)                        addFrame / queryFrame: place recognition over a session's scans
     Posegraph        src/core/Posegraph.h:10-78              setInitial / addEdge / optimize / poses
 
@@ -36,7 +37,7 @@ from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX
                     GRID_CELL_DTYPE, GridParams, GridStats,
                     PLAN_CELL_DTYPE, PLAN_PATH_DTYPE, PATH_OK, PATH_TRUNCATED, PlanParams, PlanStats,
                     ChangeCounts, ChangeParams, ChangeRule, DeskewParams, EVIDENCE_DTYPE, NovelCounts, NovelFuseParams, NovelParams, NovelStats,
-                    ObjectCounts, ObjectParams, SCAN_OBJECT_DTYPE, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
+                    ObjectCounts, ObjectParams, SCAN_OBJECT_DTYPE, LIVE_CELL_DTYPE, LiveCounts, LiveParams, LiveStats, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -337,6 +338,18 @@ def lib():
     L.suma_localizer_novel_flags.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.suma_localizer_frame.argtypes = [vp]
     L.suma_localizer_frame.restype = vp
+    lvp, lcp = C.POINTER(LiveParams), C.POINTER(LiveCounts)
+    L.suma_live_params_default.argtypes = [lvp]
+    L.suma_live_params_default.restype = None
+    L.suma_live_params_check.argtypes = [lvp]
+    L.suma_localizer_enable_live_grid.argtypes = [vp, C.POINTER(GridParams), vp, lvp]
+    L.suma_localizer_disable_live_grid.argtypes = [vp]
+    L.suma_localizer_clear_live_grid.argtypes = [vp]
+    L.suma_localizer_live_update_flags.argtypes = [vp, vp, vp, vp, u32, lcp]
+    L.suma_localizer_live_counts.argtypes = [vp, lcp, C.POINTER(i32)]
+    L.suma_localizer_live_cells_device.argtypes = [vp, vp, vp, C.POINTER(LiveStats)]
+    L.suma_localizer_live_state.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.suma_localizer_set_live_state.argtypes = [vp, vp, u32, u32]
     dkp = C.POINTER(DeskewParams)
     L.suma_deskew_params_default.argtypes = [dkp]
     L.suma_deskew_params_default.restype = None
@@ -2145,6 +2158,102 @@ class Localizer(_DeskewSwitch):
         self.ctx.check(self.L.suma_localizer_segment_flags(self.h, frame.h, _ptr(T), _ptr(fl), scan_id, C.byref(cnt)),
                        "suma_localizer_segment_flags")
         return cnt.as_dict()
+
+    # -- live obstacles for the planner (csrc/k_live.hip)
+    def enableLiveGrid(self, cells, gp: GridParams, params: LiveParams = None):
+        """from now on every collection (novelty must be on; after its segmentation when objects are on) is followed by
+        one update of a live obstacle layer over the static grid ``cells`` / ``gp`` of core.world_grid: the
+        GRID_CELL_DTYPE array (uploaded for the call), or a device address / torch tensor of gp.width * gp.height
+        cells, which is only read -- the layer keeps a copy"""
+        owned = None
+        if isinstance(cells, np.ndarray):
+            arr = np.ascontiguousarray(cells, dtype=GRID_CELL_DTYPE).reshape(-1)
+            if arr.shape[0] != int(gp.width) * int(gp.height):
+                raise ValueError(f"enableLiveGrid: {arr.shape[0]} cells against a raster of {gp.height} x {gp.width}")
+            cells = owned = self.ctx.device_array(arr)
+        try:
+            self.ctx.check(self.L.suma_localizer_enable_live_grid(self.h, C.byref(gp), _dev(cells),
+                                                                  None if params is None else C.byref(params)),
+                           "suma_localizer_enable_live_grid")
+        finally:
+            if owned:
+                self.L.suma_device_free(self.ctx.h, C.c_void_p(owned))
+        self._live_gp = GridParams.from_buffer_copy(gp)
+
+    def disableLiveGrid(self):
+        self.ctx.check(self.L.suma_localizer_disable_live_grid(self.h), "suma_localizer_disable_live_grid")
+        self._live_gp = None
+
+    def clearLiveGrid(self):
+        """no cell has a hit; setMap does this too"""
+        self.ctx.check(self.L.suma_localizer_clear_live_grid(self.h), "suma_localizer_clear_live_grid")
+
+    def liveUpdateFlags(self, frame: Frame, pose, flags, scan_id: int) -> dict:
+        """the primitive: one update of the live layer with a data-sized frame of this localiser's ctx at a sensor pose
+        (row-major 4x4, world frame) over the caller's flag image (H x W, non-zero = take the texel), segmented first
+        when objects are on; returns the update's counts"""
+        p = self.params
+        fl = np.ascontiguousarray(flags, dtype=np.uint8)
+        if fl.size != p.data_width * p.data_height:
+            raise ValueError("flags must have one byte per texel of the data image")
+        T = _cm(pose, np.float64)
+        cnt = LiveCounts()
+        self.ctx.check(self.L.suma_localizer_live_update_flags(self.h, frame.h, _ptr(T), _ptr(fl), scan_id, C.byref(cnt)),
+                       "suma_localizer_live_update_flags")
+        return cnt.as_dict()
+
+    def liveCounts(self):
+        """the suma_live_counts dict of the last update, or None when there was none since the layer was enabled or
+        cleared"""
+        cnt, upd = LiveCounts(), C.c_int32(0)
+        self.ctx.check(self.L.suma_localizer_live_counts(self.h, C.byref(cnt), C.byref(upd)), "suma_localizer_live_counts")
+        return cnt.as_dict() if upd.value else None
+
+    def liveCells(self, out=None):
+        """composes -> (cells[height, width] of GRID_CELL_DTYPE, mask[height, width] uint8: 1 live, 2 pending, the
+        suma_live_stats dict): the static cells with the live obstacles written into them, what core.grid_plan and
+        GridPlanner take.  ``out``: a device address / torch tensor of width * height cells (16-byte aligned) to leave
+        the cells at, for core.grid_plan to read there; the return is then (None, mask, stats)"""
+        gp = getattr(self, "_live_gp", None)
+        if gp is None:
+            raise SumaError("liveCells: the live layer is off (enableLiveGrid)")
+        n = int(gp.width) * int(gp.height)
+        L, h = self.L, self.ctx.h
+        d_cells, d_mask, st = C.c_void_p(), C.c_void_p(), LiveStats()
+        try:
+            if out is None:
+                self.ctx.check(L.suma_device_alloc(h, n * GRID_CELL_DTYPE.itemsize, C.byref(d_cells)), "suma_device_alloc")
+            self.ctx.check(L.suma_device_alloc(h, max(n, 16), C.byref(d_mask)), "suma_device_alloc")
+            self.ctx.check(L.suma_localizer_live_cells_device(self.h, d_cells if out is None else _dev(out), d_mask, C.byref(st)),
+                           "suma_localizer_live_cells_device")
+            cells = None
+            if out is None:
+                cells = np.zeros((gp.height, gp.width), dtype=GRID_CELL_DTYPE)
+                self.ctx.check(L.suma_device_download(h, _ptr(cells), d_cells, cells.nbytes), "suma_device_download")
+            mask = np.zeros((gp.height, gp.width), dtype=np.uint8)
+            self.ctx.check(L.suma_device_download(h, _ptr(mask), d_mask, mask.nbytes), "suma_device_download")
+        finally:
+            if d_cells:
+                L.suma_device_free(h, d_cells)
+            if d_mask:
+                L.suma_device_free(h, d_mask)
+        return cells, mask, st.as_dict()
+
+    def liveState(self) -> np.ndarray:
+        """the raw state of the layer, LIVE_CELL_DTYPE [height, width] (for tests and for keeping a layer)"""
+        gp = getattr(self, "_live_gp", None)
+        if gp is None:
+            raise SumaError("liveState: the live layer is off (enableLiveGrid)")
+        out = np.zeros((gp.height, gp.width), dtype=LIVE_CELL_DTYPE)
+        n = C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_live_state(self.h, _ptr(out), out.size, C.byref(n)), "suma_localizer_live_state")
+        return out
+
+    def setLiveState(self, state: np.ndarray, last_stamp: int):
+        """puts a raw state (what liveState gave) and the stamp of its last update back"""
+        st = np.ascontiguousarray(state, dtype=LIVE_CELL_DTYPE).reshape(-1)
+        self.ctx.check(self.L.suma_localizer_set_live_state(self.h, _ptr(st), st.shape[0], last_stamp),
+                       "suma_localizer_set_live_state")
 
     def modelFrame(self) -> Frame:
         """the window as the last scan's render saw it (the ctx's oldMapFrame)"""

@@ -74,6 +74,25 @@ extern "C" int suma_world_grid_fit(suma_ctx* c, const suma_world_surfel* d_recor
   return SUMA_OK;
 }
 
+/* the ranges stated at suma_grid_params, cell_size included */
+int grid_check_params(suma_ctx* c, const std::string& who, const suma_grid_params& gp) {
+  int r = grid_check_cell_size(c, who.c_str(), gp.cell_size);
+  if (r) return r;
+  if (!(std::isfinite(gp.origin_x) && std::isfinite(gp.origin_y)))
+    return fail(c, SUMA_ERR_INVALID, who + ": origin is not finite");
+  if (gp.width < 1 || gp.height < 1 || (uint64_t)gp.width * gp.height > GRID_MAX_CELLS)
+    return fail(c, SUMA_ERR_INVALID, who + ": width x height = " + std::to_string(gp.width) + " x " +
+                                     std::to_string(gp.height) + " (each >= 1, width * height <= 2^26)");
+  if (std::isnan(gp.min_normal_z)) return fail(c, SUMA_ERR_INVALID, who + ": min_normal_z is NaN");
+  if (!std::isfinite(gp.step_height)) return fail(c, SUMA_ERR_INVALID, who + ": step_height is not finite");
+  if (!(std::isfinite(gp.clearance) && gp.clearance > gp.step_height))
+    return fail(c, SUMA_ERR_INVALID, who + ": clearance = " + std::to_string(gp.clearance) +
+                                     " (must be finite and > step_height)");
+  if (gp.fill_radius > 8) return fail(c, SUMA_ERR_INVALID, who + ": fill_radius = " + std::to_string(gp.fill_radius) +
+                                                            " (0 .. 8)");
+  return SUMA_OK;
+}
+
 extern "C" int suma_world_grid(suma_ctx* c, const suma_grid_params* gp, const suma_world_surfel* d_records, uint32_t n,
                                suma_grid_cell* d_cells, suma_grid_stats* stats) {
   if (!c) return SUMA_ERR_INVALID;
@@ -83,19 +102,7 @@ extern "C" int suma_world_grid(suma_ctx* c, const suma_grid_params* gp, const su
   if (!d_cells) return fail(c, SUMA_ERR_INVALID, "suma_world_grid: NULL cells");
   if ((uintptr_t)d_cells & 15u) return fail(c, SUMA_ERR_INVALID, "suma_world_grid: cells not 16-byte aligned");
   int r = grid_check_records(c, who, d_records, n);
-  if (r || (r = grid_check_cell_size(c, who, gp->cell_size))) return r;
-  if (!(std::isfinite(gp->origin_x) && std::isfinite(gp->origin_y)))
-    return fail(c, SUMA_ERR_INVALID, "suma_world_grid: origin is not finite");
-  if (gp->width < 1 || gp->height < 1 || (uint64_t)gp->width * gp->height > GRID_MAX_CELLS)
-    return fail(c, SUMA_ERR_INVALID, "suma_world_grid: width x height = " + std::to_string(gp->width) + " x " +
-                                     std::to_string(gp->height) + " (each >= 1, width * height <= 2^26)");
-  if (std::isnan(gp->min_normal_z)) return fail(c, SUMA_ERR_INVALID, "suma_world_grid: min_normal_z is NaN");
-  if (!std::isfinite(gp->step_height)) return fail(c, SUMA_ERR_INVALID, "suma_world_grid: step_height is not finite");
-  if (!(std::isfinite(gp->clearance) && gp->clearance > gp->step_height))
-    return fail(c, SUMA_ERR_INVALID, "suma_world_grid: clearance = " + std::to_string(gp->clearance) +
-                                     " (must be finite and > step_height)");
-  if (gp->fill_radius > 8) return fail(c, SUMA_ERR_INVALID, "suma_world_grid: fill_radius = " + std::to_string(gp->fill_radius) +
-                                                            " (0 .. 8)");
+  if (r || (r = grid_check_params(c, who, *gp))) return r;
 
   const size_t n_cells = (size_t)gp->width * gp->height;
   size_t tmp = 0;

@@ -580,6 +580,8 @@ hipError_t launch_grid(suma_ctx* c, const suma_grid_params& gp, const suma_world
  * MIN_X stays 0xffffffff when there is none */
 hipError_t launch_grid_fit(suma_ctx* c, const suma_world_surfel* d_records, uint32_t n);
 float grid_ordered_float(uint32_t o);
+/* suma_grid.hip: SUMA_OK, or SUMA_ERR_INVALID with "who: ..." for a raster or a rule outside the ranges of suma_grid_params */
+int grid_check_params(suma_ctx* c, const std::string& who, const suma_grid_params& gp);
 
 /* k_plan.hip (the specification is there): clearance, cost-to-go field and paths on the traversability grid.  All enqueue
  * on c->stream; only launch_plan_relax waits, once per batch of rounds, for the batch's flags. */
@@ -693,6 +695,33 @@ int objects_alloc(suma_ctx* c, Objects& ob, const suma_object_params& op, uint32
 /* one segmentation of frame f's flagged texels (d_flags: P bytes on the device) at pose T, enqueued */
 int objects_segment(suma_ctx* c, Objects& ob, const suma_frame* f, const uint8_t* d_flags, const double T[16],
                     uint32_t scan_id);
+
+/* k_live.hip (the specification is there): the live obstacle layer over a static traversability grid */
+enum { LIVE_COUNT_WORDS = 10, LIVE_ANY_HIT = 10, LIVE_STAT_WORDS = 4, LIVE_STATS = 12, LIVE_WORDS = 16 };
+struct Live {
+  bool on = false;
+  suma_live_params lp;
+  suma_grid_params gp;
+  uint32_t n_cells = 0;
+  uint32_t last_stamp = 0;       /* of the last update; 0: none */
+  int32_t updated = 0;           /* words 0 .. 9 hold an update's counts */
+  DevBuf<float4> cells;          /* the static cells, 3 float4 a cell */
+  DevBuf<float> ground;          /* their ground_z, what the rays read */
+  DevBuf<suma_live_cell> state;
+  DevBuf<uint32_t> words;        /* LIVE_WORDS: the counts of the last update, "some cell has a hit", a compose's stats */
+  DevBuf<uint8_t> flags_in;      /* suma_localizer_live_update_flags' flag image, without objects */
+  PinnedBuf<uint32_t> stage_h;
+};
+/* the blocks for gp's raster, the static cells copied from d_cells, the state zeroed; blocking */
+int live_alloc(suma_ctx* c, Live& lv, const suma_grid_params& gp, const suma_grid_cell* d_cells);
+/* state and words to zero, enqueued */
+int live_clear(suma_ctx* c, Live& lv);
+/* one update with stamp s of frame f's flagged texels (d_flags: one byte a texel; d_ids: the segmentation's id image, or
+ * NULL without objects) at pose T, enqueued: the hits, then the carve */
+int live_update(suma_ctx* c, Live& lv, const suma_frame* f, const uint8_t* d_flags, const uint32_t* d_ids, const double T[16],
+                uint32_t s);
+/* the composed cells and the mask (or NULL) into the caller's device blocks, the stats into words LIVE_STATS ..; enqueued */
+int live_compose(suma_ctx* c, Live& lv, suma_grid_cell* d_out, uint8_t* d_mask);
 
 /* k_deskew.hip (the specification is there): what kd_deskew receives by value -- the twist of one sweep, made once on the
  * host in fp64 (deskew_twist) and rounded to fp32 */

@@ -41,6 +41,8 @@ struct suma_localizer {
   int32_t last_collected = 0;
   /* objects (k_objects.hip): the segmentation behind every collection */
   Objects ob;
+  /* the live obstacle layer (k_live.hip): one update behind every collection and its segmentation */
+  Live lv;
   /* motion compensation (k_deskew.hip): the correction of process_scan's points, and the staging of a host scan that is
    * corrected (an uncorrected one goes through suma_preprocess's own staging) */
   Deskew dk;
@@ -101,18 +103,34 @@ int observe(suma_localizer* l, const suma_frame* f, const double T[16], suma_cha
   return SUMA_OK;
 }
 
-/* one collection over the current window, enqueued on the ctx stream; with objects on, its segmentation behind it.  A
- * call that collects nothing leaves no segmentation */
+/* an update's stamp must lie above the last one's: checked in front of everything an update's call launches */
+int live_stamp_check(suma_localizer* l, uint32_t scan_id, const char* who) {
+  const uint32_t s = scan_id + 1u;
+  if (s > l->lv.last_stamp) return SUMA_OK;
+  return fail(l->c, SUMA_ERR_INVALID, std::string(who) + ": scan_id " + std::to_string(scan_id) + " gives the live layer the stamp " +
+                                      std::to_string(s) + ", not above the last update's " + std::to_string(l->lv.last_stamp));
+}
+
+/* one collection over the current window, enqueued on the ctx stream; with objects on, its segmentation behind it, and
+ * with the live layer on, its update behind both.  A call that collects nothing leaves no segmentation */
 int collect(suma_localizer* l, const suma_frame* f, const double T[16], uint32_t scan_id) {
   suma_ctx* c = l->c;
   l->ob.segmented = 0;
   if (!l->n_window) return SUMA_OK;
+  if (l->lv.on) {
+    int r = live_stamp_check(l, scan_id, "suma_localizer: the collection");
+    if (r) return r;
+  }
   if (c->gate_pending) HIP_TRY(c, flush_gate(c));
   const_cast<suma_frame*>(f)->last_access = ++c->enq_seq;
   int r = novel_collect(c, l->nv, l->map, (uint32_t)l->spans.size(), l->n_window, f, T, scan_id);
-  if (r || !l->ob.on) return r;
-  r = objects_segment(c, l->ob, f, l->nv.flag, T, scan_id); /* behind the collection on the same stream, enqueued only */
-  if (!r) l->ob.segmented = 1;
+  if (r) return r;
+  if (l->ob.on) {
+    r = objects_segment(c, l->ob, f, l->nv.flag, T, scan_id); /* behind the collection on the same stream, enqueued only */
+    if (r) return r;
+    l->ob.segmented = 1;
+  }
+  if (l->lv.on) r = live_update(c, l->lv, f, l->nv.flag, l->ob.on ? l->ob.ids.p : nullptr, T, scan_id + 1u);
   return r;
 }
 
@@ -181,6 +199,7 @@ extern "C" void suma_localizer_destroy(suma_localizer* l) {
   l->ev_totals.reset(), l->ev_totals_h.reset(), l->ev_source.reset();
   l->nv = Novel();
   l->ob = Objects();
+  l->lv = Live();
   l->dk.points.reset(), l->dk_points.reset(), l->dk_labels.reset(), l->dk_probs.reset();
   suma_frame_destroy(l->frame);
   suma_ctx_destroy(l->c);
@@ -198,6 +217,7 @@ extern "C" int suma_localizer_set_map_device(suma_localizer* l, const suma_world
   int r = localize_bin(c, d_records, n, &l->map, l->ev_wanted);
   if (r) return r;
   if (l->nv.on) HIP_TRY(c, hipMemsetAsync(l->nv.state, 0, sizeof(NovelState), c->stream));
+  if (l->lv.on && (r = live_clear(c, l->lv))) return r;
   l->scan_count = 0;
   l->last_collected = 0;
   l->ob.segmented = 0;
@@ -774,6 +794,7 @@ extern "C" int suma_localizer_disable_novelty(suma_localizer* l) {
     HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a collection may still write them */
     l->nv = Novel();
     l->ob = Objects(); /* the segmentation reads the collection's flags: off with it */
+    l->lv = Live();    /* and so does the live layer */
   }
   l->last_collected = 0;
   return SUMA_OK;
@@ -1131,4 +1152,184 @@ extern "C" int suma_localizer_segment_flags(suma_localizer* l, const suma_frame*
   if (r) return r;
   ob.segmented = 1;
   return counts ? objects_counts(l, counts) : SUMA_OK;
+}
+
+/* ---- the live obstacle layer (include/suma_hip.h states the entries, k_live.hip the specification) ---- */
+extern "C" void suma_live_params_default(suma_live_params* lp) {
+  if (!lp) return;
+  lp->hold_scans = 10u;
+  lp->min_hits = 2u;
+  lp->carve_range = 20.0f;
+  lp->carve_margin = 0.5f;
+}
+
+/* NULL, or what is wrong with the values */
+static const char* live_params_why(const suma_live_params& q) {
+  if (q.hold_scans < 1u || q.hold_scans > 65535u) return "hold_scans must be 1 .. 65535";
+  if (q.min_hits < 1u || q.min_hits > 65535u) return "min_hits must be 1 .. 65535";
+  if (!(std::isfinite(q.carve_range) && q.carve_range >= 0.0f)) return "carve_range must be finite and >= 0";
+  if (!(std::isfinite(q.carve_margin) && q.carve_margin >= 0.0f)) return "carve_margin must be finite and >= 0";
+  return nullptr;
+}
+
+extern "C" int suma_live_params_check(const suma_live_params* lp) {
+  if (!lp) return fail_without_ctx(SUMA_ERR_INVALID, "suma_live_params_check: NULL parameters");
+  if (const char* why = live_params_why(*lp)) return fail_without_ctx(SUMA_ERR_INVALID, std::string("suma_live_params_check: ") + why);
+  return SUMA_OK;
+}
+
+static int live_ready(suma_localizer* l, const char* who) {
+  if (!l->lv.on) return fail(l->c, SUMA_ERR_INVALID, std::string(who) + ": the live layer is off (suma_localizer_enable_live_grid)");
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_enable_live_grid(suma_localizer* l, const suma_grid_params* gp, const suma_grid_cell* d_cells,
+                                               const suma_live_params* lp) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  const char* who = "suma_localizer_enable_live_grid";
+  if (!l->nv.on)
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_enable_live_grid: novelty is off (suma_localizer_enable_novelty): the "
+                                     "hits are made of its flags");
+  if (!gp) return fail(c, SUMA_ERR_INVALID, "suma_localizer_enable_live_grid: NULL grid parameters");
+  if (!d_cells) return fail(c, SUMA_ERR_INVALID, "suma_localizer_enable_live_grid: NULL cells");
+  if ((uintptr_t)d_cells & 15u) return fail(c, SUMA_ERR_INVALID, "suma_localizer_enable_live_grid: cells not 16-byte aligned");
+  int r = grid_check_params(c, who, *gp);
+  if (r) return r;
+  suma_live_params q;
+  suma_live_params_default(&q);
+  if (lp) q = *lp;
+  if (const char* why = live_params_why(q)) return fail(c, SUMA_ERR_INVALID, std::string("suma_localizer_enable_live_grid: ") + why);
+  HIP_TRY(c, hipStreamSynchronize(c->stream)); /* an update may still write the old blocks */
+  r = live_alloc(c, l->lv, *gp, d_cells);
+  if (r) return r;
+  l->lv.lp = q;
+  l->lv.on = true;
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_disable_live_grid(suma_localizer* l) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (l->lv.on) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* an update may still write them */
+    l->lv = Live();
+  }
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_clear_live_grid(suma_localizer* l) {
+  if (!l) return SUMA_ERR_INVALID;
+  int r = live_ready(l, "suma_localizer_clear_live_grid");
+  if (r) return r;
+  return live_clear(l->c, l->lv);
+}
+
+/* words first .. first + n - 1 of the layer into host words (blocking) */
+static int live_words(suma_localizer* l, uint32_t first, uint32_t n, void* out) {
+  suma_ctx* c = l->c;
+  HIP_TRY(c, hipMemcpyAsync(l->lv.stage_h.p + first, l->lv.words.p + first, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(out, l->lv.stage_h.p + first, n * sizeof(uint32_t));
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_live_update_flags(suma_localizer* l, const suma_frame* frame, const double T[16],
+                                                const uint8_t* host_flags, uint32_t scan_id, suma_live_counts* counts) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  const char* who = "suma_localizer_live_update_flags";
+  int r = live_ready(l, who);
+  if (r) return r;
+  if (!frame || !T || !host_flags) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_update_flags: NULL argument");
+  if (frame->ctx != c) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_update_flags: the frame belongs to another ctx");
+  if (frame->width != c->p.data_width || frame->height != c->p.data_height)
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_update_flags: the frame must have the data image's size");
+  if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_update_flags: non-finite pose");
+  if ((r = live_stamp_check(l, scan_id, who))) return r;
+  if (counts) memset(counts, 0, sizeof(*counts));
+  Objects& ob = l->ob;
+  Live& lv = l->lv;
+  const size_t P = (size_t)c->p.data_width * (size_t)c->p.data_height;
+  uint8_t* d_flags = ob.flags_in;
+  if (!ob.on) {
+    if ((r = grow(c, lv.flags_in, P, {c->stream})) < 0) return r;
+    d_flags = lv.flags_in;
+  }
+  ob.segmented = 0;
+  if (c->gate_pending) HIP_TRY(c, flush_gate(c));
+  const_cast<suma_frame*>(frame)->last_access = ++c->enq_seq;
+  HIP_TRY(c, hipMemcpyAsync(d_flags, host_flags, P, hipMemcpyHostToDevice, c->stream));
+  r = ob.on ? objects_segment(c, ob, frame, d_flags, T, scan_id) : SUMA_OK;
+  if (!r) r = live_update(c, lv, frame, d_flags, ob.on ? ob.ids.p : nullptr, T, scan_id + 1u);
+  HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a pageable source: the copy has left it */
+  if (r) return r;
+  if (ob.on) ob.segmented = 1;
+  return counts ? live_words(l, 0, LIVE_COUNT_WORDS, counts) : SUMA_OK;
+}
+
+extern "C" int suma_localizer_live_counts(suma_localizer* l, suma_live_counts* counts, int32_t* updated) {
+  if (!l) return SUMA_ERR_INVALID;
+  int r = live_ready(l, "suma_localizer_live_counts");
+  if (r) return r;
+  if (counts) memset(counts, 0, sizeof(*counts));
+  if (updated) *updated = l->lv.updated;
+  if (!l->lv.updated || !counts) return SUMA_OK;
+  return live_words(l, 0, LIVE_COUNT_WORDS, counts);
+}
+
+extern "C" int suma_localizer_live_cells_device(suma_localizer* l, suma_grid_cell* d_out_cells, uint8_t* d_out_mask,
+                                                suma_live_stats* stats) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = live_ready(l, "suma_localizer_live_cells_device");
+  if (r) return r;
+  if (!d_out_cells) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_cells_device: NULL cells");
+  if ((uintptr_t)d_out_cells & 15u) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_cells_device: cells not 16-byte aligned");
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if ((r = live_compose(c, l->lv, d_out_cells, d_out_mask))) return r;
+  suma_live_stats st;
+  if ((r = live_words(l, LIVE_STATS, LIVE_STAT_WORDS, &st))) return r;
+  if (stats) *stats = st;
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_live_state(suma_localizer* l, suma_live_cell* host, uint32_t capacity, uint32_t* n) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = live_ready(l, "suma_localizer_live_state");
+  if (r) return r;
+  if (!n || (capacity && !host)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_state: NULL argument");
+  *n = l->lv.n_cells;
+  const uint32_t m = *n < capacity ? *n : capacity;
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(host, l->lv.state, (size_t)m * sizeof(suma_live_cell), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_set_live_state(suma_localizer* l, const suma_live_cell* host, uint32_t n, uint32_t last_stamp) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = live_ready(l, "suma_localizer_set_live_state");
+  if (r) return r;
+  if (!host) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_live_state: NULL argument");
+  Live& lv = l->lv;
+  if (n != lv.n_cells)
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_live_state: " + std::to_string(n) + " cells, the raster has " +
+                                     std::to_string(lv.n_cells));
+  uint32_t any = 0u;
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t H = (uint32_t)(host[k].hit >> 32);
+    if (H > last_stamp || host[k].clear > last_stamp)
+      return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_live_state: cell " + std::to_string(k) + " carries a stamp above last_stamp");
+    any |= H != 0u ? 1u : 0u;
+  }
+  if ((r = live_clear(c, lv))) return r;
+  HIP_TRY(c, hipMemcpyAsync(lv.state, host, (size_t)n * sizeof(suma_live_cell), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(lv.words.p + LIVE_ANY_HIT, &any, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream)); /* pageable sources: the copies have left them */
+  lv.last_stamp = last_stamp;
+  return SUMA_OK;
 }

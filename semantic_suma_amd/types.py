@@ -411,6 +411,47 @@ SCAN_OBJECT_DTYPE = np.dtype([("root", "<u4"), ("n_texels", "<u4"), ("label", "<
 assert SCAN_OBJECT_DTYPE.itemsize == 64
 
 
+class LiveParams(C.Structure):
+    """``struct suma_live_params``: how long a hit keeps a cell of the live obstacle layer an obstacle, how many hits in
+    a row it takes, and how far a scan's rays clear cells (csrc/k_live.hip); ``LiveParams.defaults()`` =
+    suma_live_params_default"""
+    _fields_ = [("hold_scans", u32), ("min_hits", u32), ("carve_range", f32), ("carve_margin", f32)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "LiveParams":
+        p = cls(hold_scans=10, min_hits=2, carve_range=20.0, carve_margin=0.5)
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        return p
+
+
+class LiveCounts(C.Structure):
+    """``struct suma_live_counts``: what one update of the live layer made of the texels of the frame"""
+    _fields_ = [("n_texels", u32), ("n_members", u32), ("n_outside", u32), ("n_no_ground", u32), ("n_low", u32),
+                ("n_high", u32), ("n_hit_texels", u32), ("n_hit_cells", u32), ("n_rays", u32), ("n_cleared", u32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class LiveStats(C.Structure):
+    """``struct suma_live_stats``: the cells with a hit by what a compose made of them"""
+    _fields_ = [("n_live", u32), ("n_pending", u32), ("n_expired", u32), ("n_carved", u32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+LIVE_COUNTS = tuple(k for k, _ in LiveCounts._fields_)
+LIVE_STATS = tuple(k for k, _ in LiveStats._fields_)
+# numpy view of ``struct suma_live_cell``: the raw state of one cell of the live layer
+LIVE_CELL_DTYPE = np.dtype([("hit", "<u8"), ("clear", "<u4"), ("hits", "<u4")])
+assert LIVE_CELL_DTYPE.itemsize == 16
+LIVE_MASK_LIVE, LIVE_MASK_PENDING = 1, 2
+
+
 PLACE_MAX_DIM = 64       # SUMA_PLACE_MAX_DIM: rings and sectors
 PLACE_MAX_MATCHES = 32   # SUMA_PLACE_MAX_MATCHES
 # is_dynamic_label (csrc/dev_math.h): the moving classes K1 drops at the start of a run

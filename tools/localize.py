@@ -13,7 +13,10 @@ objects out of the synthetic world the localised scans see).  --novel collects t
 (all of them without --evidence) followed by the fused new ones (--map-without takes objects out of the world the mapping
 run sees).  --objects (with --novel) segments each scan's unexplained texels into objects (csrc/k_objects.hip) and prints,
 per scan, their number and each one's class, size, centroid and nearest range; --objects-out writes them as JSON.  --deskew motion compensates the localised scans with the localiser's last increment (csrc/k_deskew.hip), for
-sensors that deliver raw sweeps.  With --relocalize the first scan goes through Localizer.relocalize against a place index (core.PlaceIndex) -- the mapping
+sensors that deliver raw sweeps.  --live-grid GRID.npz (with --novel) switches the live obstacle layer on (csrc/k_live.hip) over
+the traversability grid in GRID.npz (mapio.write_grid; a file that does not exist is made from the map as mapped, at
+--grid-cell metres, and written), prints every scan's counts and live cells and, with --goal X Y, the path cost from the
+robot's cell to the goal on the static grid and on the live one; --live-out writes the last composed grid.  With --relocalize the first scan goes through Localizer.relocalize against a place index (core.PlaceIndex) -- the mapping
 run's own scans, or with --map the file tools/export_map.py --places wrote (--places).  Needs a GPU.
     python tools/localize.py [--map-scans 80] [--first 10] [--scans 60] [--voxel 0.1] [--width 2048] [--kitti sequences/08]
     python tools/localize.py --map map.ply --start 12.0 0.5 0.0 3.0 --first 11 --scans 20
@@ -23,6 +26,7 @@ run's own scans, or with --map the file tools/export_map.py --places wrote (--pl
     python tools/localize.py --evidence --without 2 41 --prune-out pruned.ply   # cube 2 and a building are gone
     python tools/localize.py --map-without 2 41 --novel --update-out new.ply    # cube 2 and a building have arrived
     python tools/localize.py --map-without 2 41 --novel --objects [--objects-out objects.json]   # ... as objects, per scan
+    python tools/localize.py --map-without 2 41 --novel --objects --live-grid grid.npz --goal 60 -8   # ... in the planner's grid
     python tools/localize.py --kitti raw/sequence --deskew   # raw (uncompensated) sweeps: corrected in front of K1
 """
 import argparse
@@ -99,10 +103,11 @@ def observe_timing(loc, scan, pose, n_window):
                 observe_over_copy=round(k / c, 3), samples=dict(kc_observe_ms=kernel, d2d_copy_ms=copy))
 
 
-def collect_timing(loc, scan, pose, n_window):
+def collect_timing(loc, scan, pose, n_window, scan_id=0):
     """kn_mark's and kn_collect + kn_emit's event times (suma_profile, one collection at a time) against event-timed
     device-to-device copies of the bytes they touch: 32 a window record (16 of its position, 16 of the vertex texel) for
-    the marks; the frame's three maps, nine mark bytes and a flag byte a texel for the collection"""
+    the marks; the frame's three maps, nine mark bytes and a flag byte a texel for the collection.  ``scan_id``: the first of
+    the collections' ids, which count up (the live layer wants them above the run's)"""
     ctx, p = loc.ctx, loc.params
     frame = core.Frame(ctx, p.data_width, p.data_height)
     core.Preprocessing(ctx).process(scan[0], frame, scan[1], scan[2], p.active_timestamps + 10)
@@ -111,7 +116,7 @@ def collect_timing(loc, scan, pose, n_window):
     mark, collect = [], []
     for k in range(13):
         ctx.profile_reset()
-        loc.collectFrame(frame, pose, 0)
+        loc.collectFrame(frame, pose, scan_id + k)
         ms = {r["name"]: r["total_ms"] for r in ctx.profile_get()}
         if k >= 3:
             mark.append(ms["novel_mark"])
@@ -132,7 +137,7 @@ def collect_timing(loc, scan, pose, n_window):
     return out
 
 
-def objects_timing(loc, scan, pose):
+def objects_timing(loc, scan, pose, scan_id=0):
     """the event times of one segmentation's two kernel groups (suma_profile: kob_init + kob_merge + kob_flatten, and
     kob_vote + kob_emit + kob_ids) over the flags of one collection, each against an event-timed device-to-device copy of
     the bytes it touches (about 150 and 40 a texel: the vertex and semantic texels, the labels, the vote table, the ids; 96
@@ -146,7 +151,7 @@ def objects_timing(loc, scan, pose):
     frame = core.Frame(ctx, W, H)
     core.Preprocessing(ctx).process(scan[0], frame, scan[1], scan[2], p.active_timestamps + 10)
     held = loc.novelCandidates(allow_overflow=True)
-    loc.collectFrame(frame, pose, 0)
+    loc.collectFrame(frame, pose, scan_id)
     loc.setNovelCandidates(held)
     flags = loc.novelFlags()
     ctx.profile(1)
@@ -202,6 +207,96 @@ def objects_timing(loc, scan, pose):
     return out
 
 
+def live_timing(loc, scan, pose, live):
+    """the event times of the live layer's three kernels (suma_profile: klv_hit, klv_carve, klv_compose) over the flags of
+    one collection -- each update with a stamp of its own on the state the run left --, each against an event-timed
+    device-to-device copy of the bytes it touches (hit: the vertex texel, the flag and the id, 21 a texel; carve: the
+    vertex texel, 16 a texel, and what the rays read, which depends on the scene and is left out; compose: 48 + 16 read and
+    48 + 1 written a cell), and the host route timed in the same run: the flag, vertex and id images downloaded, then
+    tests/live_shim.c (gcc -O2, one thread) over them"""
+    import subprocess
+    import tempfile
+    from semantic_suma_amd.types import LIVE_CELL_DTYPE, LiveCounts, LiveParams
+    ctx, p = loc.ctx, loc.params
+    W, H = p.data_width, p.data_height
+    gp = live["gp"]
+    n_cells = int(gp.width) * int(gp.height)
+    frame = core.Frame(ctx, W, H)
+    core.Preprocessing(ctx).process(scan[0], frame, scan[1], scan[2], p.active_timestamps + 10)
+    flags = loc.novelFlags()
+    d_cells = ctx.device_array(np.zeros(n_cells * 48, dtype=np.uint8))
+    base = 1 << 20                                     # scan ids far above the run's
+    ctx.profile(1)
+    hit, carve, compose = [], [], []
+    for k in range(13):
+        ctx.profile_reset()
+        counts = loc.liveUpdateFlags(frame, pose, flags, base + k)
+        stats = loc.liveCells(out=d_cells)[2]
+        ms = {r["name"]: r["total_ms"] for r in ctx.profile_get()}
+        if k >= 3:
+            hit.append(ms["live_hit"])
+            carve.append(ms.get("live_carve", 0.0))
+            compose.append(ms["live_compose"])
+    ctx.profile(0)
+    ctx.device_free(d_cells)
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    out = dict(counts=counts, stats=stats, cells=n_cells)
+    for name, nbytes, kernel in (("hit", 21 * W * H, hit), ("carve", 16 * W * H, carve), ("compose", 113 * n_cells, compose)):
+        src, dst = ctx.device_array(np.zeros(nbytes, dtype=np.uint8)), ctx.device_array(np.zeros(nbytes, dtype=np.uint8))
+        copy = event_ms(ctx, lambda: hip.hipMemcpyAsync(dst, src, nbytes, 3, C.c_void_p(ctx.stream)))
+        ctx.device_free(src)
+        ctx.device_free(dst)
+        k, c = float(np.median(kernel)), float(np.median(copy))
+        out[name] = dict(bytes=nbytes, kernel_us_median10=round(1e3 * k, 2), d2d_copy_us_median10=round(1e3 * c, 2),
+                         kernel_over_copy=round(k / c, 3), samples=dict(kernel_ms=kernel, d2d_copy_ms=copy))
+    # the host route: one more update on the device and on the host from the same state
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tests"))
+    import live_common as lv
+    with tempfile.TemporaryDirectory() as tmp:
+        shim = lv.build_shim(tmp)
+        download, host = [], []
+        same = True
+        for k in range(13):
+            layer = lv.ShimLayer(shim, live["static"], gp, live["lp"])
+            layer.set_state(loc.liveState(), base + 12 + k)
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            fl, V = loc.novelFlags(), frame.download(0)
+            ids = loc.objectIds() if live["objects"] else None
+            t1 = time.perf_counter()
+            layer.update(V, fl, pose, base + 13 + k, ids)
+            comp = layer.compose()
+            t2 = time.perf_counter()
+            loc.liveUpdateFlags(frame, pose, flags, base + 13 + k)
+            got = loc.liveCells()
+            same = same and got[0].tobytes() == comp[0].tobytes() and loc.liveState().tobytes() == layer.state().tobytes()
+            if k >= 3:
+                download.append(1e3 * (t1 - t0))
+                host.append(1e3 * (t2 - t1))
+    out["host_route"] = dict(download_us_median10=round(1e3 * float(np.median(download)), 2),
+                             shim_us_median10=round(1e3 * float(np.median(host)), 2), equals_device=bool(same),
+                             samples=dict(download_ms=download, shim_ms=host))
+    return out
+
+
+def added_footprints(gp, boxes):
+    """bool per cell: the centre lies inside the x / y extent of one of synth._boxes(0)'s ``boxes`` (the grid's frame is
+    that of scan 0)"""
+    c, h, yaw, _ = synth._boxes(0)
+    T0 = synth.trajectory_pose(0)
+    ix, iy = np.meshgrid(np.arange(gp.width), np.arange(gp.height))
+    xyz = np.stack([gp.origin_x + (ix + 0.5) * gp.cell_size, gp.origin_y + (iy + 0.5) * gp.cell_size, np.zeros(ix.shape)],
+                   -1).reshape(-1, 3) @ T0[:3, :3].T + T0[:3, 3]
+    out = np.zeros(len(xyz), dtype=bool)
+    for b in boxes:
+        cs, sn = np.cos(yaw[b]), np.sin(yaw[b])
+        q = (xyz - c[b]) @ np.array([[cs, sn, 0], [-sn, cs, 0], [0, 0, 1]]).T
+        out |= np.all(np.abs(q[:, :2]) <= h[b][:2], axis=1)
+    return out
+
+
 def pose_from(x, y, z, yaw_deg):
     a = np.deg2rad(yaw_deg)
     T = np.eye(4)
@@ -247,7 +342,19 @@ def main():
     ap.add_argument("--objects-out", default=None, metavar="FILE.json", help="with --objects: write every scan's objects")
     ap.add_argument("--map-without", type=int, nargs="*", default=[], metavar="BOX",
                     help="synthetic scans: boxes of synth._boxes the mapping run does not see")
+    ap.add_argument("--live-grid", default=None, metavar="GRID.npz",
+                    help="with --novel: the live obstacle layer over this traversability grid (made from the map and written "
+                         "when the file does not exist)")
+    ap.add_argument("--grid-cell", type=float, default=0.2, help="cell size of a grid --live-grid makes, in metres")
+    ap.add_argument("--live-out", default=None, metavar="FILE.npz", help="with --live-grid: write the last composed grid")
+    ap.add_argument("--goal", type=float, nargs=2, metavar=("X", "Y"), default=None,
+                    help="with --live-grid: print per scan the path cost from the robot's cell to this world position on "
+                         "the static grid and on the live one (unknown cells count as traversable)")
     args = ap.parse_args()
+    if args.live_grid and not args.novel:
+        ap.error("--live-grid needs --novel")
+    if (args.live_out or args.goal) and not args.live_grid:
+        ap.error("--live-out and --goal need --live-grid")
     if args.prune_out and not args.evidence:
         ap.error("--prune-out needs --evidence")
     if args.update_out and not args.novel:
@@ -317,6 +424,24 @@ def main():
     if args.deskew:
         loc.enableDeskew()
         res["deskew"] = True
+    live = None
+    if args.live_grid:
+        from semantic_suma_amd.types import LiveParams, PlanParams
+        if os.path.exists(args.live_grid):
+            cells, gp = mapio.read_grid(args.live_grid)
+        else:
+            cells, gp, _ = core.world_grid(loc.ctx, records, cell_size=args.grid_cell)
+            mapio.write_grid(args.live_grid, cells, gp)
+        loc.enableLiveGrid(cells, gp)
+        live = dict(gp=gp, static=cells, lp=LiveParams.defaults(), objects=bool(args.objects), per_scan=[], d_cells=loc.ctx.device_array(np.zeros(cells.size * 48, dtype=np.uint8)))
+        res["live_grid"] = dict(file=args.live_grid, width=int(gp.width), height=int(gp.height), cell_size=float(gp.cell_size))
+        if args.goal:
+            live["pp"] = PlanParams.defaults(unknown_blocked=False)
+            live["goal"] = core.grid_cell_index(gp, *args.goal)
+            if live["goal"] < 0:
+                ap.error("--goal lies outside the grid")
+            live["static_field"] = core.grid_plan(loc.ctx, cells, gp, [live["goal"]], live["pp"])[0]
+            live["added"] = added_footprints(gp, args.map_without) if args.map_without and not args.kitti else None
     t = time.perf_counter()
     dropped = loc.setMap(records)
     res.update(map_records=int(len(records)), dropped=dropped, set_map_ms=round(1e3 * (time.perf_counter() - t), 3))
@@ -354,6 +479,22 @@ def main():
                 collections.append(loc.lastCollection(allow_overflow=True))
             if args.objects and not args.timing:
                 objects.append(loc.objects(allow_overflow=True))
+            if live and not args.timing:
+                gp, T = live["gp"], out[-1]["pose"]
+                entry = dict(scan=k, counts=loc.liveCounts())
+                _, mask, entry["stats"] = loc.liveCells(out=live["d_cells"])
+                if args.goal:
+                    start = core.grid_cell_index(gp, float(T[0, 3]), float(T[1, 3]))
+                    field = core.grid_plan(loc.ctx, live["d_cells"], gp, [live["goal"]], live["pp"])[0]
+                    if start >= 0:
+                        entry["static_cost"] = int(live["static_field"].reshape(-1)["cost"][start])
+                        entry["live_cost"] = int(field.reshape(-1)["cost"][start])
+                        pres, prow = core.grid_paths(loc.ctx, field, gp, [start])
+                        path = prow[0, :min(int(pres["length"][0]), prow.shape[1])]
+                        entry["path_cells"] = int(len(path))
+                        if live["added"] is not None:
+                            entry["path_cells_in_added_boxes"] = int(live["added"][path].sum())
+                live["per_scan"].append(entry)
         except core.SumaError as e:  # a run that has left the map ends on a pose that is no longer finite
             res.update(lost_at_scan=k, error=str(e))
             break
@@ -413,6 +554,22 @@ def main():
             with open(args.objects_out, "w") as f:
                 json.dump(listing, f)
             res["objects_file"] = args.objects_out
+    if live:
+        for e in live["per_scan"]:
+            c, st = e["counts"] or {}, e["stats"]
+            line = (f"scan {e['scan']:5d}  live {st['n_live']}  pending {st['n_pending']}  expired {st['n_expired']}  carved "
+                    f"{st['n_carved']}  hit texels {c.get('n_hit_texels', 0)}  hit cells {c.get('n_hit_cells', 0)}  cleared "
+                    f"{c.get('n_cleared', 0)}")
+            if "live_cost" in e:
+                line += f"  path cost static {e['static_cost']}  live {e['live_cost']}  cells {e['path_cells']}"
+                if "path_cells_in_added_boxes" in e:
+                    line += f"  of them in the added boxes {e['path_cells_in_added_boxes']}"
+            print(line)
+        comp, mask, st = loc.liveCells()
+        res["live"] = dict(last=st, per_scan=[e["stats"]["n_live"] for e in live["per_scan"]] or None)
+        if args.live_out:
+            mapio.write_grid(args.live_out, comp, live["gp"])
+            res["live_file"] = args.live_out
     origin, n_window, rebuilds = loc.window()
     res.update(tracked=sum(r["tracked"] for r in out), window_rebuilds=sum(r["window_rebuilt"] for r in out),
                n_window=n_window, worst_distance_to_mapping_pose_m=round(worst, 4))
@@ -430,9 +587,11 @@ def main():
         if args.evidence and "lost_at_scan" not in res:
             res["observe"] = observe_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], loc.window()[1])
         if args.novel and "lost_at_scan" not in res:
-            res["collect"] = collect_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], loc.window()[1])
+            res["collect"] = collect_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], loc.window()[1], (1 << 18) if live else 0)
         if args.objects and "lost_at_scan" not in res:
-            res["segment"] = objects_timing(loc, host_scans[len(out) - 1], out[-1]["pose"])
+            res["segment"] = objects_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], (1 << 19) if live else 0)
+        if live and "lost_at_scan" not in res:
+            res["live_timing"] = live_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], live)
     loc.close()
     print(json.dumps(res))
 
