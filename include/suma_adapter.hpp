@@ -922,6 +922,41 @@ class Localizer {
     chk(suma_localizer_segment_flags(l_, frame, T, flags, scan_id, &c), "Localizer::segmentFlags");
     return c;
   }
+  /* tracks (csrc/k_tracks.hip): with objects on, every segmentation is followed by one tracker update -- fragments joined
+   * into detections, detections associated to tracks, ids kept, velocities filtered; nothing else the localiser gives
+   * changes */
+  void enableTracks(const suma_track_params* tp = nullptr) { chk(suma_localizer_enable_tracks(l_, tp), "Localizer::enableTracks"); }
+  void disableTracks() { chk(suma_localizer_disable_tracks(l_), "Localizer::disableTracks"); }
+  void clearTracks() { chk(suma_localizer_clear_tracks(l_), "Localizer::clearTracks"); }
+  /* the live tracks of the last update in ascending slot order; *updated = false (and nothing returned) when there was
+   * none.  Throws when detections found no free slot */
+  std::vector<suma_object_track> tracks(suma_track_counts* counts = nullptr, bool* updated = nullptr) {
+    uint32_t n = 0;
+    int32_t upd = 0;
+    suma_track_counts c;
+    int rc = suma_localizer_tracks(l_, nullptr, 0, &n, &c, &upd);
+    if (rc != SUMA_ERR_CAPACITY) chk(rc, "Localizer::tracks");
+    std::vector<suma_object_track> out(n);
+    if (n) chk(suma_localizer_tracks(l_, out.data(), n, &n, &c, &upd), "Localizer::tracks");
+    else chk(rc, "Localizer::tracks");
+    if (counts) *counts = c;
+    if (updated) *updated = upd != 0;
+    return out;
+  }
+  /* per object of the last update the id of its track, 0 for none: objectTracks()[objectIds()[texel]] is a texel's track */
+  std::vector<uint32_t> objectTracks() {
+    uint32_t n = 0;
+    chk(suma_localizer_object_tracks(l_, nullptr, 0, &n), "Localizer::objectTracks");
+    std::vector<uint32_t> out(n);
+    if (n) chk(suma_localizer_object_tracks(l_, out.data(), n, &n), "Localizer::objectTracks");
+    return out;
+  }
+  /* the primitive on a caller's records in place of a segmentation's */
+  suma_track_counts trackObjects(const std::vector<suma_scan_object>& objects, uint32_t scan_id) {
+    suma_track_counts c;
+    chk(suma_localizer_track_objects(l_, objects.data(), (uint32_t)objects.size(), scan_id, &c), "Localizer::trackObjects");
+    return c;
+  }
   /* live obstacles for the planner (csrc/k_live.hip): with novelty on, every collection is followed by one update of a
    * layer over the static grid gp / cells (host cells, uploaded for the call); nothing else the localiser gives changes */
   void enableLiveGrid(const suma_grid_params& gp, const std::vector<suma_grid_cell>& cells, const suma_live_params* lp = nullptr) {

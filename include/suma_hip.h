@@ -1101,8 +1101,8 @@ int suma_localizer_clear_novelty(suma_localizer* l);
  *      64-byte record: class, box, centroid, nearest range.  The records are those of the LAST segmentation; they are
  *      not accumulated, enter no checkpoint, and neither the grid nor the planner reads them.  csrc/k_objects.hip states
  *      the fp32 specification, tests/object_shim.c restates it; DESIGN.md 19 has the decomposition and what is out of
- *      scope (tracking, velocities, oriented boxes).  With objects on every other output of the localiser is
- *      bit-identical to a run with them off. */
+ *      scope (oriented boxes; tracking across scans and velocities are the tracks block below).  With objects on every
+ *      other output of the localiser is bit-identical to a run with them off. */
 typedef struct suma_object_params {
   float link_base;       /* default 0.3 m: neighbouring texels this close belong together at any range; finite, >= 0 */
   float link_slope;      /* default 0.03: ... plus this much per metre of the nearer texel's range; finite, >= 0 */
@@ -1169,8 +1169,8 @@ int suma_localizer_segment_flags(suma_localizer* l, const suma_frame* frame, con
  *      Composing gives the static cells with the live obstacles written into them, in the suma_grid_cell layout:
  *      suma_grid_plan_field takes the result unchanged.  csrc/k_live.hip states the specification, tests/live_shim.c
  *      restates it; DESIGN.md 20 has the decomposition and what is out of scope (the layer in checkpoints and during
- *      mapping, exact cell traversal, tracking).  The scan path, the candidates, the objects, the grid and the planner
- *      keep their results bit for bit. */
+ *      mapping, exact cell traversal; the objects are tracked by the tracks block below, the layer does not read
+ *      them).  The scan path, the candidates, the objects, the grid and the planner keep their results bit for bit. */
 typedef struct suma_live_params {
   uint32_t hold_scans;   /* default 10: a hit keeps its cell an obstacle for this many scans; 1 .. 65 535 */
   uint32_t min_hits;     /* default 2: hits in a row (none further apart than hold_scans) before a cell is live; 1 .. 65 535 */
@@ -1229,6 +1229,104 @@ int suma_localizer_live_state(suma_localizer* l, suma_live_cell* host, uint32_t 
 /* replaces the raw state (n = width * height cells) and the last stamp: a saved layer put back, and how the tests reach
  * states that would take 65 535 updates.  Blocking. */
 int suma_localizer_set_live_state(suma_localizer* l, const suma_live_cell* host, uint32_t n, uint32_t last_stamp);
+
+/* ---- tracks: "is the car of this scan the car of the last one, and where is it going?"  With objects on, a tracker
+ *      can follow every segmentation on the ctx stream with one update: the objects of the scan are joined into
+ *      detections (fragments of one thing: same class, boxes no further apart than join_dist), the detections are
+ *      associated to the tracks of the scans before (greedy by distance to the predicted position, inside a gate that
+ *      widens while a track is not seen), matched tracks are filtered (alpha-beta), unmatched ones coast and expire,
+ *      unmatched detections found new tracks.  A track keeps its id while it lives.  The update is enqueued only; the
+ *      scan path does not wait for it, and everything else the localiser gives is bit-identical to a run with tracks
+ *      off.  csrc/k_tracks.hip states the fp32 specification, tests/track_shim.c restates it; DESIGN.md 21 has the
+ *      decomposition and what is out of scope (oriented boxes, optimal assignment, class- or size-aware gating,
+ *      predicted occupancy, tracks in checkpoints and during mapping). */
+typedef struct suma_track_params {
+  float join_dist;       /* default 2 m: objects of one class whose boxes are this close are one detection; not NaN,
+                            <= 1e6; negative: joining off */
+  float gate_base;       /* default 1.5 m: a detection this close to a track's predicted position may be the track; 0 .. 1e6 */
+  float gate_speed;      /* default 0.5 m: ... plus this much per scan-id step since the track was last matched; 0 .. 1e6 */
+  float alpha;           /* default 0.5: the share of the residual the position takes; 0 .. 1 */
+  float beta;            /* default 0.2: ... and the velocity, per step; 0 .. 2 */
+  uint32_t confirm_hits; /* default 3: matches (the founding one included) before a track is confirmed; 1 .. 65 535 */
+  uint32_t max_missed;   /* default 3: a track is dropped at its (max_missed + 1)-th update in a row without a match; 0 .. 65 535 */
+  uint32_t max_tracks;   /* default 1024 (112 bytes each): the slots of the table; 1 .. 4096 */
+  uint32_t max_rounds;   /* default 16: the rounds of mutual picks one association runs at most; 1 .. 64 */
+} suma_track_params;
+#define SUMA_TRACK_FREE 0u
+#define SUMA_TRACK_TENTATIVE 1u
+#define SUMA_TRACK_CONFIRMED 2u
+#define SUMA_TRACK_NO_DETECTION 0xffffffffu
+/* one slot of the table, 112 bytes; stamps are scan_id + 1 of an update; velocities in metres per scan-id step */
+typedef struct suma_object_track {
+  uint32_t id;           /* 1, 2, ...: never given twice between two clears; 0 in a free slot */
+  uint32_t slot;         /* the index of this record in the table */
+  uint32_t state;        /* SUMA_TRACK_FREE, _TENTATIVE or _CONFIRMED */
+  uint32_t label;        /* of the detection matched last, as are n_texels .. r_min below */
+  uint32_t n_texels, n_dynamic;
+  uint32_t n_objects;    /* the fragments (suma_scan_object records) that detection was joined from */
+  uint32_t hits;         /* matches, the founding one included; saturates at 65 535 */
+  uint32_t missed;       /* updates in a row without a match */
+  uint32_t first_stamp;  /* of the founding update */
+  uint32_t last_matched; /* stamp of the last match */
+  float position[3];     /* filtered; the prediction while the track is not seen */
+  float velocity[3];
+  float origin[3];       /* the founding detection's centroid: (position - origin) / (last_matched - first_stamp) is
+                            the net velocity over the track's life */
+  float min[3], max[3];  /* the joined box */
+  float r_min;
+  uint32_t detection;    /* the detection of this update the track matched or was founded by, else 0xffffffff */
+} suma_object_track;
+/* one update.  n_objects = n_detections + n_joined; n_detections = n_matched + n_born + n_dropped;
+ * n_tracks_before = n_matched + n_missed; n_expired <= n_missed; the tracks alive afterwards number
+ * n_tracks_before - n_expired + n_born, n_confirmed of them confirmed; rounds <= max_rounds, and n_unresolved > 0 only
+ * with rounds = max_rounds */
+typedef struct suma_track_counts {
+  uint32_t n_objects, n_detections, n_joined, n_tracks_before, n_matched, n_missed, n_expired, n_born, n_dropped,
+      n_confirmed, n_unresolved, rounds;
+} suma_track_counts;
+/* 2.0f, 1.5f, 0.5f, 0.5f, 0.2f, 3, 3, 1024, 16 */
+void suma_track_params_default(suma_track_params* tp);
+/* host only, no device: SUMA_OK, or SUMA_ERR_INVALID for values outside the ranges above, the text in
+ * suma_last_error(NULL).  suma_localizer_enable_tracks applies the same rule. */
+int suma_track_params_check(const suma_track_params* tp);
+/* switches tracks on (tp NULL = the defaults) and allocates their blocks (about 160 bytes an object of max_objects, 250
+ * bytes a slot).  Needs objects on: SUMA_ERR_INVALID otherwise, and for values outside the ranges above, with a message
+ * and nothing launched.  Enabling again replaces the parameters and forgets the tracks; so does enabling objects again
+ * with another max_objects. */
+int suma_localizer_enable_tracks(suma_localizer* l, const suma_track_params* tp);
+/* switches them off and gives the blocks back; suma_localizer_disable_objects and _disable_novelty do this too */
+int suma_localizer_disable_tracks(suma_localizer* l);
+/* no tracks, the last stamp is 0, the next id is 1; suma_localizer_set_map and _clear_novelty do this too */
+int suma_localizer_clear_tracks(suma_localizer* l);
+/* With tracks on, every segmentation -- a collection's, suma_localizer_segment_flags' or _live_update_flags' -- is
+ * followed by one update at the stamp scan_id + 1; it is only enqueued.  A scan_id whose stamp is not greater than the
+ * last update's returns SUMA_ERR_INVALID and launches nothing, the segmentation included.  These return the live
+ * tracks of the last update in ascending slot order: *n = their number, min(*n, capacity) are copied; *counts and
+ * *updated are optional; without an update since the tracks were enabled, cleared or set, *n = 0, the counts are 0 and
+ * *updated = 0.  Blocking.  SUMA_ERR_CAPACITY after filling the outputs when n_dropped > 0 (the downloads' convention). */
+int suma_localizer_tracks(suma_localizer* l, suma_object_track* host, uint32_t capacity, uint32_t* n,
+                          suma_track_counts* counts, int32_t* updated);
+int suma_localizer_tracks_device(suma_localizer* l, suma_object_track* d_out, uint32_t capacity, uint32_t* n,
+                                 suma_track_counts* counts, int32_t* updated);
+/* per object the last update read (the stored objects of its segmentation, in their order): the id of the track its
+ * detection matched or founded, 0 for none (the detection was dropped).  *n = their number (0 without an update),
+ * min(*n, capacity) are copied.  Blocking.  Texel -> object (suma_localizer_object_ids) -> track is two look-ups. */
+int suma_localizer_object_tracks(suma_localizer* l, uint32_t* host, uint32_t capacity, uint32_t* n);
+/* the primitive on a caller's records (host) in place of a segmentation's, the counterpart of
+ * suma_localizer_segment_flags: one update at the stamp scan_id + 1 over n <= max_objects records.  It needs no map,
+ * frame or pose.  *counts is optional.  Blocking.  The stamp rule above applies. */
+int suma_localizer_track_objects(suma_localizer* l, const suma_scan_object* host_objects, uint32_t n, uint32_t scan_id,
+                                 suma_track_counts* counts);
+/* the raw table, one suma_object_track a slot: *n = max_tracks, min(*n, capacity) are copied; *last_stamp and *next_id
+ * are optional.  Blocking. */
+int suma_localizer_track_state(suma_localizer* l, suma_object_track* host, uint32_t capacity, uint32_t* n,
+                               uint32_t* last_stamp, uint32_t* next_id);
+/* replaces the raw table (n = max_tracks slots), the last stamp and the next id: a saved tracker put back, and how the
+ * tests reach saturated hits, non-finite states and a full table.  A slot is checked for: state <= 2, and in a live
+ * slot 1 <= id < next_id, first_stamp <= last_matched <= last_stamp; ids are not checked for being distinct.
+ * Afterwards there is "no update" until the next one.  Blocking. */
+int suma_localizer_set_track_state(suma_localizer* l, const suma_object_track* host, uint32_t n, uint32_t last_stamp,
+                                   uint32_t next_id);
 
 /* ---- place recognition and global relocalisation: "the sensor was switched on somewhere inside yesterday's map".  A
  *      place index holds one descriptor per scan of a mapping session: a polar height map about the sensor (sectors x

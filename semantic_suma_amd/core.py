@@ -37,7 +37,7 @@ from .types import (ACC_WORDS, DRAW_COLORS, DRAW_LIGHTS, DRAW_MATERIAL, DRAW_MAX
                     GRID_CELL_DTYPE, GridParams, GridStats,
                     PLAN_CELL_DTYPE, PLAN_PATH_DTYPE, PATH_OK, PATH_TRUNCATED, PlanParams, PlanStats,
                     ChangeCounts, ChangeParams, ChangeRule, DeskewParams, EVIDENCE_DTYPE, NovelCounts, NovelFuseParams, NovelParams, NovelStats,
-                    ObjectCounts, ObjectParams, SCAN_OBJECT_DTYPE, LIVE_CELL_DTYPE, LiveCounts, LiveParams, LiveStats, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
+                    ObjectCounts, ObjectParams, SCAN_OBJECT_DTYPE, OBJECT_TRACK_DTYPE, ObjectTrack, TrackCounts, TrackParams, LIVE_CELL_DTYPE, LiveCounts, LiveParams, LiveStats, LocalizerParams, LocalizerResult, PLACE_MAX_MATCHES, PlaceMatch, PlaceParams, RelocalizeResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SUMA_HIP_LIB selects another build of the same library (A/B timing of kernel variants in one GPU session)
@@ -338,6 +338,19 @@ def lib():
     L.suma_localizer_novel_flags.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.suma_localizer_frame.argtypes = [vp]
     L.suma_localizer_frame.restype = vp
+    tpp, tcp, u32p = C.POINTER(TrackParams), C.POINTER(TrackCounts), C.POINTER(u32)
+    L.suma_track_params_default.argtypes = [tpp]
+    L.suma_track_params_default.restype = None
+    L.suma_track_params_check.argtypes = [tpp]
+    L.suma_localizer_enable_tracks.argtypes = [vp, tpp]
+    L.suma_localizer_disable_tracks.argtypes = [vp]
+    L.suma_localizer_clear_tracks.argtypes = [vp]
+    L.suma_localizer_tracks.argtypes = [vp, vp, u32, u32p, tcp, C.POINTER(i32)]
+    L.suma_localizer_tracks_device.argtypes = [vp, vp, u32, u32p, tcp, C.POINTER(i32)]
+    L.suma_localizer_object_tracks.argtypes = [vp, vp, u32, u32p]
+    L.suma_localizer_track_objects.argtypes = [vp, vp, u32, u32, tcp]
+    L.suma_localizer_track_state.argtypes = [vp, vp, u32, u32p, u32p, u32p]
+    L.suma_localizer_set_track_state.argtypes = [vp, vp, u32, u32, u32]
     lvp, lcp = C.POINTER(LiveParams), C.POINTER(LiveCounts)
     L.suma_live_params_default.argtypes = [lvp]
     L.suma_live_params_default.restype = None
@@ -2254,6 +2267,83 @@ class Localizer(_DeskewSwitch):
         st = np.ascontiguousarray(state, dtype=LIVE_CELL_DTYPE).reshape(-1)
         self.ctx.check(self.L.suma_localizer_set_live_state(self.h, _ptr(st), st.shape[0], last_stamp),
                        "suma_localizer_set_live_state")
+
+    # -- tracks: the objects of the scans tied together (csrc/k_tracks.hip)
+    def enableTracks(self, params: TrackParams = None):
+        """from now on every segmentation (objects must be on) is followed by one tracker update: fragments joined into
+        detections, detections associated to tracks, ids kept, velocities filtered; nothing else the localiser gives
+        changes"""
+        self.ctx.check(self.L.suma_localizer_enable_tracks(self.h, None if params is None else C.byref(params)),
+                       "suma_localizer_enable_tracks")
+        self._track_params = TrackParams.defaults() if params is None else TrackParams.from_buffer_copy(params)
+
+    def disableTracks(self):
+        self.ctx.check(self.L.suma_localizer_disable_tracks(self.h), "suma_localizer_disable_tracks")
+
+    def clearTracks(self):
+        """no tracks, the next id is 1; setMap and clearNovelty do this too"""
+        self.ctx.check(self.L.suma_localizer_clear_tracks(self.h), "suma_localizer_clear_tracks")
+
+    def tracks(self, allow_overflow: bool = False, out=None):
+        """(OBJECT_TRACK_DTYPE records of the live tracks in ascending slot order, the suma_track_counts dict) of the last
+        update, or None when there was none.  Detections that found no free slot raise unless ``allow_overflow``.
+        ``out``: a device address / torch tensor with room for max_tracks records to leave the records at; the return
+        is then (their number, counts)"""
+        n, cnt, upd = C.c_uint32(0), TrackCounts(), C.c_int32(0)
+        self._novel_check(self.L.suma_localizer_tracks(self.h, None, 0, C.byref(n), C.byref(cnt), C.byref(upd)),
+                          "suma_localizer_tracks", True)
+        if not upd.value:
+            return None
+        if out is not None:
+            self._novel_check(self.L.suma_localizer_tracks_device(self.h, _dev(out), n.value, C.byref(n), C.byref(cnt),
+                                                                  C.byref(upd)), "suma_localizer_tracks_device", allow_overflow)
+            return n.value, cnt.as_dict()
+        rec = np.zeros(n.value, dtype=OBJECT_TRACK_DTYPE)
+        self._novel_check(self.L.suma_localizer_tracks(self.h, _ptr(rec) if n.value else None, n.value, C.byref(n),
+                                                       C.byref(cnt), C.byref(upd)), "suma_localizer_tracks", allow_overflow)
+        return rec[:n.value], cnt.as_dict()
+
+    def trackList(self, confirmed_only: bool = True):
+        """the live tracks of the last update as ObjectTrack objects"""
+        got = self.tracks(allow_overflow=True)
+        if got is None:
+            return []
+        return [ObjectTrack(r) for r in got[0] if not confirmed_only or r["state"] == 2]
+
+    def objectTracks(self) -> np.ndarray:
+        """per object the last update read, the id of the track its detection matched or founded, 0 for none:
+        objectTracks()[objectIds()[ty, tx]] is the track of a texel"""
+        n = C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_object_tracks(self.h, None, 0, C.byref(n)), "suma_localizer_object_tracks")
+        out = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            self.ctx.check(self.L.suma_localizer_object_tracks(self.h, _ptr(out), out.size, C.byref(n)),
+                           "suma_localizer_object_tracks")
+        return out
+
+    def trackObjects(self, objects: np.ndarray, scan_id: int) -> dict:
+        """the primitive: one tracker update over the caller's SCAN_OBJECT_DTYPE records in place of a segmentation's;
+        returns the update's counts"""
+        rec = np.ascontiguousarray(objects, dtype=SCAN_OBJECT_DTYPE).reshape(-1)
+        cnt = TrackCounts()
+        self.ctx.check(self.L.suma_localizer_track_objects(self.h, _ptr(rec) if rec.shape[0] else None, rec.shape[0], scan_id,
+                                                           C.byref(cnt)), "suma_localizer_track_objects")
+        return cnt.as_dict()
+
+    def trackState(self):
+        """(the raw table OBJECT_TRACK_DTYPE[max_tracks], last_stamp, next_id): for tests and for keeping a tracker"""
+        n, last, nxt = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self.ctx.check(self.L.suma_localizer_track_state(self.h, None, 0, C.byref(n), None, None), "suma_localizer_track_state")
+        out = np.zeros(n.value, dtype=OBJECT_TRACK_DTYPE)
+        self.ctx.check(self.L.suma_localizer_track_state(self.h, _ptr(out), out.size, C.byref(n), C.byref(last), C.byref(nxt)),
+                       "suma_localizer_track_state")
+        return out, last.value, nxt.value
+
+    def setTrackState(self, state: np.ndarray, last_stamp: int, next_id: int):
+        """puts a raw table (what trackState gave), the stamp of its last update and the next id back"""
+        st = np.ascontiguousarray(state, dtype=OBJECT_TRACK_DTYPE).reshape(-1)
+        self.ctx.check(self.L.suma_localizer_set_track_state(self.h, _ptr(st), st.shape[0], last_stamp, next_id),
+                       "suma_localizer_set_track_state")
 
     def modelFrame(self) -> Frame:
         """the window as the last scan's render saw it (the ctx's oldMapFrame)"""

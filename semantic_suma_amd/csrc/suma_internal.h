@@ -723,6 +723,37 @@ int live_update(suma_ctx* c, Live& lv, const suma_frame* f, const uint8_t* d_fla
 /* the composed cells and the mask (or NULL) into the caller's device blocks, the stats into words LIVE_STATS ..; enqueued */
 int live_compose(suma_ctx* c, Live& lv, suma_grid_cell* d_out, uint8_t* d_mask);
 
+/* k_tracks.hip (the specification is there): the objects of the scans tied together */
+enum { TRK_COUNT_WORDS = 12, TRK_N_LIVE = 12, TRK_BORN_TOTAL = 13, TRK_N_IN = 14, TRK_WORDS = 16 };
+struct TrkAcc { /* what the objects of a detection add up at their root, 80 bytes */
+  uint32_t count, rmin;                 /* members, ordered r_min */
+  uint32_t mn[3], mx[3];                /* the box as ordered integers */
+  unsigned long long ntex, ndyn, W, S[3]; /* sums of n_texels, n_dynamic and the weights; centroid sums (int64) */
+};
+struct Tracks {
+  bool on = false;
+  suma_track_params tp;
+  uint32_t max_objects = 0;      /* of the segmentation the blocks below were made for */
+  uint32_t last_stamp = 0;       /* of the last update; 0: none */
+  int32_t updated = 0;           /* out, objtrack and words 0 .. 12 hold an update's results */
+  DevBuf<uint32_t> parent;       /* one an object: its root */
+  DevBuf<TrkAcc> acc;            /* one an object, used at roots */
+  DevBuf<uint32_t> det;          /* 16 words a detection */
+  DevBuf<uint32_t> objdet, objtrack, detmatch, dettrack;
+  DevBuf<unsigned long long> detpick;
+  DevBuf<float4> rec_in;         /* suma_localizer_track_objects' records */
+  DevBuf<suma_object_track> slots, out;
+  DevBuf<uint32_t> words;        /* TRK_WORDS: the counts of the last update, its live tracks, births since the clear, n of rec_in */
+  PinnedBuf<uint32_t> stage_h;
+};
+/* the blocks for max_objects objects and tp.max_tracks slots, cleared; the caller has drained the stream */
+int tracks_alloc(suma_ctx* c, Tracks& tk, const suma_track_params& tp, uint32_t max_objects);
+/* no tracks, last stamp 0, next id 1; enqueued */
+int tracks_clear(suma_ctx* c, Tracks& tk);
+/* one update with stamp s (above tk.last_stamp: the caller has checked) of the records at d_rec, *d_n of them (a device
+ * word), enqueued */
+int tracks_update(suma_ctx* c, Tracks& tk, const float4* d_rec, const uint32_t* d_n, uint32_t s);
+
 /* k_deskew.hip (the specification is there): what kd_deskew receives by value -- the twist of one sweep, made once on the
  * host in fp64 (deskew_twist) and rounded to fp32 */
 #define SUMA_DESKEW_SMALL_THETA 1e-6

@@ -43,6 +43,8 @@ struct suma_localizer {
   Objects ob;
   /* the live obstacle layer (k_live.hip): one update behind every collection and its segmentation */
   Live lv;
+  /* tracks (k_tracks.hip): one update behind every segmentation */
+  Tracks tk;
   /* motion compensation (k_deskew.hip): the correction of process_scan's points, and the staging of a host scan that is
    * corrected (an uncorrected one goes through suma_preprocess's own staging) */
   Deskew dk;
@@ -111,14 +113,32 @@ int live_stamp_check(suma_localizer* l, uint32_t scan_id, const char* who) {
                                       std::to_string(s) + ", not above the last update's " + std::to_string(l->lv.last_stamp));
 }
 
-/* one collection over the current window, enqueued on the ctx stream; with objects on, its segmentation behind it, and
- * with the live layer on, its update behind both.  A call that collects nothing leaves no segmentation */
+/* an update's stamp must lie above the last one's: checked in front of everything an update's call launches */
+int tracks_stamp_check(suma_localizer* l, uint32_t scan_id, const char* who) {
+  const uint32_t s = scan_id + 1u;
+  if (s > l->tk.last_stamp) return SUMA_OK;
+  return fail(l->c, SUMA_ERR_INVALID, std::string(who) + ": scan_id " + std::to_string(scan_id) + " gives the tracks the stamp " +
+                                      std::to_string(s) + ", not above the last update's " + std::to_string(l->tk.last_stamp));
+}
+
+/* the tracker's update behind a segmentation that has just been enqueued */
+int track_segmentation(suma_localizer* l, uint32_t scan_id) {
+  return tracks_update(l->c, l->tk, l->ob.rec, l->ob.state.p + 5, scan_id + 1u); /* word 5: the objects stored */
+}
+
+/* one collection over the current window, enqueued on the ctx stream; with objects on, its segmentation behind it, with
+ * tracks on, their update behind that, and with the live layer on, its update behind all.  A call that collects nothing
+ * leaves no segmentation */
 int collect(suma_localizer* l, const suma_frame* f, const double T[16], uint32_t scan_id) {
   suma_ctx* c = l->c;
   l->ob.segmented = 0;
   if (!l->n_window) return SUMA_OK;
   if (l->lv.on) {
     int r = live_stamp_check(l, scan_id, "suma_localizer: the collection");
+    if (r) return r;
+  }
+  if (l->tk.on) {
+    int r = tracks_stamp_check(l, scan_id, "suma_localizer: the collection");
     if (r) return r;
   }
   if (c->gate_pending) HIP_TRY(c, flush_gate(c));
@@ -129,6 +149,7 @@ int collect(suma_localizer* l, const suma_frame* f, const double T[16], uint32_t
     r = objects_segment(c, l->ob, f, l->nv.flag, T, scan_id); /* behind the collection on the same stream, enqueued only */
     if (r) return r;
     l->ob.segmented = 1;
+    if (l->tk.on && (r = track_segmentation(l, scan_id))) return r;
   }
   if (l->lv.on) r = live_update(c, l->lv, f, l->nv.flag, l->ob.on ? l->ob.ids.p : nullptr, T, scan_id + 1u);
   return r;
@@ -200,6 +221,7 @@ extern "C" void suma_localizer_destroy(suma_localizer* l) {
   l->nv = Novel();
   l->ob = Objects();
   l->lv = Live();
+  l->tk = Tracks();
   l->dk.points.reset(), l->dk_points.reset(), l->dk_labels.reset(), l->dk_probs.reset();
   suma_frame_destroy(l->frame);
   suma_ctx_destroy(l->c);
@@ -218,6 +240,7 @@ extern "C" int suma_localizer_set_map_device(suma_localizer* l, const suma_world
   if (r) return r;
   if (l->nv.on) HIP_TRY(c, hipMemsetAsync(l->nv.state, 0, sizeof(NovelState), c->stream));
   if (l->lv.on && (r = live_clear(c, l->lv))) return r;
+  if (l->tk.on && (r = tracks_clear(c, l->tk))) return r;
   l->scan_count = 0;
   l->last_collected = 0;
   l->ob.segmented = 0;
@@ -795,6 +818,7 @@ extern "C" int suma_localizer_disable_novelty(suma_localizer* l) {
     l->nv = Novel();
     l->ob = Objects(); /* the segmentation reads the collection's flags: off with it */
     l->lv = Live();    /* and so does the live layer */
+    l->tk = Tracks();  /* the tracks follow the segmentation */
   }
   l->last_collected = 0;
   return SUMA_OK;
@@ -983,6 +1007,7 @@ extern "C" int suma_localizer_clear_novelty(suma_localizer* l) {
   HIP_TRY(c, hipMemsetAsync(l->nv.state, 0, sizeof(NovelState), c->stream));
   l->last_collected = 0;
   l->ob.segmented = 0;
+  if (l->tk.on && (r = tracks_clear(c, l->tk))) return r;
   return SUMA_OK;
 }
 
@@ -1038,6 +1063,16 @@ extern "C" int suma_localizer_enable_objects(suma_localizer* l, const suma_objec
   ob.op = q;
   ob.on = true;
   ob.segmented = 0;
+  if (l->tk.on && l->tk.max_objects != q.max_objects) { /* the tracker's blocks are sized by max_objects: made again */
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const suma_track_params tp = l->tk.tp;
+    int r = tracks_alloc(c, l->tk, tp, q.max_objects);
+    if (r) {
+      l->tk = Tracks();
+      return r;
+    }
+    l->tk.on = true;
+  }
   return SUMA_OK;
 }
 
@@ -1047,6 +1082,7 @@ extern "C" int suma_localizer_disable_objects(suma_localizer* l) {
   if (l->ob.on) {
     HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a segmentation may still write them */
     l->ob = Objects();
+    l->tk = Tracks(); /* the tracks follow the segmentation */
   }
   return SUMA_OK;
 }
@@ -1141,6 +1177,7 @@ extern "C" int suma_localizer_segment_flags(suma_localizer* l, const suma_frame*
   if (frame->width != c->p.data_width || frame->height != c->p.data_height)
     return fail(c, SUMA_ERR_INVALID, "suma_localizer_segment_flags: the frame must have the data image's size");
   if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_segment_flags: non-finite pose");
+  if (l->tk.on && (r = tracks_stamp_check(l, scan_id, "suma_localizer_segment_flags"))) return r;
   if (counts) memset(counts, 0, sizeof(*counts));
   Objects& ob = l->ob;
   ob.segmented = 0;
@@ -1148,6 +1185,7 @@ extern "C" int suma_localizer_segment_flags(suma_localizer* l, const suma_frame*
   const_cast<suma_frame*>(frame)->last_access = ++c->enq_seq;
   HIP_TRY(c, hipMemcpyAsync(ob.flags_in, host_flags, ob.n_texels, hipMemcpyHostToDevice, c->stream));
   r = objects_segment(c, ob, frame, ob.flags_in, T, scan_id);
+  if (!r && l->tk.on) r = track_segmentation(l, scan_id);
   HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a pageable source: the copy has left it */
   if (r) return r;
   ob.segmented = 1;
@@ -1247,6 +1285,7 @@ extern "C" int suma_localizer_live_update_flags(suma_localizer* l, const suma_fr
     return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_update_flags: the frame must have the data image's size");
   if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_update_flags: non-finite pose");
   if ((r = live_stamp_check(l, scan_id, who))) return r;
+  if (l->tk.on && (r = tracks_stamp_check(l, scan_id, who))) return r;
   if (counts) memset(counts, 0, sizeof(*counts));
   Objects& ob = l->ob;
   Live& lv = l->lv;
@@ -1261,6 +1300,7 @@ extern "C" int suma_localizer_live_update_flags(suma_localizer* l, const suma_fr
   const_cast<suma_frame*>(frame)->last_access = ++c->enq_seq;
   HIP_TRY(c, hipMemcpyAsync(d_flags, host_flags, P, hipMemcpyHostToDevice, c->stream));
   r = ob.on ? objects_segment(c, ob, frame, d_flags, T, scan_id) : SUMA_OK;
+  if (!r && l->tk.on) r = track_segmentation(l, scan_id);
   if (!r) r = live_update(c, lv, frame, d_flags, ob.on ? ob.ids.p : nullptr, T, scan_id + 1u);
   HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a pageable source: the copy has left it */
   if (r) return r;
@@ -1331,5 +1371,223 @@ extern "C" int suma_localizer_set_live_state(suma_localizer* l, const suma_live_
   HIP_TRY(c, hipMemcpyAsync(lv.words.p + LIVE_ANY_HIT, &any, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream)); /* pageable sources: the copies have left them */
   lv.last_stamp = last_stamp;
+  return SUMA_OK;
+}
+
+/* ---- tracks (include/suma_hip.h states the entries, k_tracks.hip the specification) ---- */
+extern "C" void suma_track_params_default(suma_track_params* tp) {
+  if (!tp) return;
+  tp->join_dist = 2.0f;
+  tp->gate_base = 1.5f;
+  tp->gate_speed = 0.5f;
+  tp->alpha = 0.5f;
+  tp->beta = 0.2f;
+  tp->confirm_hits = 3u;
+  tp->max_missed = 3u;
+  tp->max_tracks = 1024u;
+  tp->max_rounds = 16u;
+}
+
+/* NULL, or what is wrong with the values */
+static const char* track_params_why(const suma_track_params& q) {
+  if (!(q.join_dist <= 1e6f)) return "join_dist must not be a NaN and at most 1e6 (negative: joining off)";
+  if (!(q.gate_base >= 0.0f && q.gate_base <= 1e6f)) return "gate_base must lie in 0 .. 1e6";
+  if (!(q.gate_speed >= 0.0f && q.gate_speed <= 1e6f)) return "gate_speed must lie in 0 .. 1e6";
+  if (!(q.alpha >= 0.0f && q.alpha <= 1.0f)) return "alpha must lie in 0 .. 1";
+  if (!(q.beta >= 0.0f && q.beta <= 2.0f)) return "beta must lie in 0 .. 2";
+  if (q.confirm_hits < 1u || q.confirm_hits > 65535u) return "confirm_hits must be 1 .. 65535";
+  if (q.max_missed > 65535u) return "max_missed must be 0 .. 65535";
+  if (q.max_tracks < 1u || q.max_tracks > 4096u) return "max_tracks must be 1 .. 4096";
+  if (q.max_rounds < 1u || q.max_rounds > 64u) return "max_rounds must be 1 .. 64";
+  return nullptr;
+}
+
+extern "C" int suma_track_params_check(const suma_track_params* tp) {
+  if (!tp) return fail_without_ctx(SUMA_ERR_INVALID, "suma_track_params_check: NULL parameters");
+  if (const char* why = track_params_why(*tp)) return fail_without_ctx(SUMA_ERR_INVALID, std::string("suma_track_params_check: ") + why);
+  return SUMA_OK;
+}
+
+static int tracks_ready(suma_localizer* l, const char* who) {
+  if (!l->tk.on) return fail(l->c, SUMA_ERR_INVALID, std::string(who) + ": tracks are off (suma_localizer_enable_tracks)");
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_enable_tracks(suma_localizer* l, const suma_track_params* tp) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (!l->ob.on)
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_enable_tracks: objects are off (suma_localizer_enable_objects): the "
+                                     "tracks are made of their records");
+  suma_track_params q;
+  suma_track_params_default(&q);
+  if (tp) q = *tp;
+  if (const char* why = track_params_why(q)) return fail(c, SUMA_ERR_INVALID, std::string("suma_localizer_enable_tracks: ") + why);
+  HIP_TRY(c, hipStreamSynchronize(c->stream)); /* an update may still write the old blocks */
+  l->tk.on = false;
+  int r = tracks_alloc(c, l->tk, q, l->ob.op.max_objects);
+  if (r) return r;
+  l->tk.on = true;
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_disable_tracks(suma_localizer* l) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  if (l->tk.on) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* an update may still write them */
+    l->tk = Tracks();
+  }
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_clear_tracks(suma_localizer* l) {
+  if (!l) return SUMA_ERR_INVALID;
+  int r = tracks_ready(l, "suma_localizer_clear_tracks");
+  if (r) return r;
+  return tracks_clear(l->c, l->tk);
+}
+
+/* the words of the tracker into host words (blocking) */
+static int tracks_words(suma_localizer* l, uint32_t* out) {
+  suma_ctx* c = l->c;
+  HIP_TRY(c, hipMemcpyAsync(l->tk.stage_h, l->tk.words, TRK_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(out, l->tk.stage_h.p, TRK_WORDS * sizeof(uint32_t));
+  return SUMA_OK;
+}
+
+static int tracks_download(suma_localizer* l, suma_object_track* out, uint32_t capacity, uint32_t* n, suma_track_counts* counts,
+                           int32_t* updated, bool to_device, const char* who) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = tracks_ready(l, who);
+  if (r) return r;
+  if (!n || (capacity && !out)) return fail(c, SUMA_ERR_INVALID, std::string(who) + ": NULL argument");
+  *n = 0;
+  if (counts) memset(counts, 0, sizeof(*counts));
+  if (updated) *updated = l->tk.updated;
+  if (!l->tk.updated) return SUMA_OK;
+  uint32_t w[TRK_WORDS];
+  if ((r = tracks_words(l, w))) return r;
+  suma_track_counts cnt;
+  memcpy(&cnt, w, sizeof(cnt));
+  if (counts) *counts = cnt;
+  *n = w[TRK_N_LIVE];
+  const uint32_t m = *n < capacity ? *n : capacity;
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(out, l->tk.out, (size_t)m * sizeof(suma_object_track),
+                              to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  if (cnt.n_dropped)
+    return fail(c, SUMA_ERR_CAPACITY, std::string(who) + ": " + std::to_string(cnt.n_dropped) +
+                                      " detections found no free slot among max_tracks = " + std::to_string(l->tk.tp.max_tracks));
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_tracks(suma_localizer* l, suma_object_track* host, uint32_t capacity, uint32_t* n,
+                                     suma_track_counts* counts, int32_t* updated) {
+  return tracks_download(l, host, capacity, n, counts, updated, false, "suma_localizer_tracks");
+}
+
+extern "C" int suma_localizer_tracks_device(suma_localizer* l, suma_object_track* d_out, uint32_t capacity, uint32_t* n,
+                                            suma_track_counts* counts, int32_t* updated) {
+  return tracks_download(l, d_out, capacity, n, counts, updated, true, "suma_localizer_tracks_device");
+}
+
+extern "C" int suma_localizer_object_tracks(suma_localizer* l, uint32_t* host, uint32_t capacity, uint32_t* n) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = tracks_ready(l, "suma_localizer_object_tracks");
+  if (r) return r;
+  if (!n || (capacity && !host)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_object_tracks: NULL argument");
+  *n = 0;
+  if (!l->tk.updated) return SUMA_OK;
+  uint32_t w[TRK_WORDS];
+  if ((r = tracks_words(l, w))) return r;
+  *n = w[0]; /* n_objects */
+  const uint32_t m = *n < capacity ? *n : capacity;
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(host, l->tk.objtrack, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_track_objects(suma_localizer* l, const suma_scan_object* host_objects, uint32_t n, uint32_t scan_id,
+                                            suma_track_counts* counts) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  const char* who = "suma_localizer_track_objects";
+  int r = tracks_ready(l, who);
+  if (r) return r;
+  if (n && !host_objects) return fail(c, SUMA_ERR_INVALID, "suma_localizer_track_objects: NULL records with n > 0");
+  Tracks& tk = l->tk;
+  if (n > tk.max_objects)
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_track_objects: " + std::to_string(n) + " records, max_objects = " +
+                                     std::to_string(tk.max_objects));
+  if ((r = tracks_stamp_check(l, scan_id, who))) return r;
+  if (counts) memset(counts, 0, sizeof(*counts));
+  if (n) HIP_TRY(c, hipMemcpyAsync(tk.rec_in, host_objects, (size_t)n * sizeof(suma_scan_object), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(tk.words.p + TRK_N_IN, &n, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  r = tracks_update(c, tk, tk.rec_in, tk.words.p + TRK_N_IN, scan_id + 1u);
+  HIP_TRY(c, hipStreamSynchronize(c->stream)); /* pageable sources: the copies have left them */
+  if (r) return r;
+  if (!counts) return SUMA_OK;
+  uint32_t w[TRK_WORDS];
+  if ((r = tracks_words(l, w))) return r;
+  memcpy(counts, w, sizeof(*counts));
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_track_state(suma_localizer* l, suma_object_track* host, uint32_t capacity, uint32_t* n,
+                                          uint32_t* last_stamp, uint32_t* next_id) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = tracks_ready(l, "suma_localizer_track_state");
+  if (r) return r;
+  if (!n || (capacity && !host)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_track_state: NULL argument");
+  *n = l->tk.tp.max_tracks;
+  uint32_t w[TRK_WORDS];
+  if ((r = tracks_words(l, w))) return r;
+  if (last_stamp) *last_stamp = l->tk.last_stamp;
+  if (next_id) *next_id = w[TRK_BORN_TOTAL] + 1u;
+  const uint32_t m = *n < capacity ? *n : capacity;
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(host, l->tk.slots, (size_t)m * sizeof(suma_object_track), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return SUMA_OK;
+}
+
+extern "C" int suma_localizer_set_track_state(suma_localizer* l, const suma_object_track* host, uint32_t n, uint32_t last_stamp,
+                                              uint32_t next_id) {
+  if (!l) return SUMA_ERR_INVALID;
+  suma_ctx* c = l->c;
+  int r = tracks_ready(l, "suma_localizer_set_track_state");
+  if (r) return r;
+  if (!host) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_track_state: NULL argument");
+  Tracks& tk = l->tk;
+  if (n != tk.tp.max_tracks)
+    return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_track_state: " + std::to_string(n) + " slots, max_tracks = " +
+                                     std::to_string(tk.tp.max_tracks));
+  if (next_id < 1u) return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_track_state: next_id must be at least 1");
+  for (uint32_t k = 0; k < n; ++k) {
+    const suma_object_track& t = host[k];
+    if (t.state > SUMA_TRACK_CONFIRMED)
+      return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_track_state: slot " + std::to_string(k) + " has no valid state");
+    if (t.state == SUMA_TRACK_FREE) continue;
+    if (t.id < 1u || t.id >= next_id)
+      return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_track_state: slot " + std::to_string(k) + " carries an id outside 1 .. next_id - 1");
+    if (t.first_stamp > t.last_matched || t.last_matched > last_stamp)
+      return fail(c, SUMA_ERR_INVALID, "suma_localizer_set_track_state: slot " + std::to_string(k) + " carries a stamp above last_stamp");
+  }
+  if ((r = tracks_clear(c, tk))) return r;
+  const uint32_t born = next_id - 1u;
+  HIP_TRY(c, hipMemcpyAsync(tk.slots, host, (size_t)n * sizeof(suma_object_track), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(tk.words.p + TRK_BORN_TOTAL, &born, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream)); /* pageable sources: the copies have left them */
+  tk.last_stamp = last_stamp;
   return SUMA_OK;
 }

@@ -452,6 +452,77 @@ assert LIVE_CELL_DTYPE.itemsize == 16
 LIVE_MASK_LIVE, LIVE_MASK_PENDING = 1, 2
 
 
+class TrackParams(C.Structure):
+    """``struct suma_track_params``: when the objects of a scan are fragments of one thing, how near a detection must
+    be to a track's prediction, the gains of the filter, and when a track is confirmed and dropped
+    (csrc/k_tracks.hip); ``TrackParams.defaults()`` = suma_track_params_default"""
+    _fields_ = [("join_dist", f32), ("gate_base", f32), ("gate_speed", f32), ("alpha", f32), ("beta", f32),
+                ("confirm_hits", u32), ("max_missed", u32), ("max_tracks", u32), ("max_rounds", u32)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "TrackParams":
+        p = cls(join_dist=2.0, gate_base=1.5, gate_speed=0.5, alpha=0.5, beta=0.2, confirm_hits=3, max_missed=3,
+                max_tracks=1024, max_rounds=16)
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        return p
+
+
+class TrackCounts(C.Structure):
+    """``struct suma_track_counts``: what one update of the tracks made of the objects of a scan"""
+    _fields_ = [("n_objects", u32), ("n_detections", u32), ("n_joined", u32), ("n_tracks_before", u32), ("n_matched", u32),
+                ("n_missed", u32), ("n_expired", u32), ("n_born", u32), ("n_dropped", u32), ("n_confirmed", u32),
+                ("n_unresolved", u32), ("rounds", u32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+TRACK_COUNTS = tuple(k for k, _ in TrackCounts._fields_)
+# numpy view of ``struct suma_object_track``: one slot of the tracker's table
+OBJECT_TRACK_DTYPE = np.dtype([("id", "<u4"), ("slot", "<u4"), ("state", "<u4"), ("label", "<u4"), ("n_texels", "<u4"),
+                               ("n_dynamic", "<u4"), ("n_objects", "<u4"), ("hits", "<u4"), ("missed", "<u4"),
+                               ("first_stamp", "<u4"), ("last_matched", "<u4"), ("position", "<f4", (3,)),
+                               ("velocity", "<f4", (3,)), ("origin", "<f4", (3,)), ("min", "<f4", (3,)), ("max", "<f4", (3,)),
+                               ("r_min", "<f4"), ("detection", "<u4")])
+assert OBJECT_TRACK_DTYPE.itemsize == 112
+TRACK_FREE, TRACK_TENTATIVE, TRACK_CONFIRMED, TRACK_NO_DETECTION = 0, 1, 2, 0xffffffff
+
+
+class ObjectTrack:
+    """one record of OBJECT_TRACK_DTYPE with what a consumer asks of it"""
+
+    def __init__(self, record):
+        self.record = record
+        for k in OBJECT_TRACK_DTYPE.names:
+            v = record[k]
+            setattr(self, k, v.copy() if isinstance(v, np.ndarray) else (float(v) if k == "r_min" else int(v)))
+
+    @property
+    def confirmed(self) -> bool:
+        return self.state == TRACK_CONFIRMED
+
+    @property
+    def age(self) -> int:
+        """scan-id steps between the founding and the last match"""
+        return self.last_matched - self.first_stamp
+
+    @property
+    def net_velocity(self) -> np.ndarray:
+        """(position - origin) / age in metres per scan-id step: the average over the track's life, zero at age 0"""
+        d = (self.position.astype(np.float64) - self.origin.astype(np.float64))
+        return d / self.age if self.age else np.zeros(3)
+
+    def as_dict(self):
+        return dict(id=self.id, slot=self.slot, confirmed=self.confirmed, label=self.label, n_texels=self.n_texels,
+                    n_objects=self.n_objects, hits=self.hits, missed=self.missed, first_stamp=self.first_stamp,
+                    last_matched=self.last_matched, position=[float(x) for x in self.position],
+                    velocity=[float(x) for x in self.velocity], net_velocity=[float(x) for x in self.net_velocity],
+                    age=self.age, detection=self.detection)
+
+
 PLACE_MAX_DIM = 64       # SUMA_PLACE_MAX_DIM: rings and sectors
 PLACE_MAX_MATCHES = 32   # SUMA_PLACE_MAX_MATCHES
 # is_dynamic_label (csrc/dev_math.h): the moving classes K1 drops at the start of a run

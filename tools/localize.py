@@ -12,7 +12,9 @@ objects out of the synthetic world the localised scans see).  --novel collects t
 (csrc/k_novel.hip), prints every scan's counts and, with --update-out, writes the updated map: the records the rule keeps
 (all of them without --evidence) followed by the fused new ones (--map-without takes objects out of the world the mapping
 run sees).  --objects (with --novel) segments each scan's unexplained texels into objects (csrc/k_objects.hip) and prints,
-per scan, their number and each one's class, size, centroid and nearest range; --objects-out writes them as JSON.  --deskew motion compensates the localised scans with the localiser's last increment (csrc/k_deskew.hip), for
+per scan, their number and each one's class, size, centroid and nearest range; --objects-out writes them as JSON.
+--tracks (with --objects) follows the objects across the scans (csrc/k_tracks.hip) and prints, per scan, the confirmed
+tracks: id, class, position, velocity, net velocity since birth, age and fragments; --tracks-out writes all tracks as JSON.  --deskew motion compensates the localised scans with the localiser's last increment (csrc/k_deskew.hip), for
 sensors that deliver raw sweeps.  --live-grid GRID.npz (with --novel) switches the live obstacle layer on (csrc/k_live.hip) over
 the traversability grid in GRID.npz (mapio.write_grid; a file that does not exist is made from the map as mapped, at
 --grid-cell metres, and written), prints every scan's counts and live cells and, with --goal X Y, the path cost from the
@@ -27,6 +29,7 @@ run's own scans, or with --map the file tools/export_map.py --places wrote (--pl
     python tools/localize.py --map-without 2 41 --novel --update-out new.ply    # cube 2 and a building have arrived
     python tools/localize.py --map-without 2 41 --novel --objects [--objects-out objects.json]   # ... as objects, per scan
     python tools/localize.py --map-without 2 41 --novel --objects --live-grid grid.npz --goal 60 -8   # ... in the planner's grid
+    python tools/localize.py --map-without 2 41 --novel --objects --tracks [--tracks-out tracks.json]   # ... followed across scans
     python tools/localize.py --kitti raw/sequence --deskew   # raw (uncompensated) sweeps: corrected in front of K1
 """
 import argparse
@@ -137,12 +140,13 @@ def collect_timing(loc, scan, pose, n_window, scan_id=0):
     return out
 
 
-def objects_timing(loc, scan, pose, scan_id=0):
+def objects_timing(loc, scan, pose, scan_id=0, tracked=False):
     """the event times of one segmentation's two kernel groups (suma_profile: kob_init + kob_merge + kob_flatten, and
     kob_vote + kob_emit + kob_ids) over the flags of one collection, each against an event-timed device-to-device copy of
     the bytes it touches (about 150 and 40 a texel: the vertex and semantic texels, the labels, the vote table, the ids; 96
     more per member for its accumulator are left out), and the host route timed in the same run: the flag, vertex and
-    semantic images downloaded, then tests/object_shim.c (gcc -O2, one thread) over them"""
+    semantic images downloaded, then tests/object_shim.c (gcc -O2, one thread) over them.  ``tracked``: the tracks are on,
+    every segmentation is followed by their update and wants a scan id of its own"""
     import subprocess
     import tempfile
     from semantic_suma_amd.types import ObjectCounts, ObjectParams, SCAN_OBJECT_DTYPE
@@ -158,7 +162,7 @@ def objects_timing(loc, scan, pose, scan_id=0):
     label, reduce_ = [], []
     for k in range(13):
         ctx.profile_reset()
-        counts = loc.segmentFlags(frame, pose, flags, 0)
+        counts = loc.segmentFlags(frame, pose, flags, scan_id + 1 + k if tracked else 0)
         ms = {r["name"]: r["total_ms"] for r in ctx.profile_get()}
         if k >= 3:
             label.append(ms["objects_label"])
@@ -281,6 +285,54 @@ def live_timing(loc, scan, pose, live):
     return out
 
 
+def tracks_timing(loc, base):
+    """the event times of one tracker update's two kernel groups (suma_profile: ktr_init + ktr_join + ktr_reduce, and
+    ktr_track) over the records of the last segmentation, each update with a stamp of its own on the state the run left,
+    and the host route timed in the same run: the object records downloaded, then tests/track_shim.c (gcc -O2, one
+    thread) over them from the same state"""
+    import tempfile
+    ctx = loc.ctx
+    rec = loc.objects(allow_overflow=True)[0]
+    ctx.profile(1)
+    join, update = [], []
+    for k in range(13):
+        ctx.profile_reset()
+        counts = loc.trackObjects(rec, base + k)
+        ms = {r["name"]: r["total_ms"] for r in ctx.profile_get()}
+        if k >= 3:
+            join.append(ms["tracks_join"])
+            update.append(ms["tracks_update"])
+    ctx.profile(0)
+    out = dict(counts=counts, objects=int(len(rec)),
+               join=dict(launches=3, kernel_us_median10=round(1e3 * float(np.median(join)), 2), samples=dict(kernel_ms=join)),
+               update=dict(launches=1, kernel_us_median10=round(1e3 * float(np.median(update)), 2), samples=dict(kernel_ms=update)))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tests"))
+    import track_common as tc
+    with tempfile.TemporaryDirectory() as tmp:
+        shim = tc.build_shim(tmp)
+        download, host, same = [], [], True
+        for k in range(13):
+            want = tc.ShimTracker(shim, loc._track_params)
+            want.set_state(*loc.trackState())
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            got = loc.objects(allow_overflow=True)[0]
+            t1 = time.perf_counter()
+            w = want.update(got, base + 13 + k)
+            t2 = time.perf_counter()
+            loc.trackObjects(rec, base + 13 + k)
+            same = same and loc.tracks(allow_overflow=True)[0].tobytes() == w[0].tobytes() and \
+                loc.trackState()[0].tobytes() == want.slots.tobytes()
+            if k >= 3:
+                download.append(1e3 * (t1 - t0))
+                host.append(1e3 * (t2 - t1))
+    out["host_route"] = dict(download_us_median10=round(1e3 * float(np.median(download)), 2),
+                             shim_us_median10=round(1e3 * float(np.median(host)), 2), equals_device=bool(same),
+                             samples=dict(download_ms=download, shim_ms=host))
+    return out
+
+
 def added_footprints(gp, boxes):
     """bool per cell: the centre lies inside the x / y extent of one of synth._boxes(0)'s ``boxes`` (the grid's frame is
     that of scan 0)"""
@@ -342,6 +394,9 @@ def main():
     ap.add_argument("--objects-out", default=None, metavar="FILE.json", help="with --objects: write every scan's objects")
     ap.add_argument("--map-without", type=int, nargs="*", default=[], metavar="BOX",
                     help="synthetic scans: boxes of synth._boxes the mapping run does not see")
+    ap.add_argument("--tracks", action="store_true",
+                    help="with --objects: track the objects across the scans and print every scan's confirmed tracks")
+    ap.add_argument("--tracks-out", default=None, metavar="FILE.json", help="with --tracks: write every scan's tracks")
     ap.add_argument("--live-grid", default=None, metavar="GRID.npz",
                     help="with --novel: the live obstacle layer over this traversability grid (made from the map and written "
                          "when the file does not exist)")
@@ -363,6 +418,10 @@ def main():
         ap.error("--objects needs --novel")
     if args.objects_out and not args.objects:
         ap.error("--objects-out needs --objects")
+    if args.tracks and not args.objects:
+        ap.error("--tracks needs --objects")
+    if args.tracks_out and not args.tracks:
+        ap.error("--tracks-out needs --tracks")
     over = {k: v for k, v in (("submap_extent", args.extent), ("submap_dimension", args.dimension)) if v is not None}
     p = params_with_size(args.width, args.height, **over)
     n_map = args.map_scans if args.map_scans is not None else (300 if args.timing else 80)
@@ -421,6 +480,8 @@ def main():
         loc.enableNovelty()
     if args.objects:
         loc.enableObjects()
+    if args.tracks:
+        loc.enableTracks()
     if args.deskew:
         loc.enableDeskew()
         res["deskew"] = True
@@ -450,7 +511,7 @@ def main():
         loc.setPose(start)
     scans = [read_scan(args, k, tuple(args.without)) for k in ks]
     host_scans = scans
-    observations, collections, objects = [], [], []
+    observations, collections, objects, tracks = [], [], [], []
     if args.timing:
         scans = [resident(loc.ctx, sc) for sc in scans]
         loc.ctx.synchronize()
@@ -479,6 +540,8 @@ def main():
                 collections.append(loc.lastCollection(allow_overflow=True))
             if args.objects and not args.timing:
                 objects.append(loc.objects(allow_overflow=True))
+            if args.tracks and not args.timing:
+                tracks.append(loc.tracks(allow_overflow=True))
             if live and not args.timing:
                 gp, T = live["gp"], out[-1]["pose"]
                 entry = dict(scan=k, counts=loc.liveCounts())
@@ -554,6 +617,27 @@ def main():
             with open(args.objects_out, "w") as f:
                 json.dump(listing, f)
             res["objects_file"] = args.objects_out
+    if args.tracks:
+        from semantic_suma_amd.types import ObjectTrack
+        listing = []
+        for k, got in zip(ks[len(ks) - len(tracks):] if args.relocalize else ks, tracks):
+            rec, cnt = got if got is not None else ((), dict(n_detections=0, n_matched=0, n_born=0, n_expired=0))
+            conf = [ObjectTrack(r) for r in rec if r["state"] == 2]
+            print(f"scan {k:5d}  tracks {len(rec)}  confirmed {len(conf)}  detections {cnt['n_detections']}  matched "
+                  f"{cnt['n_matched']}  born {cnt['n_born']}  expired {cnt['n_expired']}")
+            for t in conf:
+                v, nv = t.velocity, t.net_velocity
+                print(f"            id {t.id:4d}  class {t.label:3d}  position {t.position[0]:9.3f} {t.position[1]:9.3f} "
+                      f"{t.position[2]:7.3f}  velocity {v[0]:6.2f} {v[1]:6.2f} {v[2]:6.2f}  net {nv[0]:6.2f} {nv[1]:6.2f} {nv[2]:6.2f} "
+                      f"({float(np.linalg.norm(nv)):.3f} a scan)  age {t.age:3d}  missed {t.missed}  fragments {t.n_objects}")
+            listing.append(dict(scan=k, counts=cnt, tracks=[ObjectTrack(r).as_dict() for r in rec]))
+        last = loc.tracks(allow_overflow=True)
+        res["tracks"] = dict(confirmed_per_scan=[sum(1 for t in e["tracks"] if t["confirmed"]) for e in listing] if listing else None,
+                             last_scan=None if last is None else last[1], ids_given=loc.trackState()[2] - 1)
+        if args.tracks_out:
+            with open(args.tracks_out, "w") as f:
+                json.dump(listing, f)
+            res["tracks_file"] = args.tracks_out
     if live:
         for e in live["per_scan"]:
             c, st = e["counts"] or {}, e["stats"]
@@ -587,11 +671,13 @@ def main():
         if args.evidence and "lost_at_scan" not in res:
             res["observe"] = observe_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], loc.window()[1])
         if args.novel and "lost_at_scan" not in res:
-            res["collect"] = collect_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], loc.window()[1], (1 << 18) if live else 0)
+            res["collect"] = collect_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], loc.window()[1], (1 << 18) if live or args.tracks else 0)
         if args.objects and "lost_at_scan" not in res:
-            res["segment"] = objects_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], (1 << 19) if live else 0)
+            res["segment"] = objects_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], (1 << 19) if live or args.tracks else 0, tracked=args.tracks)
         if live and "lost_at_scan" not in res:
             res["live_timing"] = live_timing(loc, host_scans[len(out) - 1], out[-1]["pose"], live)
+        if args.tracks and "lost_at_scan" not in res:
+            res["tracks_timing"] = tracks_timing(loc, 1 << 21)
     loc.close()
     print(json.dumps(res))
 
