@@ -248,26 +248,67 @@ __device__ inline void pg_mtm6(const double* A, const double* B, double* C) { /*
     }
 }
 
-/* inverse of a symmetric positive-definite 6x6 by Gauss-Jordan without pivoting (the pivots are positive) */
-__device__ inline void pg_inv6(const double* Ain, double* Out) {
-  double a[36], b[36];
+/* Cholesky factor A = L L^T of a symmetric positive-definite 6x6 (only A's lower triangle is read).  F holds L's strict
+ * lower triangle and 1 / L_ii on the diagonal (the solves multiply by it); its upper triangle is zero.  F may be A.
+ * An explicit inverse in its place costs the cyclic reduction a factor cond(A) in accuracy: with blocks of condition
+ * 1e9 the solve was wrong by 5e-7 where this one is at the system's own conditioning (test_gpu_posegraph_solve.py) */
+__device__ inline void pg_chol6(const double* A, double* F) {
+  double l[36];
 #pragma unroll
-  for (int i = 0; i < 36; ++i) a[i] = Ain[i], b[i] = (i % 7 == 0) ? 1.0 : 0.0;
+  for (int j = 0; j < 6; ++j) {
+    double d = A[j * 6 + j];
 #pragma unroll
-  for (int p = 0; p < 6; ++p) {
-    const double r = 1.0 / a[p * 6 + p];
+    for (int k = 0; k < j; ++k) d -= l[j * 6 + k] * l[j * 6 + k];
+    const double r = 1.0 / sqrt(d);
+    l[j * 6 + j] = r;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) a[p * 6 + j] *= r, b[p * 6 + j] *= r;
+    for (int i = j + 1; i < 6; ++i) {
+      double s = A[i * 6 + j];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      if (i == p) continue;
-      const double f = a[i * 6 + p];
-#pragma unroll
-      for (int j = 0; j < 6; ++j) a[i * 6 + j] -= f * a[p * 6 + j], b[i * 6 + j] -= f * b[p * 6 + j];
+      for (int k = 0; k < j; ++k) s -= l[i * 6 + k] * l[j * 6 + k];
+      l[i * 6 + j] = s * r;
+      l[j * 6 + i] = 0.0;
     }
   }
 #pragma unroll
-  for (int i = 0; i < 36; ++i) Out[i] = b[i];
+  for (int i = 0; i < 36; ++i) F[i] = l[i];
+}
+
+/* x = A^-1 b with A's factor F of pg_chol6: L y = b, L^T x = y.  x may be b */
+__device__ inline void pg_chol_solve6(const double* F, const double* b, double* x) {
+  double y[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double s = b[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) s -= F[i * 6 + k] * y[k];
+    y[i] = s * F[i * 6 + i];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double s = y[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) s -= F[k * 6 + i] * y[k];
+    y[i] = s * F[i * 6 + i];
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) x[i] = y[i];
+}
+
+/* C = A^-1 B (6x6, row-major) with A's factor F, column by column */
+__device__ inline void pg_chol_solve6m(const double* F, const double* B, double* C) {
+  double f[36];
+#pragma unroll
+  for (int i = 0; i < 36; ++i) f[i] = F[i];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    double v[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) v[i] = B[i * 6 + c];
+    pg_chol_solve6(f, v, v);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) C[i * 6 + c] = v[i];
+  }
 }
 
 /* ---- kernels -------------------------------------------------------------------------------------------------- */
@@ -466,7 +507,7 @@ struct PgSystem {
   const double *D, *U, *O, *g;
   const int32_t *oa, *ob;         /* off-band pair k = (oa[k], ob[k]), oa < ob */
   const uint32_t *optr, *oadj;    /* per node: off-band pairs it is in, k << 1 | (node is ob) */
-  double *Binv, *Cr, *Lb;         /* block cyclic reduction: per node, at its elimination level */
+  double *Bf, *Cr, *Lb;           /* block cyclic reduction: per node, at its elimination level */
   double *x, *r, *z, *p, *q;      /* 6n each */
 };
 
@@ -504,21 +545,19 @@ __device__ void pg_spmv(const PgSystem& S, double lambda, const double* v, doubl
 
 /* Block cyclic reduction of the block-tridiagonal part T (diagonal D + lambda I, band U).  At stride s the nodes
  * e = s-1 + 2sk are eliminated (lowest set bit of e+1 is s); their neighbours e -+ s survive to stride 2s.  Per node:
- * Binv = inverse of its reduced diagonal block, Cr = its coupling to the right neighbour at its level (Rb), Lb = its
- * coupling to the left neighbour at its level. */
+ * Bf = Cholesky factor of its reduced diagonal block (pg_chol6; the reduced block itself until the node is eliminated),
+ * Cr = its coupling to the right neighbour at its level (Rb), Lb = its coupling to the left neighbour at its level. */
 __device__ void pg_bcr_factor(const PgSystem& S, double lambda) {
   const uint32_t n = S.n;
   for (uint32_t i = threadIdx.x; i < n; i += PG_SOLVE_THREADS)
     for (int k = 0; k < 36; ++k) {
-      S.Binv[(size_t)i * 36 + k] = S.D[(size_t)i * 36 + k] + (k % 7 == 0 ? lambda : 0.0);
+      S.Bf[(size_t)i * 36 + k] = S.D[(size_t)i * 36 + k] + (k % 7 == 0 ? lambda : 0.0);
       S.Cr[(size_t)i * 36 + k] = i + 1 < n ? S.U[(size_t)i * 36 + k] : 0.0;
     }
   __syncthreads();
   for (uint32_t s = 1; s <= n; s <<= 1) {
     for (size_t e = s - 1 + (size_t)2 * s * threadIdx.x; e < n; e += (size_t)2 * s * PG_SOLVE_THREADS) {
-      double B[36];
-      pg_inv6(S.Binv + (size_t)e * 36, B);
-      for (int k = 0; k < 36; ++k) S.Binv[(size_t)e * 36 + k] = B[k];
+      pg_chol6(S.Bf + (size_t)e * 36, S.Bf + (size_t)e * 36);
       for (int r = 0; r < 6; ++r)
         for (int c = 0; c < 6; ++c)
           S.Lb[(size_t)e * 36 + r * 6 + c] = e >= s ? S.Cr[(size_t)(e - s) * 36 + c * 6 + r] : 0.0;
@@ -526,19 +565,19 @@ __device__ void pg_bcr_factor(const PgSystem& S, double lambda) {
     __syncthreads();
     for (size_t k = (size_t)2 * s - 1 + (size_t)2 * s * threadIdx.x; k < n; k += (size_t)2 * s * PG_SOLVE_THREADS) {
       double T1[36], T2[36];
-      double* Bk = S.Binv + (size_t)k * 36;
+      double* Bk = S.Bf + (size_t)k * 36;
       const double* Rl = S.Cr + (size_t)(k - s) * 36; /* block (k-s, k) */
-      pg_mm6(S.Binv + (size_t)(k - s) * 36, Rl, T1);
+      pg_chol_solve6m(S.Bf + (size_t)(k - s) * 36, Rl, T1);
       pg_mtm6(Rl, T1, T2);
       for (int q = 0; q < 36; ++q) Bk[q] -= T2[q];
       if (k + s < n) {
         const double* Lr = S.Lb + (size_t)(k + s) * 36; /* block (k+s, k) */
-        const double* Bi = S.Binv + (size_t)(k + s) * 36;
-        pg_mm6(Bi, Lr, T1);
+        const double* Bi = S.Bf + (size_t)(k + s) * 36;
+        pg_chol_solve6m(Bi, Lr, T1);
         pg_mtm6(Lr, T1, T2);
         for (int q = 0; q < 36; ++q) Bk[q] -= T2[q];
         if (k + 2 * s < n) {
-          pg_mm6(Bi, S.Cr + (size_t)(k + s) * 36, T1);
+          pg_chol_solve6m(Bi, S.Cr + (size_t)(k + s) * 36, T1);
           pg_mtm6(Lr, T1, T2);
           for (int q = 0; q < 36; ++q) S.Cr[(size_t)k * 36 + q] = -T2[q];
         } else {
@@ -562,11 +601,11 @@ __device__ void pg_bcr_apply(const PgSystem& S, const double* r, double* z) {
     top = s;
     for (size_t k = (size_t)2 * s - 1 + (size_t)2 * s * threadIdx.x; k < n; k += (size_t)2 * s * PG_SOLVE_THREADS) {
       double y[6], t[6];
-      pg_mv6(S.Binv + (size_t)(k - s) * 36, z + (size_t)(k - s) * 6, y);
+      pg_chol_solve6(S.Bf + (size_t)(k - s) * 36, z + (size_t)(k - s) * 6, y);
       pg_mtv6(S.Cr + (size_t)(k - s) * 36, y, t);
       for (int c = 0; c < 6; ++c) z[(size_t)k * 6 + c] -= t[c];
       if (k + s < n) {
-        pg_mv6(S.Binv + (size_t)(k + s) * 36, z + (size_t)(k + s) * 6, y);
+        pg_chol_solve6(S.Bf + (size_t)(k + s) * 36, z + (size_t)(k + s) * 6, y);
         pg_mtv6(S.Lb + (size_t)(k + s) * 36, y, t);
         for (int c = 0; c < 6; ++c) z[(size_t)k * 6 + c] -= t[c];
       }
@@ -585,7 +624,7 @@ __device__ void pg_bcr_apply(const PgSystem& S, const double* r, double* z) {
         pg_mv6(S.Cr + (size_t)e * 36, z + (size_t)(e + s) * 6, t);
         for (int c = 0; c < 6; ++c) y[c] -= t[c];
       }
-      pg_mv6(S.Binv + (size_t)e * 36, y, t);
+      pg_chol_solve6(S.Bf + (size_t)e * 36, y, t);
       for (int c = 0; c < 6; ++c) z[(size_t)e * 6 + c] = t[c];
     }
     __syncthreads();
@@ -661,7 +700,7 @@ struct suma_posegraph {
   bool structure_dirty = true;
   /* device: factors (prior + edges), structure, system, solver */
   uint32_t n_dev = 0, m_dev = 0, np_dev = 0, no_dev = 0;
-  DevBuf<double> X, Xn, Z, Om, lin, energy, err6, D, U, O, g, Binv, Cr, Lb, work;
+  DevBuf<double> X, Xn, Z, Om, lin, energy, err6, D, U, O, g, Bf, Cr, Lb, work;
   DevBuf<int32_t> fr, to, pa, pdst, oa, ob;
   DevBuf<uint32_t> nptr, nfac, pptr, pfac, optr, oadj;
   DevBuf<PgStatus> dst;
@@ -805,7 +844,7 @@ int pg_prepare(suma_posegraph* G) {
     PG_HIP(G, pg_grow(G->optr, n + 1));
     PG_HIP(G, pg_grow(G->oadj, oadj.size()));
     PG_HIP(G, pg_grow(G->O, 36 * (size_t)no));
-    for (DevBuf<double>* b : {&G->D, &G->U, &G->Binv, &G->Cr, &G->Lb}) PG_HIP(G, pg_grow(*b, 36 * (size_t)n));
+    for (DevBuf<double>* b : {&G->D, &G->U, &G->Bf, &G->Cr, &G->Lb}) PG_HIP(G, pg_grow(*b, 36 * (size_t)n));
     PG_HIP(G, pg_grow(G->g, 6 * (size_t)n));
     PG_HIP(G, pg_grow(G->work, 30 * (size_t)n)); /* x r z p q */
     PG_HIP(G, pg_grow(G->X, 12 * (size_t)n));
@@ -868,7 +907,7 @@ PgSystem pg_system(suma_posegraph* G) {
   S.n = G->n_dev;
   S.D = G->D, S.U = G->U, S.O = G->O, S.g = G->g;
   S.oa = G->oa, S.ob = G->ob, S.optr = G->optr, S.oadj = G->oadj;
-  S.Binv = G->Binv, S.Cr = G->Cr, S.Lb = G->Lb;
+  S.Bf = G->Bf, S.Cr = G->Cr, S.Lb = G->Lb;
   S.x = G->work, S.r = G->work + n6, S.z = G->work + 2 * n6, S.p = G->work + 3 * n6, S.q = G->work + 4 * n6;
   return S;
 }

@@ -352,3 +352,212 @@ def chain_graph(n, n_loops, rng, noise=(0.01, 0.05), trajectory=None, loop_min_g
     for i in range(n - 1):
         init.append(compose(init[-1], edges[i][2]))
     return np.array(gt), HostGraph(init, edges)
+
+
+# ---- one damped solve: the yardstick of k_pg_solve ----------------------------------------------------------------
+#
+# optimize(1) with lambda_initial = lam and both error tolerances 0 runs the first damped solve at exactly lam; when the
+# step is accepted (linear_solves == 1) the poses are X0 Exp(delta), so delta = Log(X0^-1 X1) per node is the solver's
+# output.  lam = SOLVE_LAMBDA = 1 throughout: at gtsam's 1e-5 two orderings of the direct solve differ by up to 2e-10
+# relative on these graphs, at 1 by 1e-13 or less.
+
+SOLVE_LAMBDA = 1.0
+
+# every n in 1..9, then 2^k - 1, 2^k, 2^k + 1 for k = 4..10 (the edges of the cyclic reduction's level count and of its
+# `e >= s`, `k + s < n`, `k + 2s < n` branches), then 1537: three trips of the stride loop at s = 1 and two at s = 2
+SOLVE_CHAIN_SIZES = tuple(range(1, 10)) + tuple(2 ** k + d for k in range(4, 11) for d in (-1, 0, 1)) + (1537,)
+SOLVE_LOOP_CASES = ((64, 2), (257, 3), (513, 5), (1025, 20))  # (n, distinct off-band pairs)
+SOLVE_ANISOTROPIC_SIZES = (33, 513)
+# Seeds of the builders below as the tests use them.  They were picked so that, on the host alone, pcg_band meets
+# the iteration caps of the GPU tests and Levenberg-Marquardt accepts the step (tests/test_posegraph_host.py).
+SOLVE_SEED = 7
+
+
+def _perturbed(rng, hg):
+    """the odometry-integrated start satisfies every chain edge: perturb every node but the first, so that a chain has
+    work to do.  A single node is perturbed itself (the prior then pulls it back)"""
+    if len(hg.nodes) == 1:
+        hg.nodes = [perturb(rng, hg.nodes[0], 0.01, 0.1)]
+    else:
+        hg.nodes = [hg.nodes[0]] + [perturb(rng, T, 0.01, 0.1) for T in hg.nodes[1:]]
+    return hg
+
+
+def solve_chain(n, seed=SOLVE_SEED):
+    rng = np.random.default_rng([seed, n])
+    return _perturbed(rng, chain_graph(n, 0, rng)[1])
+
+
+def solve_loop_pairs(n, L, rng):
+    """L distinct off-band pairs (a, b) with a < b - 1: (0, n-1) first, then up to two more at node n-1, which so takes
+    part in three of them when L >= 3 (two distinct pairs cannot give a node three), then random ones"""
+    pairs = [(0, n - 1)]
+    while len(pairs) < min(L, 3):
+        a = int(rng.integers(1, n - 2))
+        if (a, n - 1) not in pairs:
+            pairs.append((a, n - 1))
+    while len(pairs) < L:
+        a, b = sorted(int(v) for v in rng.integers(0, n, size=2))
+        if b - a >= 2 and (a, b) not in pairs:
+            pairs.append((a, b))
+    return pairs
+
+
+def solve_loops(n, L, seed=SOLVE_SEED):
+    """a perturbed chain plus loop edges on L distinct off-band pairs; returns (graph, pairs).  Pair (0, n-1) is
+    there, node n-1 is in min(L, 3) pairs, the edges alternate between newer -> older and older -> newer, and the
+    second pair is entered twice, once in each direction (L + 1 loop edges)"""
+    rng = np.random.default_rng([seed, n, L])
+    gt, hg = chain_graph(n, 0, rng)
+    pairs = solve_loop_pairs(n, L, rng)
+    Om = np.diag([1e3, 1e3, 1e3, 1e2, 1e2, 1e2])
+    directed = [(b, a) if k % 2 == 0 else (a, b) for k, (a, b) in enumerate(pairs)]
+    directed.insert(2, directed[1][::-1])
+    for a, b in directed:
+        hg.edges.append((a, b, perturb(rng, compose(inv(gt[a]), gt[b]), 0.01, 0.05), Om))
+    return _perturbed(rng, hg), pairs
+
+
+def solve_anisotropic(n, seed=SOLVE_SEED):
+    """a perturbed chain whose edge information is Q diag(1e6, 1e6, 1e-3, 1e3, 1e-3, 1e3) Q^T with a random orthogonal
+    Q per edge: every block has condition number 1e9 and none is diagonal"""
+    rng = np.random.default_rng([seed, n, 9])
+    hg = chain_graph(n, 0, rng)[1]
+    d = np.array([1e6, 1e6, 1e-3, 1e3, 1e-3, 1e3])
+    edges = []
+    for a, b, Z, _ in hg.edges:
+        Q = np.linalg.qr(rng.normal(size=(6, 6)))[0]
+        edges.append((a, b, Z, (Q * d) @ Q.T))
+    return _perturbed(rng, HostGraph(hg.nodes, edges))
+
+
+def damped_system(graph, X, lam):
+    """(A, g) of the damped normal equations A delta = -g, A = H + lam I (csr)"""
+    g, H, _, _ = linearize(graph, X)
+    return (H + lam * sp.identity(H.shape[0], format="csr")).tocsr(), g
+
+
+def single_solve(graph, X, lam, permc_spec=None):
+    """delta of (H + lam I) delta = -g by a sparse direct solve (permc_spec: SuperLU's column ordering)"""
+    A, g = damped_system(graph, X, lam)
+    return spla.spsolve(A.tocsc(), -g, permc_spec=permc_spec)
+
+
+def band_part(A, drop_band=None):
+    """the block-tridiagonal part of A (6x6 blocks); drop_band = i also leaves out the band block (i, i+1) and its
+    transpose, which keeps the matrix positive-definite (two principal sub-matrices of A's band part remain)"""
+    C = A.tocoo()
+    bi, bj = C.row // 6, C.col // 6
+    keep = np.abs(bi - bj) <= 1
+    if drop_band is not None:
+        keep &= ~((np.minimum(bi, bj) == drop_band) & (bi != bj))
+    return sp.csc_matrix((C.data[keep], (C.row[keep], C.col[keep])), shape=A.shape)
+
+
+def pcg_band(graph, X, lam, tol, max_it, drop_band=None):
+    """the preconditioned CG of DESIGN.md "Pose graph" in fp64 with k_pg_solve's order of operations and its stopping
+    rule !(rzn > tol^2 rz0); the preconditioner is an exact sparse factorisation of the block-tridiagonal part.
+    Returns (delta, iterations).  drop_band: see band_part (a deliberately inexact preconditioner)"""
+    A, g = damped_system(graph, X, lam)
+    M = spla.splu(band_part(A, drop_band))
+    x = np.zeros_like(g)
+    r = -g
+    z = M.solve(r)
+    p = z.copy()
+    rz = rz0 = float(r @ z)
+    it = 0
+    if rz0 > 0:
+        while it < max_it:
+            q = A @ p
+            pq = float(p @ q)
+            if not pq > 0:
+                break
+            alpha = rz / pq
+            x += alpha * p
+            r -= alpha * q
+            it += 1
+            z = M.solve(r)
+            rzn = float(r @ z)
+            if not rzn > tol * tol * rz0:
+                break
+            p = z + (rzn / rz) * p
+            rz = rzn
+    return x, it
+
+
+def step_of(X0, X1):
+    """delta with X1 = X0 Exp(delta), per node (n x 6)"""
+    return se3_log(compose(inv(np.asarray(X0)), np.asarray(X1)))
+
+
+def model_fidelity(graph, X, delta):
+    """(error(X) - error(X Exp(delta))) / linearised decrease: Levenberg-Marquardt accepts above min_model_fidelity"""
+    g, H, _, _ = linearize(graph, X)
+    lin = -(g @ delta + 0.5 * delta @ (H @ delta))
+    return (error(graph, X) - error(graph, retract(X, delta))) / lin
+
+
+_SOLVE_CASES = {}
+
+
+def solve_case(kind, n, L=0):
+    """one case of the single-solve tests, computed once and shared (read only): the graph, its start X, the direct
+    solve's delta (n x 6), and pcg_band's iteration count at the tolerance the GPU test of that kind runs with"""
+    key = (kind, n, L)
+    if key not in _SOLVE_CASES:
+        hg = {"chain": lambda: solve_chain(n), "loops": lambda: solve_loops(n, L)[0],
+              "anisotropic": lambda: solve_anisotropic(n)}[kind]()
+        X = np.array(hg.nodes)
+        tol = 1e-13 if kind == "loops" else 1e-6
+        _SOLVE_CASES[key] = dict(graph=hg, X=X, delta=single_solve(hg, X, SOLVE_LAMBDA).reshape(-1, 6), cg_tolerance=tol,
+                                 pcg_iterations=pcg_band(hg, X, SOLVE_LAMBDA, tol, 1000)[1])
+    return _SOLVE_CASES[key]
+
+
+def step_errors(delta, reference):
+    """(relative 2-norm over all entries, largest per-node error norm / largest per-node reference norm)"""
+    d, r = np.asarray(delta).reshape(-1, 6), np.asarray(reference).reshape(-1, 6)
+    return (np.linalg.norm(d - r) / np.linalg.norm(r),
+            np.linalg.norm(d - r, axis=1).max() / np.linalg.norm(r, axis=1).max())
+
+
+def reference_uncertainty(graph, X, lam):
+    """how well the host knows delta: the larger of the relative difference between two column orderings of the direct
+    solve and the relative error of the round trip Log(X^-1 (X Exp(delta)))"""
+    d = single_solve(graph, X, lam)
+    dn = single_solve(graph, X, lam, permc_spec="NATURAL")
+    nd = np.linalg.norm(d)
+    ordering = np.linalg.norm(d - dn) / nd
+    trip = np.linalg.norm(step_of(X, retract(X, d)).ravel() - d) / nd
+    return max(ordering, trip), ordering, trip
+
+
+# The largest reference_uncertainty over every case of the single-solve tests, rounded up to one digit.  The GPU tests
+# allow the device 1e3 times this (cyclic reduction is not backward stable the way sparse LU is).  Measured at
+# SOLVE_LAMBDA with SOLVE_SEED (tests/test_posegraph_host.py asserts that no case exceeds the constant):
+#
+#   case                 ordering   round trip         case                 ordering   round trip
+#   chain 1              0          3.7e-17            chain 63             5.2e-15    3.2e-14
+#   chain 2              0          9.3e-16            chain 64             4.8e-15    3.2e-14
+#   chain 3              0          3.0e-16            chain 65             2.1e-15    3.0e-14
+#   chain 4              7.9e-16    3.3e-15            chain 127            2.9e-15    7.0e-14
+#   chain 5              1.3e-15    2.2e-15            chain 128            1.4e-15    6.4e-14
+#   chain 6              2.0e-15    6.1e-15            chain 129            4.3e-15    6.2e-14
+#   chain 7              5.8e-16    4.3e-15            chain 255            1.2e-15    1.2e-13
+#   chain 8              4.0e-15    3.5e-15            chain 256            1.9e-15    1.0e-13
+#   chain 9              1.9e-15    5.2e-15            chain 257            1.3e-15    1.1e-13
+#   chain 15             1.3e-14    7.1e-15            chain 511            1.1e-15    2.7e-13
+#   chain 16             3.2e-15    7.3e-15            chain 512            1.7e-15    3.0e-13
+#   chain 17             6.7e-15    7.2e-15            chain 513            9.3e-16    3.1e-13
+#   chain 31             5.9e-15    1.1e-14            chain 1023           9.8e-16    7.6e-13
+#   chain 32             6.7e-15    1.2e-14            chain 1024           1.2e-15    7.6e-13
+#   chain 33             2.4e-15    1.6e-14            chain 1025           1.4e-15    7.7e-13
+#   loops (64, 2)        3.7e-13    4.7e-14            chain 1537           5.7e-16    2.0e-12
+#   loops (257, 3)       3.7e-14    1.0e-13            anisotropic 33       7.5e-11    1.7e-14
+#   loops (513, 5)       1.1e-13    6.4e-13            anisotropic 513      9.1e-11    2.9e-13
+#   loops (1025, 20)     4.9e-13    1.3e-12
+#
+# The round trip grows with n because X^-1 (X Exp(delta)) subtracts translations of the order of n metres.  The
+# anisotropic chains set the constant: their damped system has condition number 5e6, and two orderings of the same
+# LU differ by about that times the rounding unit.
+SOLVE_REFERENCE_UNCERTAINTY = 1e-10

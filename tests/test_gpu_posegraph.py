@@ -1,6 +1,7 @@
 """GPU checks of the pose-graph optimiser (suma_posegraph_*, k_posegraph.hip) against the fp64 host restatement
-tests/posegraph_host.py: the linear system, the optimum on chain / loop / non-chain graphs, the default-parameter run,
-determinism, the API's error codes, and a loop closed end to end on the scan pipeline."""
+tests/posegraph_host.py: the linear system (also past one block of lanes), the optimum on chain / loop / non-chain
+graphs, the default-parameter run, determinism, the API's error codes, and a loop closed end to end on the scan pipeline.
+tests/test_gpu_posegraph_solve.py observes the linear solver alone, one damped solve at a time."""
 import math
 
 import numpy as np
@@ -75,6 +76,57 @@ def test_linearisation_equals_the_host(hip, kind):
         assert _rel(B, Hd[6 * a:6 * a + 6, 6 * b:6 * b + 6]) < 1e-12, (a, b)
     # error() is the sum of the factor energies
     assert abs(dg.error() - ph.error(hg, X)) <= 1e-12 * ph.error(hg, X)
+
+
+def test_linearisation_over_more_than_one_block(hip):
+    """k_pg_factor, k_pg_nodes and k_pg_pairs past their first block of 256 lanes: 600 nodes, 920 factors, 899 distinct
+    pairs.  300 edges join distinct nodes to one hub, half of them hub -> node and half node -> hub on either side of
+    it, so the hub's CSR row has 322 entries and its pair rows take both flip paths; 20 of those pairs are entered a
+    second time the other way round, so one pair row mixes them.  Same bars as test_linearisation_equals_the_host."""
+    rng = np.random.default_rng(4)
+    n, hub = 600, 300
+    X = np.array([ph.random_pose(rng, scale=3.0) for _ in range(n)])
+    others = [int(i) for i in rng.permutation(np.r_[0:hub - 1, hub + 2:n])[:300]]
+    pairs = [(i, i + 1) for i in range(n - 1)]
+    pairs += [(hub, i) if k % 2 == 0 else (i, hub) for k, i in enumerate(others)]
+    pairs += [(b, a) for a, b in pairs[n - 1:n - 1 + 40:2]]
+    assert len(pairs) + 1 == 920 and len({(min(a, b), max(a, b)) for a, b in pairs}) == 899
+    assert {a < b for a, b in pairs[n - 1:]} == {True, False}
+    edges = []
+    for a, b in pairs:
+        E = ph.random_pose(rng, scale=0.5)
+        edges.append((a, b, ph.compose(ph.inv(E), ph.compose(ph.inv(X[a]), X[b])), ph.info_matrix(rng, 10.0)))
+    hg = ph.HostGraph(X, edges)
+    dg = _device_graph(hip, hg)
+    lin = dg.linearize()
+    g, H, _, e = _host_blocks(hg, X)
+    blk = lambda a, b: H[6 * a:6 * a + 6, 6 * b:6 * b + 6].toarray()
+    assert lin["errors"].shape == e.shape and _rel(lin["errors"], e) < 1e-12
+    for f in range(len(e)):
+        assert np.linalg.norm(lin["errors"][f] - e[f]) <= 1e-12 * max(np.linalg.norm(e[f]), 1.0), f
+    assert _rel(lin["gradient"], g) < 1e-12
+    for i in range(n):
+        assert _rel(lin["gradient"][i], g[i]) < 1e-12, i
+        assert _rel(lin["diag"][i], blk(i, i)) < 1e-12, i
+        if i + 1 < n:
+            assert _rel(lin["band"][i], blk(i, i + 1)) < 1e-12, i
+    assert len(lin["off_pairs"]) == 300
+    assert {(int(a), int(b)) for a, b in lin["off_pairs"]} == {(min(i, hub), max(i, hub)) for i in others}
+    for (a, b), B in zip(lin["off_pairs"], lin["off"]):
+        assert a < b - 1
+        assert _rel(B, blk(a, b)) < 1e-12, (a, b)
+    assert abs(dg.error() - ph.error(hg, X)) <= 1e-12 * ph.error(hg, X)
+
+
+@pytest.mark.parametrize("m", [255, 256, 257, 513])
+def test_error_at_block_edges(hip, m):
+    """m factors (the prior and a chain's m - 1 edges): k_pg_energy's strided sum ends before, at and past a full trip
+    of its 256 lanes, and k_pg_factor's second block holds one lane at m = 257"""
+    hg = ph.solve_chain(m)
+    assert len(hg.edges) + 1 == m
+    dg = _device_graph(hip, hg)
+    e = ph.error(hg, np.array(hg.nodes))
+    assert abs(dg.error() - e) <= 1e-12 * e
 
 
 def _graphs():

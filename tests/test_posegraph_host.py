@@ -97,6 +97,78 @@ def test_lm_reaches_the_dense_gauss_newton_optimum():
     assert np.abs(grad).max() < 1e-6
 
 
+# ---- the single damped solve: the reference stays inside every cap that tests/test_gpu_posegraph_solve.py sets ---------
+#
+# The graphs come from ph.SOLVE_SEED.  The seed was picked so that the host alone meets the caps below: a GPU failure
+# of the same assertions is then the device's doing.
+
+SOLVE_CASES = ([("chain", n, 0) for n in ph.SOLVE_CHAIN_SIZES] + [("loops", n, L) for n, L in ph.SOLVE_LOOP_CASES]
+               + [("anisotropic", n, 0) for n in ph.SOLVE_ANISOTROPIC_SIZES])
+
+
+@pytest.mark.parametrize("kind,n,L", SOLVE_CASES)
+def test_single_solve_reference_is_known_to_the_recorded_uncertainty(kind, n, L):
+    c = ph.solve_case(kind, n, L)
+    hg, X = c["graph"], c["X"]
+    assert len(X) == n and np.abs(c["delta"]).max() > 0
+    s, ordering, trip = ph.reference_uncertainty(hg, X, ph.SOLVE_LAMBDA)
+    print(f"{kind} {n} {L}: ordering {ordering:.1e} round trip {trip:.1e}")
+    assert s <= ph.SOLVE_REFERENCE_UNCERTAINTY
+    # Levenberg-Marquardt accepts this step, so optimize(1) is one damped solve at SOLVE_LAMBDA and its poses are
+    # X Exp(delta)
+    assert ph.model_fidelity(hg, X, c["delta"].ravel()) > 0.9
+    # the PCG's answer is the direct solve's
+    d, it = ph.pcg_band(hg, X, ph.SOLVE_LAMBDA, c["cg_tolerance"], 1000)
+    assert it == c["pcg_iterations"]
+    assert max(ph.step_errors(d, c["delta"])) <= 1e3 * ph.SOLVE_REFERENCE_UNCERTAINTY
+
+
+@pytest.mark.parametrize("kind,n", [("chain", n) for n in ph.SOLVE_CHAIN_SIZES]
+                         + [("anisotropic", n) for n in ph.SOLVE_ANISOTROPIC_SIZES])
+def test_band_preconditioner_solves_a_chain_in_one_iteration(kind, n):
+    """on a chain the block-tridiagonal part is the whole system, ill-conditioned blocks or not"""
+    assert ph.solve_case(kind, n)["pcg_iterations"] == 1
+
+
+@pytest.mark.parametrize("n,L", ph.SOLVE_LOOP_CASES)
+def test_loop_graphs_have_the_asked_structure_and_end_within_rank_plus_one(n, L):
+    hg, pairs = ph.solve_loops(n, L)
+    assert len(set(pairs)) == L and all(0 <= a < b - 1 < n - 1 for a, b in pairs)
+    assert (0, n - 1) in pairs
+    loop_edges = [(a, b) for a, b, _, _ in hg.edges if abs(a - b) > 1]
+    assert {(min(a, b), max(a, b)) for a, b in loop_edges} == set(pairs)
+    # one pair is entered twice, in opposite directions
+    assert len(loop_edges) == L + 1
+    assert sum((b, a) in loop_edges for a, b in loop_edges) == 2
+    # one node takes part in three off-band pairs; two distinct pairs can give a node only two
+    count = np.bincount(np.array(pairs).ravel(), minlength=n)
+    assert count.max() >= min(L, 3)
+    # M^-1 A = I + M^-1 E with E of rank <= 12 per off-band pair: exact CG ends within rank + 1 steps
+    it = ph.solve_case("loops", n, L)["pcg_iterations"]
+    print(f"loops ({n}, {L}): {it} iterations, cap {12 * L + 1}")
+    assert 1 < it <= 12 * L + 1
+
+
+def test_anisotropic_blocks_are_ill_conditioned_and_full():
+    for n in ph.SOLVE_ANISOTROPIC_SIZES:
+        hg = ph.solve_case("anisotropic", n)["graph"]
+        assert len(hg.edges) == n - 1
+        for _, _, _, O in hg.edges:
+            w = np.linalg.eigvalsh(O)
+            assert abs(w[-1] / w[0] - 1e9) < 1e9 * 1e-6
+            assert np.abs(O - np.diag(np.diag(O))).max() > 1e3
+
+
+@pytest.mark.parametrize("n,node", [(16, 7), (257, 0), (1025, 511)])
+def test_iteration_count_tells_an_inexact_preconditioner(n, node):
+    """without the band block (node, node + 1) the preconditioner is still positive-definite and CG still reaches the
+    same delta, but not in one iteration: the count discriminates"""
+    c = ph.solve_case("chain", n)
+    d, it = ph.pcg_band(c["graph"], c["X"], ph.SOLVE_LAMBDA, 1e-6, 1000, drop_band=node)
+    assert it > 1
+    assert ph.step_errors(d, c["delta"])[0] < 1e-3  # it converges (the rule stops at 1e-6 in the M^-1 norm)
+
+
 def test_default_parameters_stop_on_the_relative_decrease():
     rng = np.random.default_rng(8)
     _, g = ph.chain_graph(40, 6, rng)
