@@ -422,7 +422,9 @@ typedef struct suma_semantic_knn {
  *   ranked by |range - the point's range| * (1 - the normalised Gaussian weight of the offset), ties to the lower
  *   window index.  The first K vote for their pixel's class (the reference's argmax rule, on the index) unless it is
  *   none, index 0 or (cutoff > 0) farther than cutoff; the most votes win, equal counts go to the lowest index.
- *   label = label_map[winner], prob = the largest pixel prob among its voters; no vote gives (0, 0).  search = 1 or
+ *   label = label_map[winner], prob = the largest pixel prob among its voters; no vote gives (0, 0), and so does a
+ *   point that suma_semantic_project would not have projected (d_pixel outside [0, H * W), or -- with a d_pixel that was
+ *   not made from these points -- a zero, non-finite or overflowing range of its own).  search = 1 or
  *   k = 1 gives the plain back-projection for every point whose pixel class is >= 1.  Runs on the ctx stream; its
  *   scratch (12 bytes a pixel, kept by the ctx) is used only there.  Invalid parameters return SUMA_ERR_INVALID. */
 int suma_semantic_unproject_knn(suma_ctx* ctx, const suma_semantic_params* sp, const suma_semantic_knn* knn,

@@ -17,6 +17,10 @@
  * Projection, point i = (x, y, z, r):
  *   depth = sqrt(fma(z, z, fma(y, y, x * x)))
  *   projected iff depth > 0 and depth <= FLT_MAX      (a NaN / inf coordinate or an overflowing range is not)
+ *     The squares are fp32: with every |coordinate| below 2^-75 (about 2.6e-23) each square rounds to 0 and depth is 0;
+ *     with one of 2^64 (about 1.8e19) or more its square is inf and so is depth.  Such a point is NOT projected although
+ *     its true range is a finite fp32 number.  Between 2^-75 and 2^-60 the largest square is subnormal and depth carries
+ *     few bits; between 2^60 and 2^64 the sum may overflow.  No lidar returns such coordinates; nothing rescales.
  *   yaw   = -sdm_atan2(y, x)
  *   pitch = sdm_asin(z / depth)
  *   fu = sdm_floor((0.5f * (yaw / pi_f + 1.0f)) * Wf)

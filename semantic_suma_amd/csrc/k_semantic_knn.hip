@@ -18,7 +18,9 @@
  *  2. Pixel class.  ks_unproject's rule on pixel p's scores, softmax included in logits mode, with the class index in
  *     place of the label: cls = none, prob = 0; for j in class order: if (prob <= s_j) { cls = j; prob = s_j; }.
  *     All-negative or NaN scores leave cls = none.  Empty pixels get a class too (the network scores every pixel).
- *  3. Window.  Point i with pixel[i] = v * W + u (pixel < 0 or >= H * W: output (0, 0), as the plain path); offsets
+ *  3. Window.  Point i with pixel[i] = v * W + u (pixel < 0 or >= H * W: output (0, 0), as the plain path; so is a
+ *     point whose own range r_i is not in (0, FLT_MAX] -- ks_scatter gives such a point no pixel, so this only meets a
+ *     pixel array that was not made from these points; without it d would be NaN or inf in every slot); offsets
  *     dy, dx in [-R, R], window index t = (dy + R) * S + (dx + R), neighbour (v + dy, u + dx).  Outside the image:
  *     range 0.0f, class none; columns do not wrap (the published zero padding).  The centre t_c = (S * S - 1) / 2 has
  *     range r_i, but the pixel's class and prob.
@@ -35,8 +37,8 @@
  *     published code reports class 1, an artefact of its argmax over an all-zero row.
  *  search = 1 or k = 1 is the plain back-projection for every point whose pixel class is >= 1.
  *
- * Device form of 6 -- 8: d >= 0 and never NaN (range >= 0 or +inf, r_i finite, w > 0 off the centre), so bits(d) orders
- * as d does.  The centre is taken first; the k - 1 others are found by k - 1 sweeps over the window, each taking the
+ * Device form of 6 -- 8: d >= 0 and never NaN (range >= 0 or +inf, r_i finite by rule 3, w > 0 off the centre), so
+ * bits(d) orders as d does.  The centre is taken first; the k - 1 others are found by k - 1 sweeps over the window, each taking the
  * smallest (bits(d), t) above the previous one.  The votes go into bit-sliced counters (bit j of plane b = bit b of class
  * j's count), and the winner is found by narrowing the voted classes plane by plane from the top: no register array is
  * indexed at run time, so nothing goes to scratch.  kk_points<5, 5> is the published default with S and K at compile
@@ -161,6 +163,11 @@ __global__ void __launch_bounds__(256)
   if (pix >= 0 && (uint32_t)pix < a.P) {
     const float4 pt = pts[i];
     const float ri = sdm_sqrt(__builtin_fmaf(pt.z, pt.z, __builtin_fmaf(pt.y, pt.y, pt.x * pt.x)));
+    if (!(ri > 0.0f && ri <= FLT_MAX)) { /* rule 3: a pixel from another scan's projection; also keeps d free of NaN */
+      labels[i] = 0.0f;
+      probs[i] = 0.0f;
+      return;
+    }
     const int32_t v = pix / a.W, u = pix - v * a.W;
     uint32_t d[S2]; /* bits of d[t]; the centre's is never read */
 #pragma unroll

@@ -96,6 +96,7 @@ void sem_unproject_knn(const suma_semantic_params* sp, const suma_semantic_knn* 
     probs[i] = 0.0f;
     if (pix < 0 || (uint32_t)pix >= P) continue;
     const float ri = depth_of(points + 4 * (size_t)i);
+    if (!(ri > 0.0f && ri <= FLT_MAX)) continue; /* rule 3: not a point the projection gives a pixel */
     const int32_t v = pix / W, u = pix % W;
     float d[KNN_MAX], pr[KNN_MAX];
     int32_t c[KNN_MAX];

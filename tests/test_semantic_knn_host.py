@@ -226,7 +226,7 @@ def numpy_knn(sp, kp, pts, scores, pixel, proj_idx):
     for x in e:
         total += x
     w = (1.0 - e / total).astype(np.float32)
-    ok = pixel >= 0
+    ok = (pixel >= 0) & (r_pt > 0) & (r_pt <= np.finfo(np.float32).max)  # rule 3: the point's own range in (0, FLT_MAX]
     v, u = np.divmod(pixel[ok], W)
     yy, xx = v[:, None] + dy[None], u[:, None] + dx[None]
     inside = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)
