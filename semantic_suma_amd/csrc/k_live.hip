@@ -273,7 +273,6 @@ int live_alloc(suma_ctx* c, Live& lv, const suma_grid_params& gp, const suma_gri
   if (e == hipSuccess) e = nw.ground.alloc(n);
   if (e == hipSuccess) e = nw.state.alloc(n);
   if (e == hipSuccess) e = nw.words.alloc(LIVE_WORDS);
-  if (e == hipSuccess) e = nw.stage_h.alloc(LIVE_WORDS);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     return fail(c, SUMA_ERR_NOMEM, "suma_localizer_enable_live_grid: no device memory for " + std::to_string(n) + " cells");

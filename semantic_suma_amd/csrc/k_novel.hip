@@ -366,8 +366,8 @@ int novel_collect(suma_ctx* c, Novel& nv, const LocMap& m, uint32_t n_spans, uin
 }
 
 int novel_fuse(suma_ctx* c, Novel& nv, uint32_t n, const suma_novel_fuse_params& fp, suma_world_surfel* d_out,
-               uint32_t* d_views, uint32_t capacity, uint32_t counters_out[3]) {
-  counters_out[0] = counters_out[1] = counters_out[2] = 0u;
+               uint32_t* d_views, uint32_t capacity, uint32_t* counters_h) {
+  counters_h[0] = counters_h[1] = counters_h[2] = 0u;
   if (!n) return SUMA_OK;
   hipStream_t st = c->stream;
   int r;
@@ -411,8 +411,7 @@ int novel_fuse(suma_ctx* c, Novel& nv, uint32_t n, const suma_novel_fuse_params&
   kn_reduce<<<blocks, NOV_THREADS, 0, st>>>(n, key.current(), idx.current(), cand, u0, u1, views, fp.confidence,
                                             reinterpret_cast<float4*>(d_out), d_views, capacity, counters);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(nv.stage_h, counters, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(counters_h, counters, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  memcpy(counters_out, nv.stage_h.p, 3 * sizeof(uint32_t));
   return SUMA_OK;
 }

@@ -404,7 +404,6 @@ int objects_alloc(suma_ctx* c, Objects& ob, const suma_object_params& op, uint32
   if (e == hipSuccess) e = nw.rec.alloc(4 * (size_t)op.max_objects);
   if (e == hipSuccess) e = nw.ids.alloc(P);
   if (e == hipSuccess) e = nw.flags_in.alloc(P);
-  if (e == hipSuccess) e = nw.stage_h.alloc(8);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     return fail(c, SUMA_ERR_NOMEM, "suma_localizer_enable_objects: no device memory for " + std::to_string(P) + " texels");

@@ -547,7 +547,6 @@ int tracks_alloc(suma_ctx* c, Tracks& tk, const suma_track_params& tp, uint32_t 
   if (e == hipSuccess) e = nw.slots.alloc(tp.max_tracks);
   if (e == hipSuccess) e = nw.out.alloc(tp.max_tracks);
   if (e == hipSuccess) e = nw.words.alloc(TRK_WORDS);
-  if (e == hipSuccess) e = nw.stage_h.alloc(TRK_WORDS);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     return fail(c, SUMA_ERR_NOMEM, "suma_localizer_enable_tracks: no device memory for " + std::to_string(max_objects) +

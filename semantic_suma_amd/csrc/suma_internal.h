@@ -654,7 +654,6 @@ struct Novel {
   DevBuf<uint8_t> mark, flag;    /* one byte a texel of the data image */
   DevBuf<uint32_t> block_counts; /* kn_collect's counts, 8 words a block of 256 texels */
   DevBuf<NovelState> state;
-  PinnedBuf<uint32_t> stage_h;   /* 16 words: the state, or the fusion's counters, on their way to the host */
   DevBuf<char> scratch, tmp;     /* the fusion's arrays and rocPRIM's temporary storage */
   DevBuf<float4> fused;          /* the fusion's output on its way to the host */
   DevBuf<uint32_t> fused_views;
@@ -662,10 +661,10 @@ struct Novel {
 /* one collection of frame f at pose T over the first `total` window records of the span table in m.spans, enqueued */
 int novel_collect(suma_ctx* c, Novel& nv, const LocMap& m, uint32_t n_spans, uint32_t total, const suma_frame* f,
                   const double T[16], uint32_t scan_id);
-/* candidates 0 .. n - 1 fused into d_out / d_views (device, capacity records); blocking.  counters_out: n_dropped,
- * n_voxels, n_out */
+/* candidates 0 .. n - 1 fused into d_out / d_views (device, capacity records); blocking.  counters_h: three words of the
+ * caller's pinned block, which hold n_dropped, n_voxels, n_out when the call returns */
 int novel_fuse(suma_ctx* c, Novel& nv, uint32_t n, const suma_novel_fuse_params& fp, suma_world_surfel* d_out,
-               uint32_t* d_views, uint32_t capacity, uint32_t counters_out[3]);
+               uint32_t* d_views, uint32_t capacity, uint32_t* counters_h);
 
 /* k_objects.hip (the specification is there): the objects of one scan's unexplained texels */
 struct ObjAcc { /* what the members of a component add up at their root, 96 bytes */
@@ -688,7 +687,6 @@ struct Objects {
   DevBuf<float4> rec;            /* 4 float4 a record, op.max_objects of them */
   DevBuf<uint32_t> ids;
   DevBuf<uint8_t> flags_in;      /* suma_localizer_segment_flags' flag image */
-  PinnedBuf<uint32_t> stage_h;   /* the counts on their way to the host */
 };
 /* the blocks for P texels and op.max_objects records; the caller has drained the stream */
 int objects_alloc(suma_ctx* c, Objects& ob, const suma_object_params& op, uint32_t P);
@@ -710,7 +708,6 @@ struct Live {
   DevBuf<suma_live_cell> state;
   DevBuf<uint32_t> words;        /* LIVE_WORDS: the counts of the last update, "some cell has a hit", a compose's stats */
   DevBuf<uint8_t> flags_in;      /* suma_localizer_live_update_flags' flag image, without objects */
-  PinnedBuf<uint32_t> stage_h;
 };
 /* the blocks for gp's raster, the static cells copied from d_cells, the state zeroed; blocking */
 int live_alloc(suma_ctx* c, Live& lv, const suma_grid_params& gp, const suma_grid_cell* d_cells);
@@ -744,7 +741,6 @@ struct Tracks {
   DevBuf<float4> rec_in;         /* suma_localizer_track_objects' records */
   DevBuf<suma_object_track> slots, out;
   DevBuf<uint32_t> words;        /* TRK_WORDS: the counts of the last update, its live tracks, births since the clear, n of rec_in */
-  PinnedBuf<uint32_t> stage_h;
 };
 /* the blocks for max_objects objects and tp.max_tracks slots, cleared; the caller has drained the stream */
 int tracks_alloc(suma_ctx* c, Tracks& tk, const suma_track_params& tp, uint32_t max_objects);

@@ -17,9 +17,12 @@
 
 #include "suma_internal.h"
 
+enum { STAGE_WORDS = 16 };
+
 struct suma_localizer {
   suma_ctx* c = nullptr;
   suma_frame* frame = nullptr; /* the scan, K1-K3 */
+  PinnedBuf<uint32_t> stage_h; /* STAGE_WORDS: whatever few device words a call reads back, on their way to the host */
   suma_localizer_params lp;
   LocMap map;
   bool have_map = false, have_pose = false, first = true;
@@ -31,7 +34,6 @@ struct suma_localizer {
   bool ev_wanted = false;
   suma_change_params cp;
   DevBuf<uint32_t> ev_totals;             /* the nine totals of one observation */
-  PinnedBuf<uint32_t> ev_totals_h;
   DevBuf<suma_change_evidence> ev_source; /* the evidence in source order, made by every download */
   suma_change_counts last_counts;
   int32_t last_observed = 0;
@@ -58,6 +60,128 @@ bool finite16(const double* T) {
   for (int k = 0; k < 16; ++k)
     if (!std::isfinite(T[k])) return false;
   return true;
+}
+
+/* ---- the decisions every layer's entries share, each stated once ---- */
+
+/* what a caller's frame and pose must satisfy before a layer reads them */
+int frame_pose_check(suma_localizer* l, const suma_frame* frame, const double* T, const char* who) {
+  suma_ctx* c = l->c;
+  if (!frame || !T) return fail(c, SUMA_ERR_INVALID, std::string(who) + ": NULL argument");
+  if (frame->ctx != c) return fail(c, SUMA_ERR_INVALID, std::string(who) + ": the frame belongs to another ctx");
+  if (frame->width != c->p.data_width || frame->height != c->p.data_height)
+    return fail(c, SUMA_ERR_INVALID, std::string(who) + ": the frame must have the data image's size");
+  if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, std::string(who) + ": non-finite pose");
+  return SUMA_OK;
+}
+
+/* in front of the first launch that reads frame f on the ctx stream: an earlier suma_preprocess on the side stream comes
+ * first, and the frame counts as used */
+int frame_read_begin(suma_ctx* c, const suma_frame* f) {
+  if (c->gate_pending) HIP_TRY(c, flush_gate(c));
+  const_cast<suma_frame*>(f)->last_access = ++c->enq_seq;
+  return SUMA_OK;
+}
+
+/* a few words (at most STAGE_WORDS) at d_src into host words, blocking: through the localiser's one pinned block */
+int read_words(suma_localizer* l, const void* d_src, size_t bytes, void* out) {
+  suma_ctx* c = l->c;
+  HIP_TRY(c, hipMemcpyAsync(l->stage_h, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(out, l->stage_h.p, bytes);
+  return SUMA_OK;
+}
+static_assert(sizeof(NovelState) <= STAGE_WORDS * 4 && LIVE_WORDS <= STAGE_WORDS && TRK_WORDS <= STAGE_WORDS &&
+              sizeof(suma_change_counts) <= STAGE_WORDS * 4 && sizeof(suma_object_counts) <= STAGE_WORDS * 4,
+              "the largest read-back fits the pinned block");
+
+/* a capacity-bounded download: *n is the total whatever the capacity, the first min(total, capacity) elements of d_src
+ * go to out (a device block, or host memory), blocking.  What a site reports beyond that -- an overflow, after the
+ * outputs are filled -- is the site's */
+int download(suma_ctx* c, void* out, uint32_t capacity, uint32_t* n, const void* d_src, uint32_t total, size_t elem_bytes,
+             bool to_device) {
+  *n = total;
+  const uint32_t m = total < capacity ? total : capacity;
+  if (!m) return SUMA_OK;
+  HIP_TRY(c, hipMemcpyAsync(out, d_src, (size_t)m * elem_bytes, to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                            c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SUMA_OK;
+}
+
+/* an update's stamp must lie above the last one's */
+int stamp_check(suma_localizer* l, uint32_t scan_id, uint32_t last_stamp, const char* whose, const char* who) {
+  const uint32_t s = scan_id + 1u;
+  if (s > last_stamp) return SUMA_OK;
+  return fail(l->c, SUMA_ERR_INVALID, std::string(who) + ": scan_id " + std::to_string(scan_id) + " gives " + whose + " the stamp " +
+                                      std::to_string(s) + ", not above the last update's " + std::to_string(last_stamp));
+}
+
+/* the stamps of every layer run_layers will update, checked in front of everything the call launches or writes: a
+ * refusal leaves all layers as they were.  with_live: the entry updates the live layer (suma_hip.h) */
+int stamps_check(suma_localizer* l, uint32_t scan_id, const char* who, bool with_live) {
+  int r = SUMA_OK;
+  if (with_live && l->lv.on) r = stamp_check(l, scan_id, l->lv.last_stamp, "the live layer", who);
+  if (!r && l->tk.on) r = stamp_check(l, scan_id, l->tk.last_stamp, "the tracks", who);
+  return r;
+}
+
+/* what runs behind a flag image (d_flags: one byte a texel, on the device) of frame f at pose T, enqueued on the ctx
+ * stream in this order: with objects on, the segmentation; with tracks on, their update behind it; with with_live and
+ * the live layer on, its update behind all.  The caller has passed stamps_check and frame_read_begin.  ob.segmented is
+ * set as soon as the segmentation is enqueued, whatever fails behind it */
+int run_layers(suma_localizer* l, const suma_frame* f, const uint8_t* d_flags, const double T[16], uint32_t scan_id,
+               bool with_live) {
+  suma_ctx* c = l->c;
+  Objects& ob = l->ob;
+  int r = SUMA_OK;
+  if (ob.on) {
+    if ((r = objects_segment(c, ob, f, d_flags, T, scan_id))) return r;
+    ob.segmented = 1;
+    /* word 5: the objects stored */
+    if (l->tk.on && (r = tracks_update(c, l->tk, ob.rec, ob.state.p + 5, scan_id + 1u))) return r;
+  }
+  if (with_live && l->lv.on) r = live_update(c, l->lv, f, d_flags, ob.on ? ob.ids.p : nullptr, T, scan_id + 1u);
+  return r;
+}
+
+/* which layer is made of which: novelty's flags feed the objects and the live layer, the objects' records feed the
+ * tracks (the enables refuse a layer whose source is off).  A layer's blocks go with those of everything made of it; the
+ * caller has drained the stream */
+enum Layer { LAYER_NOVELTY, LAYER_OBJECTS, LAYER_LIVE, LAYER_TRACKS };
+void release_layer(suma_localizer* l, Layer which) {
+  const bool novelty = which == LAYER_NOVELTY, objects = novelty || which == LAYER_OBJECTS;
+  if (novelty) l->nv = Novel();
+  if (objects) l->ob = Objects();
+  if (novelty || which == LAYER_LIVE) l->lv = Live();
+  if (objects || which == LAYER_TRACKS) l->tk = Tracks();
+}
+
+bool layer_on(const suma_localizer* l, Layer which) {
+  if (which == LAYER_NOVELTY) return l->nv.on;
+  if (which == LAYER_OBJECTS) return l->ob.on;
+  if (which == LAYER_LIVE) return l->lv.on;
+  return l->tk.on;
+}
+
+/* a suma_localizer_disable_*: nothing when the layer is off */
+int disable_layer(suma_localizer* l, Layer which) {
+  if (!layer_on(l, which)) return SUMA_OK;
+  HIP_TRY(l->c, hipStreamSynchronize(l->c->stream)); /* a scan's work may still write the blocks */
+  release_layer(l, which);
+  return SUMA_OK;
+}
+
+/* the last scan's results, as the entries report them: the observation (last_counts, last_observed), the collection
+ * (last_collected) and the segmentation (ob.segmented: the objects' blocks hold one) */
+enum { LAST_OBSERVATION = 1, LAST_COLLECTION = 2, LAST_SEGMENTATION = 4, LAST_ALL = 7 };
+void forget_last(suma_localizer* l, unsigned what) {
+  if (what & LAST_OBSERVATION) {
+    memset(&l->last_counts, 0, sizeof(l->last_counts));
+    l->last_observed = 0;
+  }
+  if (what & LAST_COLLECTION) l->last_collected = 0;
+  if (what & LAST_SEGMENTATION) l->ob.segmented = 0;
 }
 
 /* the window around (oi, oj) into the ctx's active buffer; a window beyond max_surfels is refused before anything is
@@ -88,79 +212,37 @@ int observe(suma_localizer* l, const suma_frame* f, const double T[16], suma_cha
   if (l->n_window) {
     int r = grow(c, l->ev_totals, 9, {c->stream});
     if (r < 0) return r;
-    r = grow(c, l->ev_totals_h, 9, {c->stream});
-    if (r < 0) return r;
-    if (c->gate_pending) HIP_TRY(c, flush_gate(c));
-    const_cast<suma_frame*>(f)->last_access = ++c->enq_seq;
+    if ((r = frame_read_begin(c, f))) return r;
     HIP_TRY(c, hipMemsetAsync(l->ev_totals, 0, 9 * sizeof(uint32_t), c->stream));
     {
       ProfScope ps(c, "change_observe", 64.0 * l->n_window + 48.0 * f->width * f->height);
       HIP_TRY(c, launch_kc_observe(c, l->map, (uint32_t)l->spans.size(), l->n_window, f, T, l->cp, l->ev_totals));
     }
-    HIP_TRY(c, hipMemcpyAsync(l->ev_totals_h, l->ev_totals, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    memcpy(&out, l->ev_totals_h.p, sizeof(out));
+    if ((r = read_words(l, l->ev_totals, sizeof(out), &out))) return r;
   }
   if (counts) *counts = out;
   return SUMA_OK;
 }
 
-/* an update's stamp must lie above the last one's: checked in front of everything an update's call launches */
-int live_stamp_check(suma_localizer* l, uint32_t scan_id, const char* who) {
-  const uint32_t s = scan_id + 1u;
-  if (s > l->lv.last_stamp) return SUMA_OK;
-  return fail(l->c, SUMA_ERR_INVALID, std::string(who) + ": scan_id " + std::to_string(scan_id) + " gives the live layer the stamp " +
-                                      std::to_string(s) + ", not above the last update's " + std::to_string(l->lv.last_stamp));
-}
-
-/* an update's stamp must lie above the last one's: checked in front of everything an update's call launches */
-int tracks_stamp_check(suma_localizer* l, uint32_t scan_id, const char* who) {
-  const uint32_t s = scan_id + 1u;
-  if (s > l->tk.last_stamp) return SUMA_OK;
-  return fail(l->c, SUMA_ERR_INVALID, std::string(who) + ": scan_id " + std::to_string(scan_id) + " gives the tracks the stamp " +
-                                      std::to_string(s) + ", not above the last update's " + std::to_string(l->tk.last_stamp));
-}
-
-/* the tracker's update behind a segmentation that has just been enqueued */
-int track_segmentation(suma_localizer* l, uint32_t scan_id) {
-  return tracks_update(l->c, l->tk, l->ob.rec, l->ob.state.p + 5, scan_id + 1u); /* word 5: the objects stored */
-}
-
-/* one collection over the current window, enqueued on the ctx stream; with objects on, its segmentation behind it, with
- * tracks on, their update behind that, and with the live layer on, its update behind all.  A call that collects nothing
- * leaves no segmentation */
+/* one collection over the current window, enqueued on the ctx stream, and the layers behind its flags.  The caller has
+ * forgotten the last collection and segmentation: a call that collects nothing leaves none */
 int collect(suma_localizer* l, const suma_frame* f, const double T[16], uint32_t scan_id) {
   suma_ctx* c = l->c;
-  l->ob.segmented = 0;
   if (!l->n_window) return SUMA_OK;
-  if (l->lv.on) {
-    int r = live_stamp_check(l, scan_id, "suma_localizer: the collection");
-    if (r) return r;
-  }
-  if (l->tk.on) {
-    int r = tracks_stamp_check(l, scan_id, "suma_localizer: the collection");
-    if (r) return r;
-  }
-  if (c->gate_pending) HIP_TRY(c, flush_gate(c));
-  const_cast<suma_frame*>(f)->last_access = ++c->enq_seq;
-  int r = novel_collect(c, l->nv, l->map, (uint32_t)l->spans.size(), l->n_window, f, T, scan_id);
+  int r = stamps_check(l, scan_id, "suma_localizer: the collection", true);
   if (r) return r;
-  if (l->ob.on) {
-    r = objects_segment(c, l->ob, f, l->nv.flag, T, scan_id); /* behind the collection on the same stream, enqueued only */
-    if (r) return r;
-    l->ob.segmented = 1;
-    if (l->tk.on && (r = track_segmentation(l, scan_id))) return r;
-  }
-  if (l->lv.on) r = live_update(c, l->lv, f, l->nv.flag, l->ob.on ? l->ob.ids.p : nullptr, T, scan_id + 1u);
-  return r;
+  if ((r = frame_read_begin(c, f))) return r;
+  r = novel_collect(c, l->nv, l->map, (uint32_t)l->spans.size(), l->n_window, f, T, scan_id);
+  if (r) return r;
+  return run_layers(l, f, l->nv.flag, T, scan_id, true);
 }
 
-int change_params_check(const suma_change_params& q, std::string* why) {
-  if (!(std::isfinite(q.free_margin) && q.free_margin > 0.0f)) *why = "free_margin must be finite and > 0";
-  else if (!(std::isfinite(q.min_view_cos) && q.min_view_cos >= 0.0f && q.min_view_cos < 1.0f)) *why = "min_view_cos must lie in [0, 1)";
-  else if (!(std::isfinite(q.max_range) && q.max_range > 0.0f)) *why = "max_range must be finite and > 0";
-  else return SUMA_OK;
-  return SUMA_ERR_INVALID;
+/* NULL, or what is wrong with the values */
+const char* change_params_why(const suma_change_params& q) {
+  if (!(std::isfinite(q.free_margin) && q.free_margin > 0.0f)) return "free_margin must be finite and > 0";
+  if (!(std::isfinite(q.min_view_cos) && q.min_view_cos >= 0.0f && q.min_view_cos < 1.0f)) return "min_view_cos must lie in [0, 1)";
+  if (!(std::isfinite(q.max_range) && q.max_range > 0.0f)) return "max_range must be finite and > 0";
+  return nullptr;
 }
 
 }  // namespace
@@ -203,6 +285,11 @@ extern "C" int suma_localizer_create(const suma_params* params, const suma_local
     suma_localizer_destroy(l);
     return r;
   }
+  if (l->stage_h.alloc(STAGE_WORDS) != hipSuccess) {
+    (void)hipGetLastError();
+    suma_localizer_destroy(l);
+    return fail_without_ctx(SUMA_ERR_NOMEM, "suma_localizer_create: no pinned memory for the read-back block");
+  }
   l->lp = q;
   suma_change_params_default(&l->cp);
   memset(&l->last_counts, 0, sizeof(l->last_counts));
@@ -217,11 +304,8 @@ extern "C" void suma_localizer_destroy(suma_localizer* l) {
   if (!l) return;
   if (l->c && l->c->stream) hipStreamSynchronize(l->c->stream);
   l->map = LocMap(); /* device blocks go before the ctx */
-  l->ev_totals.reset(), l->ev_totals_h.reset(), l->ev_source.reset();
-  l->nv = Novel();
-  l->ob = Objects();
-  l->lv = Live();
-  l->tk = Tracks();
+  l->ev_totals.reset(), l->ev_source.reset(), l->stage_h.reset();
+  release_layer(l, LAYER_NOVELTY);
   l->dk.points.reset(), l->dk_points.reset(), l->dk_labels.reset(), l->dk_probs.reset();
   suma_frame_destroy(l->frame);
   suma_ctx_destroy(l->c);
@@ -242,10 +326,7 @@ extern "C" int suma_localizer_set_map_device(suma_localizer* l, const suma_world
   if (l->lv.on && (r = live_clear(c, l->lv))) return r;
   if (l->tk.on && (r = tracks_clear(c, l->tk))) return r;
   l->scan_count = 0;
-  l->last_collected = 0;
-  l->ob.segmented = 0;
-  memset(&l->last_counts, 0, sizeof(l->last_counts));
-  l->last_observed = 0;
+  forget_last(l, LAST_ALL);
   l->have_map = true;
   l->have_pose = false;
   l->n_window = 0, l->rebuilds = 0;
@@ -295,7 +376,7 @@ static int preprocess_deskewed(suma_localizer* l, const suma_float4* points, con
     const size_t cap = (size_t)n + n / 4 + 1024;
     if (grow(c, l->dk_points, n, {c->stream}, cap) < 0 || (labels && grow(c, l->dk_labels, n, {c->stream}, cap) < 0) ||
         (probs && grow(c, l->dk_probs, n, {c->stream}, cap) < 0))
-      return SUMA_ERR_HIP;
+      return SUMA_ERR_HIP; /* grow has left its text in the ctx */
     HIP_TRY(c, hipMemcpyAsync(l->dk_points, points, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     if (labels) HIP_TRY(c, hipMemcpyAsync(l->dk_labels, labels, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (probs) HIP_TRY(c, hipMemcpyAsync(l->dk_probs, probs, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -400,8 +481,7 @@ static int process_scan(suma_localizer* l, const suma_float4* points, const floa
   res->n_window = l->n_window;
   /* 8. with evidence on: one observation of the scan's own frame at the final pose (k_change.hip) */
   if (l->map.has_evidence && !frame_ready) {
-    memset(&l->last_counts, 0, sizeof(l->last_counts));
-    l->last_observed = 0;
+    forget_last(l, LAST_OBSERVATION);
     if (l->n_window && (res->tracked || !l->cp.tracked_only) && finite16(pose)) {
       int r = observe(l, l->frame, pose, &l->last_counts);
       if (r) return r;
@@ -412,8 +492,7 @@ static int process_scan(suma_localizer* l, const suma_float4* points, const floa
   if (!frame_ready) {
     const uint32_t scan_id = l->scan_count++;
     if (l->nv.on) {
-      l->last_collected = 0;
-      l->ob.segmented = 0;
+      forget_last(l, LAST_COLLECTION | LAST_SEGMENTATION);
       if (l->n_window && (res->tracked || !l->nv.np.tracked_only) && finite16(pose)) {
         int r = collect(l, l->frame, pose, scan_id);
         if (r) return r;
@@ -628,8 +707,7 @@ extern "C" int suma_localizer_enable_evidence(suma_localizer* l, const suma_chan
   suma_change_params q;
   suma_change_params_default(&q);
   if (cp) q = *cp;
-  std::string why;
-  if (change_params_check(q, &why)) return fail(l->c, SUMA_ERR_INVALID, "suma_localizer_enable_evidence: " + why);
+  if (const char* why = change_params_why(q)) return fail(l->c, SUMA_ERR_INVALID, std::string("suma_localizer_enable_evidence: ") + why);
   l->cp = q;
   l->ev_wanted = true;
   return SUMA_OK;
@@ -646,8 +724,7 @@ extern "C" int suma_localizer_disable_evidence(suma_localizer* l) {
     l->map.src_idx.reset();
     l->ev_source.reset();
   }
-  l->last_observed = 0;
-  memset(&l->last_counts, 0, sizeof(l->last_counts));
+  forget_last(l, LAST_OBSERVATION);
   return SUMA_OK;
 }
 
@@ -661,14 +738,9 @@ static int evidence_ready(suma_localizer* l, const char* who) {
 extern "C" int suma_localizer_observe_frame(suma_localizer* l, const suma_frame* frame, const double T[16],
                                             suma_change_counts* counts) {
   if (!l) return SUMA_ERR_INVALID;
-  suma_ctx* c = l->c;
   int r = evidence_ready(l, "suma_localizer_observe_frame");
+  if (!r) r = frame_pose_check(l, frame, T, "suma_localizer_observe_frame");
   if (r) return r;
-  if (!frame || !T) return fail(c, SUMA_ERR_INVALID, "suma_localizer_observe_frame: NULL argument");
-  if (frame->ctx != c) return fail(c, SUMA_ERR_INVALID, "suma_localizer_observe_frame: the frame belongs to another ctx");
-  if (frame->width != c->p.data_width || frame->height != c->p.data_height)
-    return fail(c, SUMA_ERR_INVALID, "suma_localizer_observe_frame: the frame must have the data image's size");
-  if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_observe_frame: non-finite pose");
   return observe(l, frame, T, counts);
 }
 
@@ -701,15 +773,9 @@ static int evidence_download(suma_localizer* l, suma_change_evidence* out, uint3
   int r = evidence_ready(l, who);
   if (r) return r;
   if (!n || (capacity && !out)) return fail(c, SUMA_ERR_INVALID, std::string(who) + ": NULL argument");
-  *n = l->map.n_total;
-  const uint32_t m = *n < capacity ? *n : capacity;
-  if (!m) return SUMA_OK;
-  r = evidence_to_source_order(l);
-  if (r) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, l->ev_source, (size_t)m * sizeof(suma_change_evidence),
-                            to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return SUMA_OK;
+  *n = l->map.n_total; /* also when the scatter below fails */
+  if (capacity && (r = evidence_to_source_order(l))) return r; /* nothing is made for a call that only asks for n */
+  return download(c, out, capacity, n, l->ev_source, l->map.n_total, sizeof(suma_change_evidence), to_device);
 }
 
 extern "C" int suma_localizer_evidence(suma_localizer* l, suma_change_evidence* host, uint32_t capacity, uint32_t* n) {
@@ -727,8 +793,7 @@ extern "C" int suma_localizer_clear_evidence(suma_localizer* l) {
   if (r) return r;
   if (l->map.n_kept)
     HIP_TRY(c, hipMemsetAsync(l->map.evidence, 0, (size_t)l->map.n_kept * sizeof(suma_change_evidence), c->stream));
-  memset(&l->last_counts, 0, sizeof(l->last_counts));
-  l->last_observed = 0;
+  forget_last(l, LAST_OBSERVATION);
   return SUMA_OK;
 }
 
@@ -765,6 +830,14 @@ extern "C" void suma_novel_fuse_params_default(const suma_params* params, suma_n
   fp->confidence = (params ? params->confidence_threshold : 0.0f) + 1.0f;
 }
 
+/* NULL, or what is wrong with the values */
+static const char* novel_params_why(const suma_novel_params& q) {
+  if (!(std::isfinite(q.agree_margin) && q.agree_margin > 0.0f)) return "agree_margin must be finite and > 0";
+  if (!(std::isfinite(q.max_range) && q.max_range > 0.0f)) return "max_range must be finite and > 0";
+  if (q.max_candidates < 1u || q.max_candidates > (1u << 30)) return "max_candidates must be 1 .. 2^30";
+  return nullptr;
+}
+
 static int novelty_ready(suma_localizer* l, const char* who) {
   if (!l->nv.on) return fail(l->c, SUMA_ERR_INVALID, std::string(who) + ": novelty is off (suma_localizer_enable_novelty)");
   return SUMA_OK;
@@ -776,11 +849,7 @@ extern "C" int suma_localizer_enable_novelty(suma_localizer* l, const suma_novel
   suma_novel_params q;
   suma_novel_params_default(&q);
   if (np) q = *np;
-  const char* why = nullptr;
-  if (!(std::isfinite(q.agree_margin) && q.agree_margin > 0.0f)) why = "agree_margin must be finite and > 0";
-  else if (!(std::isfinite(q.max_range) && q.max_range > 0.0f)) why = "max_range must be finite and > 0";
-  else if (q.max_candidates < 1u || q.max_candidates > (1u << 30)) why = "max_candidates must be 1 .. 2^30";
-  if (why) return fail(c, SUMA_ERR_INVALID, std::string("suma_localizer_enable_novelty: ") + why);
+  if (const char* why = novel_params_why(q)) return fail(c, SUMA_ERR_INVALID, std::string("suma_localizer_enable_novelty: ") + why);
   Novel& nv = l->nv;
   const size_t P = (size_t)c->p.data_width * (size_t)c->p.data_height;
   const size_t blocks = (P + 255) / 256;
@@ -793,7 +862,6 @@ extern "C" int suma_localizer_enable_novelty(suma_localizer* l, const suma_novel
     if (e == hipSuccess) e = nw.flag.alloc(P);
     if (e == hipSuccess) e = nw.block_counts.alloc(8 * blocks);
     if (e == hipSuccess) e = nw.state.alloc(1);
-    if (e == hipSuccess) e = nw.stage_h.alloc(16);
     if (e != hipSuccess) {
       (void)hipGetLastError();
       return fail(c, SUMA_ERR_NOMEM, "suma_localizer_enable_novelty: no device memory for " +
@@ -803,7 +871,7 @@ extern "C" int suma_localizer_enable_novelty(suma_localizer* l, const suma_novel
     HIP_TRY(c, hipMemsetAsync(nw.mark, 0, P, c->stream));
     HIP_TRY(c, hipMemsetAsync(nw.flag, 0, P, c->stream)); /* suma_localizer_novel_flags in front of the first collection */
     nv = std::move(nw);
-    l->last_collected = 0;
+    forget_last(l, LAST_COLLECTION);
   }
   nv.np = q;
   nv.on = true;
@@ -812,26 +880,14 @@ extern "C" int suma_localizer_enable_novelty(suma_localizer* l, const suma_novel
 
 extern "C" int suma_localizer_disable_novelty(suma_localizer* l) {
   if (!l) return SUMA_ERR_INVALID;
-  suma_ctx* c = l->c;
-  if (l->nv.on) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a collection may still write them */
-    l->nv = Novel();
-    l->ob = Objects(); /* the segmentation reads the collection's flags: off with it */
-    l->lv = Live();    /* and so does the live layer */
-    l->tk = Tracks();  /* the tracks follow the segmentation */
-  }
-  l->last_collected = 0;
+  const int r = disable_layer(l, LAYER_NOVELTY);
+  if (r) return r;
+  forget_last(l, LAST_COLLECTION);
   return SUMA_OK;
 }
 
 /* the device state into host words (blocking): count, n_overflow, done, pad, counts[8] */
-static int novel_state(suma_localizer* l, NovelState* out) {
-  suma_ctx* c = l->c;
-  HIP_TRY(c, hipMemcpyAsync(l->nv.stage_h, l->nv.state, sizeof(NovelState), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  memcpy(out, l->nv.stage_h.p, sizeof(NovelState));
-  return SUMA_OK;
-}
+static int novel_state(suma_localizer* l, NovelState* out) { return read_words(l, l->nv.state, sizeof(NovelState), out); }
 
 static int novel_overflow(suma_localizer* l, const NovelState& s, const char* who) {
   if (!s.n_overflow) return SUMA_OK;
@@ -843,17 +899,11 @@ static int novel_overflow(suma_localizer* l, const NovelState& s, const char* wh
 extern "C" int suma_localizer_collect_frame(suma_localizer* l, const suma_frame* frame, const double T[16], uint32_t scan_id,
                                             suma_novel_counts* counts) {
   if (!l) return SUMA_ERR_INVALID;
-  suma_ctx* c = l->c;
   int r = novelty_ready(l, "suma_localizer_collect_frame");
+  if (!r) r = frame_pose_check(l, frame, T, "suma_localizer_collect_frame");
   if (r) return r;
-  if (!frame || !T) return fail(c, SUMA_ERR_INVALID, "suma_localizer_collect_frame: NULL argument");
-  if (frame->ctx != c) return fail(c, SUMA_ERR_INVALID, "suma_localizer_collect_frame: the frame belongs to another ctx");
-  if (frame->width != c->p.data_width || frame->height != c->p.data_height)
-    return fail(c, SUMA_ERR_INVALID, "suma_localizer_collect_frame: the frame must have the data image's size");
-  if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_collect_frame: non-finite pose");
   if (counts) memset(counts, 0, sizeof(*counts));
-  l->last_collected = 0;
-  l->ob.segmented = 0;
+  forget_last(l, LAST_COLLECTION | LAST_SEGMENTATION);
   if (!l->have_map || !l->n_window) return SUMA_OK;
   r = collect(l, frame, T, scan_id);
   if (r) return r;
@@ -892,13 +942,7 @@ static int candidates_download(suma_localizer* l, suma_world_surfel* out, uint32
   NovelState s;
   r = novel_state(l, &s);
   if (r) return r;
-  *n = s.count;
-  const uint32_t m = s.count < capacity ? s.count : capacity;
-  if (m) {
-    HIP_TRY(c, hipMemcpyAsync(out, l->nv.cand, (size_t)m * sizeof(suma_world_surfel),
-                              to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
+  if ((r = download(c, out, capacity, n, l->nv.cand, s.count, sizeof(suma_world_surfel), to_device))) return r;
   return novel_overflow(l, s, who);
 }
 
@@ -926,7 +970,7 @@ extern "C" int suma_localizer_set_novel_candidates(suma_localizer* l, const suma
     HIP_TRY(c, hipMemcpyAsync(&l->nv.state->count, &n, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream)); /* pageable sources: the copies have left them */
-  l->last_collected = 0;
+  forget_last(l, LAST_COLLECTION);
   return SUMA_OK;
 }
 
@@ -959,13 +1003,14 @@ static int novel_fused(suma_localizer* l, const suma_novel_fuse_params* fp, suma
     d_out = reinterpret_cast<suma_world_surfel*>(l->nv.fused.p);
     d_views = l->nv.fused_views;
   }
-  uint32_t cnt[3];
-  r = novel_fuse(c, l->nv, s.count, q, d_out, d_views, cap, cnt);
+  r = novel_fuse(c, l->nv, s.count, q, d_out, d_views, cap, l->stage_h);
   if (r) return r;
-  stats->n_dropped = cnt[0];
-  stats->n_voxels = cnt[1];
-  stats->n_out = cnt[2];
-  const uint32_t m = cnt[2] < cap ? cnt[2] : cap;
+  stats->n_dropped = l->stage_h.p[0];
+  stats->n_voxels = l->stage_h.p[1];
+  stats->n_out = l->stage_h.p[2];
+  /* the kernel has written a device caller's blocks itself; a host caller's two arrays go under one synchronise, which
+   * is why this site does not call download() twice */
+  const uint32_t m = stats->n_out < cap ? stats->n_out : cap;
   if (!to_device && m) {
     HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)m * sizeof(suma_world_surfel), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(views, d_views, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -990,13 +1035,7 @@ extern "C" int suma_localizer_novel_marks(suma_localizer* l, uint8_t* host, uint
   int r = novelty_ready(l, "suma_localizer_novel_marks");
   if (r) return r;
   if (!n || (capacity && !host)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_novel_marks: NULL argument");
-  *n = (uint32_t)c->p.data_width * (uint32_t)c->p.data_height;
-  const uint32_t m = *n < capacity ? *n : capacity;
-  if (m) {
-    HIP_TRY(c, hipMemcpyAsync(host, l->nv.mark, m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return SUMA_OK;
+  return download(c, host, capacity, n, l->nv.mark, (uint32_t)c->p.data_width * (uint32_t)c->p.data_height, 1, false);
 }
 
 extern "C" int suma_localizer_clear_novelty(suma_localizer* l) {
@@ -1005,8 +1044,7 @@ extern "C" int suma_localizer_clear_novelty(suma_localizer* l) {
   int r = novelty_ready(l, "suma_localizer_clear_novelty");
   if (r) return r;
   HIP_TRY(c, hipMemsetAsync(l->nv.state, 0, sizeof(NovelState), c->stream));
-  l->last_collected = 0;
-  l->ob.segmented = 0;
+  forget_last(l, LAST_COLLECTION | LAST_SEGMENTATION);
   if (l->tk.on && (r = tracks_clear(c, l->tk))) return r;
   return SUMA_OK;
 }
@@ -1062,7 +1100,7 @@ extern "C" int suma_localizer_enable_objects(suma_localizer* l, const suma_objec
   }
   ob.op = q;
   ob.on = true;
-  ob.segmented = 0;
+  forget_last(l, LAST_SEGMENTATION);
   if (l->tk.on && l->tk.max_objects != q.max_objects) { /* the tracker's blocks are sized by max_objects: made again */
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const suma_track_params tp = l->tk.tp;
@@ -1077,23 +1115,12 @@ extern "C" int suma_localizer_enable_objects(suma_localizer* l, const suma_objec
 }
 
 extern "C" int suma_localizer_disable_objects(suma_localizer* l) {
-  if (!l) return SUMA_ERR_INVALID;
-  suma_ctx* c = l->c;
-  if (l->ob.on) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a segmentation may still write them */
-    l->ob = Objects();
-    l->tk = Tracks(); /* the tracks follow the segmentation */
-  }
-  return SUMA_OK;
+  return l ? disable_layer(l, LAYER_OBJECTS) : SUMA_ERR_INVALID;
 }
 
 /* the counts of the last segmentation into host words (blocking) */
 static int objects_counts(suma_localizer* l, suma_object_counts* out) {
-  suma_ctx* c = l->c;
-  HIP_TRY(c, hipMemcpyAsync(l->ob.stage_h, l->ob.state, sizeof(suma_object_counts), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  memcpy(out, l->ob.stage_h.p, sizeof(*out));
-  return SUMA_OK;
+  return read_words(l, l->ob.state, sizeof(suma_object_counts), out);
 }
 
 static int objects_download(suma_localizer* l, suma_scan_object* out, uint32_t capacity, uint32_t* n,
@@ -1111,13 +1138,7 @@ static int objects_download(suma_localizer* l, suma_scan_object* out, uint32_t c
   r = objects_counts(l, &cnt);
   if (r) return r;
   if (counts) *counts = cnt;
-  *n = cnt.stored;
-  const uint32_t m = cnt.stored < capacity ? cnt.stored : capacity;
-  if (m) {
-    HIP_TRY(c, hipMemcpyAsync(out, l->ob.rec, (size_t)m * sizeof(suma_scan_object),
-                              to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
+  if ((r = download(c, out, capacity, n, l->ob.rec, cnt.stored, sizeof(suma_scan_object), to_device))) return r;
   if (cnt.n_objects > cnt.stored)
     return fail(c, SUMA_ERR_CAPACITY, std::string(who) + ": " + std::to_string(cnt.n_objects - cnt.stored) +
                                       " objects did not fit into max_objects = " + std::to_string(l->ob.op.max_objects));
@@ -1140,13 +1161,7 @@ extern "C" int suma_localizer_object_ids(suma_localizer* l, uint32_t* host, uint
   int r = objects_ready(l, "suma_localizer_object_ids");
   if (r) return r;
   if (!n || (capacity && !host)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_object_ids: NULL argument");
-  *n = l->ob.segmented ? l->ob.n_texels : 0u;
-  const uint32_t m = *n < capacity ? *n : capacity;
-  if (m) {
-    HIP_TRY(c, hipMemcpyAsync(host, l->ob.ids, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return SUMA_OK;
+  return download(c, host, capacity, n, l->ob.ids, l->ob.segmented ? l->ob.n_texels : 0u, sizeof(uint32_t), false);
 }
 
 extern "C" suma_frame* suma_localizer_frame(suma_localizer* l) { return l ? l->frame : nullptr; }
@@ -1157,38 +1172,27 @@ extern "C" int suma_localizer_novel_flags(suma_localizer* l, uint8_t* host, uint
   int r = novelty_ready(l, "suma_localizer_novel_flags");
   if (r) return r;
   if (!n || (capacity && !host)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_novel_flags: NULL argument");
-  *n = (uint32_t)c->p.data_width * (uint32_t)c->p.data_height;
-  const uint32_t m = *n < capacity ? *n : capacity;
-  if (m) {
-    HIP_TRY(c, hipMemcpyAsync(host, l->nv.flag, m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return SUMA_OK;
+  return download(c, host, capacity, n, l->nv.flag, (uint32_t)c->p.data_width * (uint32_t)c->p.data_height, 1, false);
 }
 
 extern "C" int suma_localizer_segment_flags(suma_localizer* l, const suma_frame* frame, const double T[16],
                                             const uint8_t* host_flags, uint32_t scan_id, suma_object_counts* counts) {
   if (!l) return SUMA_ERR_INVALID;
   suma_ctx* c = l->c;
-  int r = objects_ready(l, "suma_localizer_segment_flags");
+  const char* who = "suma_localizer_segment_flags";
+  int r = objects_ready(l, who);
   if (r) return r;
-  if (!frame || !T || !host_flags) return fail(c, SUMA_ERR_INVALID, "suma_localizer_segment_flags: NULL argument");
-  if (frame->ctx != c) return fail(c, SUMA_ERR_INVALID, "suma_localizer_segment_flags: the frame belongs to another ctx");
-  if (frame->width != c->p.data_width || frame->height != c->p.data_height)
-    return fail(c, SUMA_ERR_INVALID, "suma_localizer_segment_flags: the frame must have the data image's size");
-  if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_segment_flags: non-finite pose");
-  if (l->tk.on && (r = tracks_stamp_check(l, scan_id, "suma_localizer_segment_flags"))) return r;
+  if (!host_flags) return fail(c, SUMA_ERR_INVALID, "suma_localizer_segment_flags: NULL argument");
+  if ((r = frame_pose_check(l, frame, T, who))) return r;
+  if ((r = stamps_check(l, scan_id, who, false))) return r;
   if (counts) memset(counts, 0, sizeof(*counts));
   Objects& ob = l->ob;
-  ob.segmented = 0;
-  if (c->gate_pending) HIP_TRY(c, flush_gate(c));
-  const_cast<suma_frame*>(frame)->last_access = ++c->enq_seq;
+  forget_last(l, LAST_SEGMENTATION);
+  if ((r = frame_read_begin(c, frame))) return r;
   HIP_TRY(c, hipMemcpyAsync(ob.flags_in, host_flags, ob.n_texels, hipMemcpyHostToDevice, c->stream));
-  r = objects_segment(c, ob, frame, ob.flags_in, T, scan_id);
-  if (!r && l->tk.on) r = track_segmentation(l, scan_id);
+  r = run_layers(l, frame, ob.flags_in, T, scan_id, false);
   HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a pageable source: the copy has left it */
   if (r) return r;
-  ob.segmented = 1;
   return counts ? objects_counts(l, counts) : SUMA_OK;
 }
 
@@ -1247,13 +1251,7 @@ extern "C" int suma_localizer_enable_live_grid(suma_localizer* l, const suma_gri
 }
 
 extern "C" int suma_localizer_disable_live_grid(suma_localizer* l) {
-  if (!l) return SUMA_ERR_INVALID;
-  suma_ctx* c = l->c;
-  if (l->lv.on) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* an update may still write them */
-    l->lv = Live();
-  }
-  return SUMA_OK;
+  return l ? disable_layer(l, LAYER_LIVE) : SUMA_ERR_INVALID;
 }
 
 extern "C" int suma_localizer_clear_live_grid(suma_localizer* l) {
@@ -1265,11 +1263,7 @@ extern "C" int suma_localizer_clear_live_grid(suma_localizer* l) {
 
 /* words first .. first + n - 1 of the layer into host words (blocking) */
 static int live_words(suma_localizer* l, uint32_t first, uint32_t n, void* out) {
-  suma_ctx* c = l->c;
-  HIP_TRY(c, hipMemcpyAsync(l->lv.stage_h.p + first, l->lv.words.p + first, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  memcpy(out, l->lv.stage_h.p + first, n * sizeof(uint32_t));
-  return SUMA_OK;
+  return read_words(l, l->lv.words.p + first, n * sizeof(uint32_t), out);
 }
 
 extern "C" int suma_localizer_live_update_flags(suma_localizer* l, const suma_frame* frame, const double T[16],
@@ -1279,13 +1273,9 @@ extern "C" int suma_localizer_live_update_flags(suma_localizer* l, const suma_fr
   const char* who = "suma_localizer_live_update_flags";
   int r = live_ready(l, who);
   if (r) return r;
-  if (!frame || !T || !host_flags) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_update_flags: NULL argument");
-  if (frame->ctx != c) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_update_flags: the frame belongs to another ctx");
-  if (frame->width != c->p.data_width || frame->height != c->p.data_height)
-    return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_update_flags: the frame must have the data image's size");
-  if (!finite16(T)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_update_flags: non-finite pose");
-  if ((r = live_stamp_check(l, scan_id, who))) return r;
-  if (l->tk.on && (r = tracks_stamp_check(l, scan_id, who))) return r;
+  if (!host_flags) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_update_flags: NULL argument");
+  if ((r = frame_pose_check(l, frame, T, who))) return r;
+  if ((r = stamps_check(l, scan_id, who, true))) return r;
   if (counts) memset(counts, 0, sizeof(*counts));
   Objects& ob = l->ob;
   Live& lv = l->lv;
@@ -1295,16 +1285,12 @@ extern "C" int suma_localizer_live_update_flags(suma_localizer* l, const suma_fr
     if ((r = grow(c, lv.flags_in, P, {c->stream})) < 0) return r;
     d_flags = lv.flags_in;
   }
-  ob.segmented = 0;
-  if (c->gate_pending) HIP_TRY(c, flush_gate(c));
-  const_cast<suma_frame*>(frame)->last_access = ++c->enq_seq;
+  forget_last(l, LAST_SEGMENTATION);
+  if ((r = frame_read_begin(c, frame))) return r;
   HIP_TRY(c, hipMemcpyAsync(d_flags, host_flags, P, hipMemcpyHostToDevice, c->stream));
-  r = ob.on ? objects_segment(c, ob, frame, d_flags, T, scan_id) : SUMA_OK;
-  if (!r && l->tk.on) r = track_segmentation(l, scan_id);
-  if (!r) r = live_update(c, lv, frame, d_flags, ob.on ? ob.ids.p : nullptr, T, scan_id + 1u);
+  r = run_layers(l, frame, d_flags, T, scan_id, true);
   HIP_TRY(c, hipStreamSynchronize(c->stream)); /* a pageable source: the copy has left it */
   if (r) return r;
-  if (ob.on) ob.segmented = 1;
   return counts ? live_words(l, 0, LIVE_COUNT_WORDS, counts) : SUMA_OK;
 }
 
@@ -1340,13 +1326,7 @@ extern "C" int suma_localizer_live_state(suma_localizer* l, suma_live_cell* host
   int r = live_ready(l, "suma_localizer_live_state");
   if (r) return r;
   if (!n || (capacity && !host)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_live_state: NULL argument");
-  *n = l->lv.n_cells;
-  const uint32_t m = *n < capacity ? *n : capacity;
-  if (m) {
-    HIP_TRY(c, hipMemcpyAsync(host, l->lv.state, (size_t)m * sizeof(suma_live_cell), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return SUMA_OK;
+  return download(c, host, capacity, n, l->lv.state, l->lv.n_cells, sizeof(suma_live_cell), false);
 }
 
 extern "C" int suma_localizer_set_live_state(suma_localizer* l, const suma_live_cell* host, uint32_t n, uint32_t last_stamp) {
@@ -1432,13 +1412,7 @@ extern "C" int suma_localizer_enable_tracks(suma_localizer* l, const suma_track_
 }
 
 extern "C" int suma_localizer_disable_tracks(suma_localizer* l) {
-  if (!l) return SUMA_ERR_INVALID;
-  suma_ctx* c = l->c;
-  if (l->tk.on) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream)); /* an update may still write them */
-    l->tk = Tracks();
-  }
-  return SUMA_OK;
+  return l ? disable_layer(l, LAYER_TRACKS) : SUMA_ERR_INVALID;
 }
 
 extern "C" int suma_localizer_clear_tracks(suma_localizer* l) {
@@ -1450,11 +1424,7 @@ extern "C" int suma_localizer_clear_tracks(suma_localizer* l) {
 
 /* the words of the tracker into host words (blocking) */
 static int tracks_words(suma_localizer* l, uint32_t* out) {
-  suma_ctx* c = l->c;
-  HIP_TRY(c, hipMemcpyAsync(l->tk.stage_h, l->tk.words, TRK_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  memcpy(out, l->tk.stage_h.p, TRK_WORDS * sizeof(uint32_t));
-  return SUMA_OK;
+  return read_words(l, l->tk.words, TRK_WORDS * sizeof(uint32_t), out);
 }
 
 static int tracks_download(suma_localizer* l, suma_object_track* out, uint32_t capacity, uint32_t* n, suma_track_counts* counts,
@@ -1473,13 +1443,7 @@ static int tracks_download(suma_localizer* l, suma_object_track* out, uint32_t c
   suma_track_counts cnt;
   memcpy(&cnt, w, sizeof(cnt));
   if (counts) *counts = cnt;
-  *n = w[TRK_N_LIVE];
-  const uint32_t m = *n < capacity ? *n : capacity;
-  if (m) {
-    HIP_TRY(c, hipMemcpyAsync(out, l->tk.out, (size_t)m * sizeof(suma_object_track),
-                              to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
+  if ((r = download(c, out, capacity, n, l->tk.out, w[TRK_N_LIVE], sizeof(suma_object_track), to_device))) return r;
   if (cnt.n_dropped)
     return fail(c, SUMA_ERR_CAPACITY, std::string(who) + ": " + std::to_string(cnt.n_dropped) +
                                       " detections found no free slot among max_tracks = " + std::to_string(l->tk.tp.max_tracks));
@@ -1506,13 +1470,7 @@ extern "C" int suma_localizer_object_tracks(suma_localizer* l, uint32_t* host, u
   if (!l->tk.updated) return SUMA_OK;
   uint32_t w[TRK_WORDS];
   if ((r = tracks_words(l, w))) return r;
-  *n = w[0]; /* n_objects */
-  const uint32_t m = *n < capacity ? *n : capacity;
-  if (m) {
-    HIP_TRY(c, hipMemcpyAsync(host, l->tk.objtrack, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return SUMA_OK;
+  return download(c, host, capacity, n, l->tk.objtrack, w[0] /* n_objects */, sizeof(uint32_t), false);
 }
 
 extern "C" int suma_localizer_track_objects(suma_localizer* l, const suma_scan_object* host_objects, uint32_t n, uint32_t scan_id,
@@ -1527,7 +1485,7 @@ extern "C" int suma_localizer_track_objects(suma_localizer* l, const suma_scan_o
   if (n > tk.max_objects)
     return fail(c, SUMA_ERR_INVALID, "suma_localizer_track_objects: " + std::to_string(n) + " records, max_objects = " +
                                      std::to_string(tk.max_objects));
-  if ((r = tracks_stamp_check(l, scan_id, who))) return r;
+  if ((r = stamp_check(l, scan_id, tk.last_stamp, "the tracks", who))) return r;
   if (counts) memset(counts, 0, sizeof(*counts));
   if (n) HIP_TRY(c, hipMemcpyAsync(tk.rec_in, host_objects, (size_t)n * sizeof(suma_scan_object), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(tk.words.p + TRK_N_IN, &n, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
@@ -1548,17 +1506,12 @@ extern "C" int suma_localizer_track_state(suma_localizer* l, suma_object_track* 
   int r = tracks_ready(l, "suma_localizer_track_state");
   if (r) return r;
   if (!n || (capacity && !host)) return fail(c, SUMA_ERR_INVALID, "suma_localizer_track_state: NULL argument");
-  *n = l->tk.tp.max_tracks;
+  *n = l->tk.tp.max_tracks; /* also when the read below fails */
   uint32_t w[TRK_WORDS];
   if ((r = tracks_words(l, w))) return r;
   if (last_stamp) *last_stamp = l->tk.last_stamp;
   if (next_id) *next_id = w[TRK_BORN_TOTAL] + 1u;
-  const uint32_t m = *n < capacity ? *n : capacity;
-  if (m) {
-    HIP_TRY(c, hipMemcpyAsync(host, l->tk.slots, (size_t)m * sizeof(suma_object_track), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return SUMA_OK;
+  return download(c, host, capacity, n, l->tk.slots, l->tk.tp.max_tracks, sizeof(suma_object_track), false);
 }
 
 extern "C" int suma_localizer_set_track_state(suma_localizer* l, const suma_object_track* host, uint32_t n, uint32_t last_stamp,
